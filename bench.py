@@ -2,8 +2,11 @@
 """Headline benchmark: candidate edges scored per second on a ppa-like graph (BASELINE.json configs[2]:
 "ogbl-ppa Adamic-Adar scoring of full non-edge candidate set, 1xMI355X").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+--dump-outputs DIR writes the rows the last timed step returned (scan.scan_topk's pairs and scores) as DIR/pairs.npy and
+DIR/scores.npy; the graph is seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (synthetic, seeded; no dataset / network exists on either box)
   graph : S3 "ppa-like" -- N = 576,289 nodes, ~21.2 M undirected edges (nnz ~42.5 M, avg degree ~74), R-MAT skew,
@@ -45,6 +48,8 @@ HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s 
 MFMA_F32_PEAK_TF = 157.3   # fp32-input MFMA, dense
 CPU_SAMPLE = 4_000_000     # candidate pairs timed through the single-thread SciPy mirror (~10-20 s)
 PAIR_LEG = 1 << 25
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together; a larger output is written as a seeded sample of its rows
+DUMP_SEED = 0
 
 
 def _events(torch, n):
@@ -65,6 +70,30 @@ def _timed_loop(torch, fn, reps, warmup=2, batch=1):
         b.record(s)
     torch.cuda.synchronize()
     return sum(a.elapsed_time(b) for a, b in evs) / reps / batch
+
+
+def dump_outputs(path, pairs, scores, n_nodes):
+    """--dump-outputs: what a caller of scan.scan_topk receives from the last timed step -- pairs [2, K] (u; v) and scores [K] --
+    as ``path``/pairs.npy and ``path``/scores.npy.  Node ids are written as float32 when every id of the graph is exact in it
+    (N <= 2^24; decided by the graph, not by the data, so two builds write the same dtype), else float64; scores stay float32.
+    When the whole exceeds DUMP_MAX_BYTES the same DUMP_SEED-seeded sample of rows (ascending) is taken from both arrays."""
+    import numpy as np
+    id_dtype = np.float32 if n_nodes <= (1 << 24) else np.float64
+    p = pairs.cpu().numpy().astype(id_dtype)
+    s = scores.cpu().numpy().astype(np.float32)
+    rows = s.shape[0]
+    row_bytes = 2 * p.itemsize + s.itemsize
+    sampled = None
+    budget = DUMP_MAX_BYTES - 2 * 4096                           # (the two .npy headers)
+    if rows * row_bytes > budget:
+        sampled = budget // row_bytes
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, sampled, replace=False))
+        p, s = p[:, idx], s[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pairs.npy"), np.ascontiguousarray(p))
+    np.save(os.path.join(path, "scores.npy"), s)
+    return {"dir": path, "rows": rows, "sampled_rows": sampled, "seed": DUMP_SEED if sampled else None,
+            "arrays": {"pairs": [list(p.shape), str(p.dtype)], "scores": [list(s.shape), str(s.dtype)]}}
 
 
 # ------------------------------------------------------------------------------------------------ secondary legs
@@ -341,7 +370,14 @@ def parse_args(argv=None):
     ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the extra sustained loop (0: skip)")
     ap.add_argument("--nodes", type=int, default=576_289, help="graph size (tests use a small one)")
     ap.add_argument("--edges", type=int, default=21_231_931)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last timed step returned as DIR/pairs.npy and DIR/scores.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -485,6 +521,9 @@ def run(args):
     barrier()
     dt = time.perf_counter() - t0
     events, ops.KERNEL_EVENTS, ops.EVENT_NAMES = ops.KERNEL_EVENTS, None, None
+    dumped = None
+    if args.dump_outputs and rank == 0:                         # (strong scaling: the rows are gathered on rank 0, rows_on=0)
+        dumped = dump_outputs(args.dump_outputs, out["r"][0], out["r"][1], g.n_rows)
     # where the rest of a step goes (`step_breakdown_ms`, `sharded_ms_per_rank`): a second, short loop with events around EVERY
     # library call -- some forty event records per step, which cost the host 0.4 ms a step when they sat in the timed region
     bd_steps = max(1, min(args.steps, 20))
@@ -639,6 +678,7 @@ def run(args):
             "replicated_ms": ms_step - max(r[2] for r in per_rank),
             "step_breakdown_ms": per_step,
             "sustained": sustained,
+            "dump_outputs": dumped,
             "config": {"workload": "configs[2] ppa-like S3, full candidate set: N=%d, nnz=%d, %d directed 2-hop non-edge "
                                    "candidates per graph, filter.py --model adamic_ogb --keep_top %d (scan.scan_topk)"
                                    % (g.n_rows, g.nnz(), n_cand, args.keep_top),
