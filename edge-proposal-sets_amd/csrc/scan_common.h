@@ -5,6 +5,7 @@
 
 #define SP_M 32                 // id windows per graph (one 64-byte row of cuts per node); 48 windows: 1.99 M instead of 2.03 M pieces, -0.5 % (r04)
 #define SP_FLAG 0x80000000u      // value word of a KNOWN EDGE's endpoint (put in before the walk): sums stay below 2^31, so the bit survives them
+                                 // (not in sketch pieces: they put no flags in, their estimates may reach 2^32 - 1 and are compared unsigned)
 
 #if defined(__HIPCC__)
 // The bar in the table's domain.  filter_scan.hip keeps a candidate when its 2^-40 fixed-point sum a satisfies

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void sp_refine_kernel(const eps_survivors *__r
     for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < n; i0 += stride) {
         const int64_t i = i0 + lane;
         const int64_t key = i < n ? in_key[i] : -1;
-        uint32_t total = 0u;
+        unsigned long long total = 0ull;   // (64 bits: a sketch piece's estimate may reach 2^32 - 1, and the head term comes on top)
         bool pass = false;
         if (key >= 0) {
             const int32_t v = (int32_t)(key >> 32), u = (int32_t)(key & 0xFFFFFFFFll);
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(256) void sp_refine_kernel(const eps_survivors *__r
                 }
                 out_of_reach = (unsigned long long)s_walk + c + rem < (unsigned long long)thr32;
             }
-            total = s_walk + c;
-            pass = !out_of_reach && total >= thr32;
+            total = (unsigned long long)s_walk + c;
+            pass = !out_of_reach && total >= (unsigned long long)thr32;
         }
         const unsigned long long m = __ballot(pass);
         if (m) {

@@ -635,6 +635,8 @@ def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, bo
     out.walked_slots = None
     if screen is not None:
         out.status = torch.empty(1, dtype=torch.int32, device=g.device)      # (cleared by eps_scan_screen itself)
+        if not columns.numel():
+            out.status.zero_()           # (no launch clears it: a rank with no columns reports a clean status, not stale memory)
     if columns.numel():
         if screen is not None and heads is not None:
             bounds, cuts = screen_tables(g)

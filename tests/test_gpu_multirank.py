@@ -147,7 +147,8 @@ def test_bench_self_launch_from_plain_shell(dev, tmp_path):
     assert 0 < line["roofline"]["frac"] <= 1 and line["value_unordered_pairs_per_s"] * 2 == pytest.approx(line["value"])
 
 
-def _relabelled_scan_rank_main(rank, world, port, workdir, dist_rows_min=0, rows_on=None, kind="aa", k=30000, dist_hist=True):
+def _relabelled_scan_rank_main(rank, world, port, workdir, dist_rows_min=0, rows_on=None, kind="aa", k=30000, dist_hist=True,
+                               graph=None):
     sys.path.insert(0, ROOT)
     os.chdir(workdir)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
@@ -162,13 +163,14 @@ def _relabelled_scan_rank_main(rank, world, port, workdir, dist_rows_min=0, rows
     scan.DIST_ROWS_MIN = dist_rows_min               # 0: the final ordering is dealt over the ranks by score range
     scan.DIST_HIST = dist_hist                       # the step's one exchange: score histograms (r06) or the scores themselves (r05)
     dev = torch.device("cuda:0")
-    g = synth.rmat_graph(13, 10, 21, dev)
+    g = synth.rmat_graph(13, 10, 21, dev) if graph is None else graph().to(dev)
     w = torch.ones(g.n_rows, dtype=torch.float32, device=dev) if kind == "cn" else node_weight_table(g, ops.W_AA)
     st = {}
     pairs, scores = scan.scan_topk(g, w, k, rank, world, relabel=True, rows_on=rows_on, stats=st)
     assert scan.scan_graph(g)[1] is not None
     assert (pairs is None) == (rows_on is not None and rows_on != "shards" and rank != rows_on)
-    torch.save(None if pairs is None else (pairs.cpu(), scores.cpu(), st.get("shard")), f"scan_rank{rank}.pt")
+    n_cols = scan.shard_columns(scan.scan_graph(g)[0], rank, world).numel()        # (this rank's column list)
+    torch.save(None if pairs is None else (pairs.cpu(), scores.cpu(), st.get("shard"), n_cols), f"scan_rank{rank}.pt")
     torch.distributed.destroy_process_group()
 
 
@@ -187,7 +189,7 @@ def test_scan_two_ranks_hubs_first_labels(eps, dev, tmp_path, world, dist_rows_m
     mp.spawn(_relabelled_scan_rank_main, args=(world, _free_port(), str(tmp_path), dist_rows_min, rows_on), nprocs=world, join=True)
     if rows_on == "shards":
         # (r06) every rank keeps the chunk of the declared order it ordered: the chunks, in rank order, ARE the single-process rows
-        parts = [torch.load(os.path.join(tmp_path, f"scan_rank{r}.pt")) for r in range(world)]
+        parts = [torch.load(os.path.join(tmp_path, f"scan_rank{r}.pt"))[:3] for r in range(world)]
         total = parts[0][2][1]
         at = 0
         for p, s, shard in parts:
@@ -202,7 +204,7 @@ def test_scan_two_ranks_hubs_first_labels(eps, dev, tmp_path, world, dist_rows_m
         if rows_on is not None and r != rows_on:          # (the rows travel to one rank only)
             assert got is None
             continue
-        p, s, _ = got
+        p, s = got[:2]
         assert torch.equal(p, want_p.cpu()) and torch.equal(s, want_s.cpu())
 
 
@@ -219,7 +221,32 @@ def test_scan_ranks_tied_levels_beyond_the_room(eps, dev, tmp_path, world, dist_
     want_p, want_s = scan.scan_topk(g, ones, 3000)
     mp.spawn(_relabelled_scan_rank_main, args=(world, _free_port(), str(tmp_path), 0, None, "cn", 3000, dist_hist), nprocs=world, join=True)
     for r in range(world):
-        p, s, _ = torch.load(os.path.join(tmp_path, f"scan_rank{r}.pt"))
+        p, s = torch.load(os.path.join(tmp_path, f"scan_rank{r}.pt"))[:2]
+        assert torch.equal(p, want_p.cpu()) and torch.equal(s, want_s.cpu())
+
+
+def _short_path_graph():
+    """0 - 1 - 2: three columns, one candidate pair."""
+    from eps_amd.graph import CSRGraph
+    ei = torch.tensor([[0, 1], [1, 2]], dtype=torch.int64)
+    return CSRGraph.from_edge_index(ei, None, sparse_sizes=(3, 3)).to_symmetric()
+
+
+def test_scan_ranks_more_than_columns(eps, dev, tmp_path):
+    """a rank whose column list is EMPTY (here more ranks than a three-node graph has columns) launches no kernel
+    that clears its status word -- the step must still read a clean status from it, not stale memory (which reads as a full hash
+    table or a void sketch launch).  Every rank ends with the single-process rows."""
+    from eps_amd import scan
+    from eps_amd.heuristics import node_weight_table
+    g = _short_path_graph().to(dev)
+    want_p, want_s = scan.scan_topk(g, node_weight_table(g, eps.ops.W_AA), 2)
+    assert sorted(map(tuple, want_p.t().tolist())) == [(0, 2), (2, 0)]
+    world = 4
+    mp.spawn(_relabelled_scan_rank_main, args=(world, _free_port(), str(tmp_path), 0, None, "aa", 2, True, _short_path_graph),
+             nprocs=world, join=True)
+    got = [torch.load(os.path.join(tmp_path, f"scan_rank{r}.pt")) for r in range(world)]
+    assert min(n for *_, n in got) == 0, "the precondition: some rank's column list is empty"
+    for p, s, _, _ in got:
         assert torch.equal(p, want_p.cpu()) and torch.equal(s, want_s.cpu())
 
 
