@@ -23,6 +23,7 @@ runs on every rank -- no collective on the data path.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import List, Optional, Tuple
 
 import torch
@@ -36,8 +37,6 @@ SMALL_SET = 1 << 25        # candidate sets with at most this many two-hop half 
 MAX_K = 1 << 30            # rows a survivor list (< 2^32 slots, handed out in chunks) can be asked for; beyond: block streaming
 MAX_LAUNCHES = 8           # estimate -> scan -> correct rounds before giving up (two are the rule)
 _CHUNK_SLACK = 8192 * 320  # survivor slots are handed out in chunks of 8192 per workgroup
-PLAN_TABLE = True            # eps_scan_screen reads a per-graph table of every column's pieces instead of planning in the launch
-PACKED_PIECES = True         # eps_scan_screen may keep key and sum of a candidate in one table word (see _sum_bounds)
 RELABEL_MIN_NODES = 100_000  # graphs at least this large are scanned under hubs-first labels (see scan_graph)
 ONE_PASS = True            # score with the one-pass piece kernel (csrc/scan_pieces.hip) where the graph qualifies, else eps_filter_scan
 _PIECE_SLACK = 8192 * 1024 + 65536   # eps_scan_screen hands slots out in chunks of <= 32768 per workgroup (<= 1024 workgroups)
@@ -59,7 +58,7 @@ def _sharded(world: int) -> bool:
     return world > 1 or FORCE_SHARDED
 
 
-SKETCH_PIECES = True          # r06: in the main launch (heads, under a bar) the packed pieces of single-round columns keep no keys -- a
+SKETCH_PIECES = True          # in the main launch (heads, under a bar) the packed pieces of single-round columns keep no keys -- a
                               # count-min sketch of two half tables, non-returning adds, a second look at the paths (csrc/scan_pieces.hip)
 SKETCH_MIN_PATHS = 1.5        # ... when the bar is at least this many of the HEAVIEST node weight: a tail candidate then needs several paths to
                               # reach it and most sketch pieces end at their read sweep; resource allocation (weights up to 1 under a bar of 0.085
@@ -68,7 +67,6 @@ SKETCH_WIDE = True            # ... and their head tables carry a plan whose pac
                               # no keys to run out of slots for): 1.20 M -> 0.98 M pieces on the ppa-like graph, 7.25 -> 6.75 ms
 SKETCH_SET = 0                # slots of a sketch piece's set of reported ids (a power of two <= 64; 0 = the kernel's 128): tests shrink it
 LAZY_PLAN = True              # the whole-graph plan table (no skipped heads) is built when a launch first wants it; the bar sample plans itself
-ROW_RECORDS = True            # the launch gathers a row's cuts, first entry and weight out of ONE 128-byte line (ops.scan_row_records)
 BATCH_MIN_COLUMNS = 1 << 16   # lists shorter than this are handed out one column at a time throughout
 BATCH_PATHS = 1 << 13      # columns of a heaviest-first list with fewer half paths are handed out eight per ticket (see batch_from)
 
@@ -291,7 +289,7 @@ class Screen:
     def __init__(self, fx32, shift, fixw, val, node_w, usable, ssum=None, smax=None, plan=None, d_used=0, w_min=0.0):
         self.fx32, self.shift, self.fixw, self.val, self.node_w, self.usable = fx32, shift, fixw, val, node_w, usable
         self.ssum, self.smax, self._plan = ssum, smax, plan
-        self._plan_build = None      # r06: () -> ((pptr, records), bits dropped): the whole-graph plan is built when a launch WITHOUT
+        self._plan_build = None      # () -> ((pptr, records), bits dropped): the whole-graph plan is built when a launch WITHOUT
                                      # skipped heads first asks for it (see `plan`); a one-shot run under a bar never does
         self.d_used = d_used         # most low bits any packed / 16-bit direct piece drops from the screening weights
         self.w_min = w_min           # smallest weight of a node that can be a common neighbour (0: no relative bound)
@@ -364,7 +362,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
             return Screen(None, shift, None, g.val, nw, fits and bool((nw >= 0).all().item()))
         fixw = _scan_weights(g0, g, perm, node_w)
         if fixw.numel():
-            # (r06) the heaviest screening weight stays below 2^19: 8192 of them -- a whole sketch piece hashed into ONE slot -- cannot
+            # the heaviest screening weight stays below 2^19: 8192 of them -- a whole sketch piece hashed into ONE slot -- cannot
             # wrap a 32-bit slot, so a sketch table's sums are upper bounds whatever collides (one more host read when a weight table's
             # screen is built; Adamic-Adar on the ppa-like graph: 1 / ln 2 x 2^19 -> shift 18)
             # (... when that costs one bit at most: resource allocation -- weights from 1 down to 1 / 13 230 -- would lose three and
@@ -376,11 +374,11 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
         # Everything is launched before anything is read back: the verdict on the weights (`bad`), the bits the plan drops and the
         # smallest weight come back in ONE host read at the end (tables built from unusable weights are simply not used).
         one_pass = fits and one_pass_available(g)
-        ssum, smax, min_fx = _sum_bounds(g, fx32) if one_pass and PACKED_PIECES else (None, None, None)
+        ssum, smax, min_fx = _sum_bounds(g, fx32) if one_pass else (None, None, None)
         plan, d_word, plan_build = None, None, None
         vword = screen_variant(g)
         dmax_limit = max(0, min(24, shift - 8))                   # (csrc/scan_pieces.hip: packed_dmax)
-        if one_pass and PLAN_TABLE:
+        if one_pass:
             # How many low weight bits a piece may drop: a screening score exceeds the exact one by up to 2^d + 1 units per path, and
             # the pre-filter in front of the exact re-scoring (lower_params) is as sharp as that is small next to the smallest
             # weight -- DMAX_MARGIN bits below it (one host read; resource allocation on a graph with hubs weighs 1 / 13 230: at the
@@ -389,8 +387,8 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
             if lowest not in (0, 0xFFFFFFFF):
                 dmax_limit = min(dmax_limit, max(0, lowest.bit_length() - 1 - DMAX_MARGIN))
                 vword = ops.scan_variant_word(screen_variant(g), max(0, lowest.bit_length() - 1 - DMAX_MARGIN))
-            # every column's pieces, planned once per (graph, weight table): a launch reads them instead of planning (5 %) -- r06:
-            # planned when a launch without skipped heads first wants them (Screen.plan); LAZY_PLAN off: here and now, as in r05
+            # every column's pieces, planned once per (graph, weight table): a launch reads them instead of planning (5 %) -- when
+            # a launch without skipped heads first wants them (Screen.plan); LAZY_PLAN off: here and now
             vword_plan = vword
 
             def plan_build():
@@ -408,7 +406,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
                                                    f_lo.view(1), f_hi.view(1)]).tolist()
         bad_h, d_h, min_h = bad_h & 0xFFFFFFFF, d_h & 0xFFFFFFFF, min_h & 0xFFFFFFFF
         usable = fits and bad_h == 0
-        rowrec = ops.scan_row_records(screen_tables(g)[1], g.rowptr, fx32) if usable and one_pass and ROW_RECORDS else None
+        rowrec = ops.scan_row_records(screen_tables(g)[1], g.rowptr, fx32) if usable and one_pass else None
         if not usable:
             ssum = smax = plan = plan_build = None
         d_used, w_min = 0, 0.0
@@ -419,7 +417,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
             lowest = min_h & 0xFFFFFFFF
             w_min = 0.0 if lowest == 0xFFFFFFFF else max(0, lowest - 1) * 2.0 ** -shift
         sc = Screen(fx32, shift, fixw, None, None, usable, ssum, smax, plan, d_used, w_min)
-        sc._plan_build = plan_build if one_pass and PLAN_TABLE and usable else None
+        sc._plan_build = plan_build
         sc.rowrec = rowrec
         sc.vword = vword
         sc.w_max_units = float(f_hi) * 2.0 ** (shift - 40)      # the heaviest node weight in screening units (see SKETCH_MIN_PATHS)
@@ -525,14 +523,11 @@ def live_columns(g: CSRGraph, screen: Screen, ht: HeadTables, rank: int, world: 
     return ht.live[key]
 
 
-COLUMN_RECORDS = True         # a launch reads a column's header as one 32-byte record in hand-out order (column_records)
-
-
 def column_records(g: CSRGraph, screen: Screen, columns: torch.Tensor, plan, heads: Optional[torch.Tensor], cache: dict, key):
     """int32 [len(columns), 8], cached in ``cache[key]``: per column of the hand-out list {v, rowptr[v], degree, head rows, head
     weight, row sum, first plan record, pieces} -- what the kernel's column set-up otherwise reads through a chain of dependent
     loads into five tables (plain gathers here: the list, the plan and the head table are fixed once built)."""
-    if not COLUMN_RECORDS or plan is None or columns.numel() == 0:
+    if plan is None or columns.numel() == 0:
         return None
     if key not in cache:
         c = columns.long()
@@ -669,8 +664,7 @@ def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, bo
 
 def variant_is_main(g: CSRGraph, screen: Screen) -> bool:
     """The launch is the one the specialised body serves (csrc/scan_pieces.hip FULL): 256-thread geometry, plan, records, sum bounds."""
-    return bool(screen_variant(g) == 2 and screen.has_plan and screen.rowrec is not None and screen.ssum is not None
-                and COLUMN_RECORDS)
+    return bool(screen_variant(g) == 2 and screen.has_plan and screen.rowrec is not None and screen.ssum is not None)
 
 
 def sample_window_paths(g: CSRGraph, columns: torch.Tensor, key) -> torch.Tensor:
@@ -765,7 +759,6 @@ def sample_columns(g: CSRGraph, stride: int, rank: int = 0, world: int = 1):
     return g._cache[key]
 
 
-BAR_FROM_HISTOGRAM = True  # repeated scans of a graph at the same K read the bar estimate off a score histogram around the previous bar
 SAMPLE_RANK = 4096         # the sample is thinned (stride doubled) while the rank read off it stays at least this large
 
 
@@ -811,9 +804,9 @@ def estimate_bar(g: CSRGraph, fixw: torch.Tensor, k: int, stride: Optional[int] 
     # takes the lowest of them (one all-reduce of a word).  Any bar is a valid bar: the verification after the main launch is
     # what makes the result exact.
     m_loc = m if world == 1 else (m + world - 1) // world
-    hint = screen.bar_hint.get((k, stride, float(safety))) if BAR_FROM_HISTOGRAM else None
+    hint = screen.bar_hint.get((k, stride, float(safety)))
     if hint is not None and hint > 0.0:
-        # r06: a graph that is scanned again reads the bar off a score-bucket histogram around the bar its last scan at this K
+        # a graph that is scanned again reads the bar off a score-bucket histogram around the bar its last scan at this K
         # ended with (two short launches instead of the four-round select): buckets are 2^-8 of a score's distance to the base --
         # half the old bar -- so the value is at most 0.4 % below the exact order statistic: an estimate either way, and the
         # verification after the main launch is what makes the step exact.  A sample whose m-th best fell below the base answers
@@ -963,8 +956,8 @@ def _deal_rows(keys: torch.Tensor, vals: torch.Tensor, sp: torch.Tensor, c: List
     """The k best directed rows, ordered by the declared rule, when every rank holds its OWN selected pairs (keys, vals) and the
     deal plan (``_deal_plan``: splitters on the device, the counts table read back with the step's status).  The final ordering
     is dealt over the ranks by score range: ONE all-to-all moves each selected pair to the rank that orders its range (1 / world
-    of the pairs arrive per rank, not all of them on every rank as in r04), the rank mirrors and sorts them, and the sorted chunks
-    go to ``rows_on`` (or to everyone) in rank order = the declared order.  No host read of its own."""
+    of the pairs arrive per rank), the rank mirrors and sorts them, and the sorted chunks go to ``rows_on`` (or to everyone) in
+    rank order = the declared order.  No host read of its own."""
     from . import dist as epd
     rng = (vals.unsqueeze(1) < sp.unsqueeze(0)).sum(1)
     order = torch.sort(rng, stable=True).indices                                      # own pairs, grouped by destination
@@ -975,7 +968,7 @@ def _deal_rows(keys: torch.Tensor, vals: torch.Tensor, sp: torch.Tensor, c: List
     rk, rv = ops.select_rows(mk, mv, 2 * m, bits, perm)                                # all 2 m rows of the range, ordered
     lens = [2 * sum(c[r][q] for r in range(world)) for q in range(world)]
     if rows_on == "shards":
-        # (r06) the rows stay where they were ordered: this rank's chunk is rows [offset, offset + len) of the declared order, cut
+        # the rows stay where they were ordered: this rank's chunk is rows [offset, offset + len) of the declared order, cut
         # where the first k rows end -- no gather of 48 MB onto one rank; the proposal file is written as one shard per rank and
         # read back in rank order (proposals.load_proposals)
         offset = sum(lens[:rank])
@@ -1003,6 +996,275 @@ def _capacity(slots_wanted: int, slack: Optional[int] = None) -> int:
     return cap
 
 
+# _verdict's result: the next action, the launches counted, whether the next launch under a bar takes a head table built for its
+# bar (drop_heads: screen.head_cur = None), and the call's walked-list overflows and head tables built for another bar
+Verdict = namedtuple("Verdict", "action launches drop_heads head_trouble head_stale")
+
+
+def _verdict(table, capacity: int, walked_cap: int, head_budget: Optional[int], shift: Optional[int], screened: bool,
+             rescore_all: bool, k2: int, bar_set: bool, launches: int, head_trouble: int = 0, head_stale: int = 0) -> Verdict:
+    """Whether a launch's selection IS the job's k2 best pairs ("done") or what the next launch changes, from the status ``table``
+    (per rank: slots, candidates, n_sel, cut bits, kernel status, pre-filter threshold bits, walked slots, bar bits); ``head_budget``
+    (table units), ``shift``: None without heads.  The first check that fails names the action: status bit 3 "sketch off" (other
+    unknown bits raise); a void head table "grow walked list" / "rebuild heads" / "heads off"; an unsound pre-filter "rescore all"
+    (these repeat the SAME launch); an overflowing list "rescan below cut" / "rescan wider" (-inf cut); too few "lower bar" / "drop bar"."""
+    def again(action: str, failing: str, drop_heads: bool = False) -> Verdict:
+        n = launches - 1                                  # (the same launch again, not a corrected bar: it does not count twice)
+        if n + 2 > MAX_LAUNCHES:
+            raise ops._lib.EpsError(f"scan_topk: {failing} kept failing")
+        return Verdict(action, n, drop_heads, head_trouble, head_stale)
+
+    if any(t[4] & 8 for t in table):
+        # (status bit 3: a sketch piece had more ids to report than its set holds -- a bar far below what K asks for: the launch is
+        #  void, the call goes on with hashed packed pieces)
+        return again("sketch off", "launches with sketch pieces")
+    if any(t[4] & ~(4 | 16) for t in table):
+        raise ops._lib.EpsError("scan_topk: eps_scan_screen reported a full hash table (status %s)" % [t[4] for t in table])
+    drop_heads = False
+    if head_budget is not None:
+        # The head table was taken without looking at the bar.  A head as heavy as the bar (status bit 2: the bar fell since the
+        # table was built), a bar below the lowest one the table -- and its list of live columns -- was built for, or a walked
+        # list that overflowed: the launch is void; twice in a row: this call goes on without heads.
+        bar_units = _f32_from_bits(table[0][7]) * 2.0 ** shift
+        overflow = any(t[6] > walked_cap for t in table)
+        stale = any(t[4] & 4 for t in table) or head_budget > HEAD_KEEP[1] * bar_units
+        # (a budget out of range on a good launch only costs time: the NEXT launch takes a table for its bar)
+        drop_heads = overflow or stale or not HEAD_KEEP[0] * bar_units <= head_budget <= HEAD_KEEP[1] * bar_units
+        if overflow or stale:
+            # two causes, two remedies (ADVICE r05): a table built for another bar is simply rebuilt; only an overflowing walked
+            # list grows the list and counts toward giving heads up for this call
+            head_trouble, head_stale = head_trouble + overflow, head_stale + (not overflow)
+            action = "heads off" if head_trouble >= 2 or head_stale >= 3 else "grow walked list" if overflow else "rebuild heads"
+            return again(action, "launches with skipped heads", drop_heads)
+    slot_overflow = any(t[0] > capacity for t in table)
+    cut_is_inf = (table[0][3] & 0xFFFFFFFF) == 0xFF800000
+    if screened and not rescore_all and not slot_overflow:
+        # the pre-filter was sound iff the cut reaches every rank's threshold (floats compared through their bits on the host).
+        # A cut of -inf -- fewer than k2 re-scored pairs job-wide -- is NOT exempt (ADVICE r04): with uneven shards one rank's
+        # pre-filter may have held back pairs that belong to the k2 best while another rank had too few to fill its share, so
+        # any finite threshold above a -inf cut sends the step round again with everything re-scored.  Only when no rank
+        # filtered at all (every threshold -inf) does -inf mean "fewer than k2 pairs survived": the bar is lowered below.
+        cut_f = float("-inf") if cut_is_inf else _f32_from_bits(table[0][3])
+        if any(cut_f < _f32_from_bits(t[5]) for t in table):
+            return again("rescore all", "the re-scoring pre-filter", drop_heads)
+    if slot_overflow:
+        # the bar was too low for the list.  What was kept is a subset of the survivors, so the k2-th best score among it (the
+        # cut, job-wide) is a lower bound of the final cut: scan again just below it, with more room (a level of tied scores --
+        # common-neighbour counts -- may hold far more pairs than K)
+        return Verdict("rescan wider" if cut_is_inf else "rescan below cut", launches, drop_heads, head_trouble, head_stale)
+    # (a launch with skipped heads counts the candidates its walk touched, not all of them: fewer than k2 selected under a bar
+    #  then always means "lower the bar" -- the launch without one counts them all)
+    n_cand, n_sel = sum(t[1] for t in table), sum(t[2] for t in table)
+    if bar_set and n_sel < (k2 if head_budget is not None else min(k2, n_cand)):
+        return Verdict("drop bar" if launches > 3 else "lower bar", launches, drop_heads, head_trouble, head_stale)
+    return Verdict("done", launches, drop_heads, head_trouble, head_stale)
+
+
+def _status_words(res: ops.Survivors, status, pre_thr, bar) -> List[torch.Tensor]:
+    """A rank's six int64 status words (1-element tensors; zero where the launch has none): [slots, candidates, kernel status,
+    pre-filter threshold bits, walked slots, bar bits] -- a row of the status table without n_sel and the cut (after the second)."""
+    zero = torch.zeros(1, dtype=torch.int64, device=res.rec.device)
+    return [res.rec[1:2], res.rec[4:5],
+            status.to(torch.int64) if status is not None else zero,
+            pre_thr.view(torch.int32).to(torch.int64) if pre_thr is not None else zero,
+            res.walked_slots if res.walked_slots is not None else zero,
+            bar.view(torch.int32).to(torch.int64) if bar is not None else zero]
+
+
+def _device_tail(g: CSRGraph, screen: Screen, res: ops.Survivors, bar: torch.Tensor, k: int, k2: int, params, bits: int, perm):
+    """One rank under a bar: pre-filter, exact re-scoring (not for Screen.exact) and cut from score-bucket histograms
+    (csrc/tail_sort.hip).  Threshold and cut are the lower edges of the buckets that hold the k2-th best screening / exact score
+    (<= the exact order statistics: a few pairs more are re-scored and sorted, the K rows are the same; _verdict checks both).
+    -> (status table, selected keys, values, cut, pairs re-scored, rows).  TAIL_SORT = "library": library sorts, sized from the
+    host (host read 1: the pre-filter's count), rows = None -- faster on MI355X than "radix": a grid-wide hand-over inside a kernel
+    costs ~50 us there, a kernel boundary ~10 (profiles/r06/sort_probe.txt); "radix": cooperative sorts sized on the device, the
+    rows ordered here too, ONE host read.  Tied scores at the threshold beyond the room: the tail (not the launch) runs again."""
+    library = TAIL_SORT == "library"
+    room = min(res.capacity, 2 * k2 + (1 << 16))
+    while True:
+        ops.score_hist(res.key, res.val, res.count_ptr, bar)
+        c_keys, c_vals, n_valid, _, pre_thr = ops.score_pick_compact(res.key, res.val, res.count_ptr, bar, k2, mode=2,
+                                                                     params=params, room=room, want_vals=screen.exact)
+        count, sel_room = n_valid, room
+        if library:
+            nv = int(n_valid.item())                                                         # (one word: sizes the sorts)
+            if nv > room:
+                room = min(res.capacity, nv)
+                continue
+            c_keys, c_vals = c_keys[:nv], c_vals[:nv] if screen.exact else None
+            count, sel_room = None, max(nv, 1)
+        if screen.exact:
+            x_keys, x_vals = c_keys, c_vals
+        elif library:
+            x_keys = ops.sort_pairs_by_u(c_keys, bits, RESCORE_V_BLOCK)                      # (u << 32 | v): runs of equal u
+            x_vals = ops.rescore_runs(g.rowptr, g.col, screen.fixw, g.n_rows, x_keys)
+        else:
+            x_keys = ops.radix_sort_by_u(c_keys, n_valid, bits, RESCORE_V_BLOCK)
+            x_vals = ops.rescore_runs_dev(g.rowptr, g.col, screen.fixw, g.n_rows, x_keys, n_valid)
+        ops.score_hist(x_keys, x_vals, count, bar, above=bar)
+        sel_k, sel_v, n_sel, cut, _ = ops.score_pick_compact(x_keys, x_vals, count, bar, k2, above=bar, swap_halves=not screen.exact,
+                                                             room=sel_room)
+        if library:
+            # (the status vector as 32-bit words -- views, ONE cat launch, no dtype conversions: [slots lo hi, candidates lo hi,
+            #  n_sel lo hi, cut, kernel status, pre-filter threshold, walked slots lo hi, bar])
+            w32 = torch.cat([res.rec[1:2].view(torch.int32), res.rec[4:5].view(torch.int32), n_sel.view(torch.int32),
+                             cut.view(torch.int32), res.status, pre_thr.view(torch.int32),
+                             (res.walked_slots if res.walked_slots is not None else res.rec[1:2]).view(torch.int32),
+                             bar.view(torch.int32)]).tolist()                                 # the host read of the step
+            u64 = lambda lo, hi: (lo & 0xFFFFFFFF) | (hi << 32)                              # noqa: E731
+            table = [[u64(*w32[0:2]), u64(*w32[2:4]), u64(*w32[4:6]), w32[6], w32[7], w32[8],
+                      u64(*w32[9:11]) if res.walked_slots is not None else 0, w32[11]]]
+            return table, sel_k, sel_v, cut, 0 if screen.exact else nv, None
+        r_pairs, r_scores, n_rows = ops.radix_sort_rows(sel_k, sel_v, n_sel, k, bits, perm)
+        w = _status_words(res, res.status, pre_thr, bar)
+        row = torch.cat(w[:2] + [n_sel, cut.view(torch.int32).to(torch.int64)] + w[2:] + [n_valid, n_rows]).tolist()   # the host read
+        nv = row[8]
+        if nv <= room:
+            return [row[:8]], sel_k, sel_v, cut, 0 if screen.exact else nv, (r_pairs, r_scores, row[9])
+        room = min(res.capacity, nv)
+
+
+def _prefilter(g: CSRGraph, screen: Screen, res: ops.Survivors, bar, k2: int, params, world: int, rescore_all: bool):
+    """This rank's survivors of the one-pass kernel that can reach the job's k2 best, re-scored exactly (those that do not exceed
+    the bar after all drop out).  -> (keys, scores, pre-filter threshold, pairs re-scored, room).  With t = lower(the k_pre-th best
+    screening score of THIS rank's list) every pair that is not re-scored has an exact score < t (Screen.lower_bound), so the cut
+    is final iff it is >= every rank's t (_verdict).  k_pre = k2 / world: the shards are dealt round-robin out of one
+    heaviest-first order, so a rank's (k2 / world)-th best sits at the job's k2-th best; lower() leaves ~4 % of margin."""
+    k_pre = 0 if rescore_all else (k2 + world - 1) // world
+    # (2 x k_pre pairs: lower() keeps ~10 % more than k_pre; tied scores at the threshold beyond the room: once more with room for all)
+    room = res.capacity if rescore_all else min(res.capacity, 2 * k_pre + (1 << 16))
+    c_keys, c_vals, n_valid, _, pre_thr = ops.select_compact(res.key, res.val, k_pre, res.count_ptr, mode=2, params=params, room=room)
+    nv = int(n_valid.item())                                                                  # (one word: sizes the re-scoring)
+    if nv > room:
+        c_keys, c_vals, n_valid, _, pre_thr = ops.select_compact(res.key, res.val, k_pre, res.count_ptr, mode=2, params=params,
+                                                                 room=min(res.capacity, nv))
+        nv = int(n_valid.item())
+    if screen.exact:                                    # (screening sums that ARE the exact scores: Screen.exact)
+        return c_keys[:nv], c_vals[:nv], pre_thr, 0, room
+    keys, vals = rescore_exact(g, screen, c_keys[:nv], bar)
+    return keys, vals, pre_thr, nv, room
+
+
+def _read_exchange(got: torch.Tensor, nsel_all: torch.Tensor, cut: torch.Tensor, counts: torch.Tensor, world: int):
+    """(status table, deal counts) of a sharded step from its exchange ``got``, the selection counts, the cut and the deal plan's
+    counts: ONE host read -- fixed shapes, nothing waits for a size."""
+    heads6 = got[:, :12].contiguous().view(torch.int64)                                          # [world, 6]
+    st_all = torch.cat([heads6[:, :2], nsel_all.unsqueeze(1), cut.view(torch.int32).to(torch.int64).expand(world, 1),
+                        heads6[:, 2:]], 1)
+    flat = torch.cat([st_all.reshape(-1), counts.reshape(-1)]).tolist()                         # the host read of the step
+    return ([flat[r * 8:(r + 1) * 8] for r in range(world)],
+            [flat[8 * world + r * world:8 * world + (r + 1) * world] for r in range(world)])
+
+
+def _cut_from_histograms(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, bar: torch.Tensor, world: int):
+    """A sharded step under a bar (DIST_HIST): ONE exchange of 25 KB per rank -- every rank's histogram of its re-scored scores
+    over buckets of their distance to the (common) bar behind its six status words.  From it every rank derives in ONE launch
+    (ops.score_deal_plan) the cut -- the lower edge of the bucket of the k2-th best score: the K rows are the same --, everybody's
+    selection count and the deal plan of the final ordering.  -> (selected keys, values, cut, status table, deal plan)."""
+    from . import dist as epd
+    bins = ops.score_bins()
+    head = torch.cat(words).view(torch.int32)
+    send = torch.zeros(_XCHG_HEAD + bins, dtype=torch.int32, device=head.device)
+    send[:head.numel()] = head
+    ops.score_hist_into(keys, vals, None, bar, send[_XCHG_HEAD:], above=bar)
+    got = epd._gather_into(send, world).view(world, _XCHG_HEAD + bins)
+    cut, sp, counts, nsel_all = ops.score_deal_plan(got[:, _XCHG_HEAD:], k2, bar)
+    sel_k, sel_v, _ = ops.compact_at_least(keys, vals, cut)
+    table, deal_c = _read_exchange(got, nsel_all, cut, counts, world)
+    return sel_k, sel_v, cut, table, (sp, deal_c)
+
+
+def _cut_from_scores(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, room: int, world: int):
+    """The same from an exchange of the scores themselves (no bar -- small candidate sets -- or DIST_HIST off): every rank selects
+    the same cut from the same gathered scores.  The exchange must hold the longest list, which tied scores at a pre-filter
+    threshold may have grown beyond its ``room``: the ranks agree on it first (one all-reduced word)."""
+    from . import dist as epd
+    dev = vals.device
+    room = max(room, -int(epd.all_reduce_min_(torch.tensor([-int(vals.numel())], dtype=torch.int64, device=dev)).item()))
+    head = torch.cat(words).view(torch.int32)
+    send = torch.full((_XCHG_HEAD + room,), _NEG_INF_BITS, dtype=torch.int32, device=dev)
+    send[:head.numel()] = head
+    send[_XCHG_HEAD:_XCHG_HEAD + vals.numel()] = vals.view(torch.int32)
+    got = epd._gather_into(send, world).view(world, _XCHG_HEAD + room)
+    scores_all = got[:, _XCHG_HEAD:].contiguous().view(torch.float32)
+    cut = ops.select_compact(None, scores_all.reshape(-1), k2, compact=False)[3]
+    sel_k, sel_v, _ = ops.compact_at_least(keys, vals, cut)
+    nsel_all = ((scores_all >= cut) & (scores_all > float("-inf"))).sum(1)
+    sp, counts = _deal_plan(scores_all, cut, world)
+    table, deal_c = _read_exchange(got, nsel_all, cut, counts, world)
+    return sel_k, sel_v, cut, table, (sp, deal_c)
+
+
+def _cut_local(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, screened: bool, world: int):
+    """The cut -- the k2-th best score, -inf when fewer survived -- and the selection without an exchange of scores: one rank, or a
+    job without the one-pass kernel or re-scoring everything (a job-wide select, an all-gather of the status rows); no deal plan."""
+    if not _sharded(world) and screened:
+        sel_k, sel_v, n_sel, cut, _ = ops.select_compact(keys, vals, k2)
+    else:
+        cut = ops.kth_largest_dist(vals, k2, world)
+        sel_k, sel_v, n_sel = ops.compact_at_least(keys, vals, cut)
+    st = torch.cat(words[:2] + [n_sel, cut.view(torch.int32).to(torch.int64)] + words[2:])
+    if _sharded(world):
+        from . import dist as epd
+        return sel_k, sel_v, cut, torch.stack(epd.all_gather_list(st)).tolist(), None            # the host read of the step
+    return sel_k, sel_v, cut, [st.tolist()], None
+
+
+def _ordered_rows(sel_k: torch.Tensor, sel_v: torch.Tensor, nsel_r: List[int], deal, k: int, bits: int, perm, rank: int,
+                  world: int, rows_on):
+    """The k best directed rows of the selection (in the scanned graph's labels: the orderings map them back), ordered: -> (pairs
+    [2, <=k] as (u; v), scores) or (None, None) on a rank that does not get them, and stats["shard"].  A job deals the ordering
+    over the ranks by score range (with the exchange's deal plan: _deal_rows) unless the list is short."""
+    keys, vals = sel_k[:nsel_r[rank]], sel_v[:nsel_r[rank]]
+    if not _sharded(world):
+        pairs, scores = ops.select_rows_pairs(keys.contiguous(), vals.contiguous(), k, bits, perm)
+        return pairs, scores, None
+    from . import dist as epd
+    n_sel_all = sum(nsel_r)
+    shard = None
+    if deal is not None and n_sel_all >= DIST_ROWS_MIN:
+        sp, c = deal
+        keys, vals = _deal_rows(keys.contiguous(), vals.contiguous(), sp, c, k, bits, perm, rank, world, rows_on)
+        if rows_on == "shards":
+            lens = [2 * sum(c[r][q] for r in range(world)) for q in range(world)]
+            shard = (min(sum(lens[:rank]), k), min(sum(lens), k))
+    else:
+        keys, vals = epd.gather_ragged(keys, nsel_r), epd.gather_ragged(vals, nsel_r)
+        if n_sel_all >= DIST_ROWS_MIN:
+            keys, vals = _ordered_rows_distributed(keys.contiguous(), vals.contiguous(), k, bits, perm, rank, world,
+                                                   None if rows_on == "shards" else rows_on)
+        elif rows_on is None or rows_on == rank or rows_on == "shards":
+            keys, vals = ops.select_rows(keys.contiguous(), vals.contiguous(), k, bits, perm)
+        else:
+            keys = vals = None
+        if rows_on == "shards" and keys is not None:
+            # (a short list, or the exchange without a deal plan: every rank holds all rows -- it keeps an even share of them)
+            n_rows = keys.numel()
+            lo_r, hi_r = rank * n_rows // world, (rank + 1) * n_rows // world
+            shard = (lo_r, n_rows)
+            keys, vals = keys[lo_r:hi_r], vals[lo_r:hi_r]
+    if keys is None:
+        return None, None, shard
+    return torch.stack([keys & 0xFFFFFFFF, keys >> 32]), vals, shard
+
+
+def _step_stats(stats: dict, g: CSRGraph, screen: Optional[Screen], fixw, table, ht: Optional[HeadTables], capacity: int,
+                launches: int, sketch_void: int, n_rescored, shard, bar, rank: int, world: int) -> None:
+    """scan_topk's ``stats`` from the final status table.  survivors: DIRECTED rows at or above the job-wide cut; survivor_slots:
+    list slots the launches handed out (chunks: holes included); bar: None or a 1-element device tensor; candidates: DIRECTED 2-hop
+    non-edges the filter covered.  A launch with skipped heads counts only those its walk touched (`touched`); the exact number
+    then comes from `candidate_count` (one counting scan per graph, cached) unless ``stats`` holds count=False (candidates None)."""
+    n_cand, n_sel = sum(t[1] for t in table), sum(t[2] for t in table)
+    if ht is None and world == 1:
+        g._cache.setdefault("n_candidates", n_cand)
+    n_all = 2 * n_cand if ht is None else 2 * candidate_count(g, screen, fixw, rank, world) if stats.get("count", True) else None
+    stats.update(candidates=n_all, touched=2 * n_cand, launches=launches, survivors=2 * n_sel, heads=ht is not None, shard=shard,
+                 sketch=any(t[4] & 16 for t in table), sketch_void=sketch_void,      # (status bit 4: sketch pieces ran)
+                 head_budget=None if ht is None else ht.budget * 2.0 ** -screen.shift,
+                 walked_slots=sum(t[6] for t in table) if ht is not None else None, rescored=n_rescored,
+                 survivor_slots=sum(min(t[0], capacity) for t in table), bar=bar)
+
+
 def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: int = 1, stats: Optional[dict] = None,
               relabel: bool = False, rows_on: Optional[int] = None):
     """Exact top-``k`` candidates of the whole graph: (pairs int64 [2,<=k] as (u; v), scores float32), best first.
@@ -1013,19 +1275,12 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     the chunk of the declared order it ordered itself (rank r's rows follow rank r - 1's; together the first k rows) -- nothing is
     gathered, ``stats["shard"]`` = (first row of this rank's chunk, rows of all chunks).
 
-    Per call, in the steady state (tables cached on the graph): sample launch -> bar (device; the lowest of the ranks' own
-    estimates; r06: read off a score histogram around the previous bar when the graph was scanned at this K before) -> main launch,
-    under a bar with skipped heads + eps_scan_refine (r06: the body compiled for its tables, the per-column pack from the graph's
-    second scan on) -> LOCAL pre-filter of this rank's list (r06, one rank under a bar: a score-bucket histogram + pick-and-compact;
-    its count -- one word -- is read to size the library sorts: host read 1) -> exact re-scoring of what passed (not for uniform
-    weights whose screening sums are exact: Screen.exact) -> job-wide cut (one rank: the lower edge of the bucket of the
-    ceil(k/2)-th best exact score; on a job one all-gather of the ranks' score HISTOGRAMS behind their status words, every rank
-    derives the same cut and deal plan: ops.score_deal_plan) + compaction -> host read 2 of a status vector (slots, candidates,
-    selected, cut, kernel status, the rank's pre-filter threshold, walked slots, the bar; all-gathered when world > 1), which
-    VERIFIES the step: enough survivors, no list overflow, the cut at or above every rank's pre-filter threshold, usable heads --
-    else the launch repeats with what was learnt -> mirrored + ordered (one rank: ops.select_rows_pairs writes the [2, K] tensor),
-    on a job the ordering dealt over the ranks by score range, the rows sent to ``rows_on`` or left where they were ordered
-    (ops.select_rows, _deal_rows).  TAIL_SORT = "radix": the same with one-launch cooperative sorts, sizes on the device, ONE host read."""
+    The stages, tables cached on the graph: the bar (estimate_bar: a sample launch; on the device) -> the main launch (_launch:
+    under a bar with skipped heads) -> one rank under a bar: the device tail (_device_tail); else the pre-filter and exact
+    re-scoring of this rank's list (_prefilter) and the job-wide cut with the status table (_cut_from_histograms, _cut_from_scores,
+    _cut_local) -> the verdict on the status table (_verdict), which VERIFIES the step -- else the launch repeats with what was
+    learnt -> the rows (_ordered_rows) and the stats (_step_stats).  Host reads per step on one rank: two (the pre-filter's count,
+    the status table); TAIL_SORT = "radix": one."""
     if relabel and scan_plausible(g):
         scan_graph(g, build=True)        # (first: the symmetry check below then reads the copy's table, the one the scan needs)
     if not scan_available(g):
@@ -1037,13 +1292,13 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     if not candidates.fused_scores_fit(g, node_w):
         raise ops._lib.EpsError(f"scan_topk: score bound {candidates.fused_score_bound(g, node_w):.3e} of this graph / weight "
                                 "table leaves the 2^-40 fixed-point range of the scan (use the pair kernels)")
-    dev = g.device
     g0 = g
     g, perm = scan_graph(g0, relabel)    # from here on g is the graph as scanned; ids go back through perm at the end
     fixw = _scan_weights(g0, g, perm, node_w) if g.val is None else None
     mine = shard_columns(g, rank, world)
     total_half = total_half_paths(g)
     k2 = (k + 1) // 2                    # the k-th best directed row belongs to the ceil(k/2)-th best unordered pair
+    bits = max(1, min(32, int(g.n_rows - 1).bit_length()))
     screen = None
     if one_pass_available(g):
         sc = screen_weights(g0, g, perm, node_w)
@@ -1062,15 +1317,13 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     # a factor 0.35 .. 1.7), or every candidate without a bar
     wanted = (2 * total_half if bar is None else int(2 * SAFETY * k)) // world
     capacity = _capacity(wanted, slack)
-    neg_inf = torch.full((1,), float("-inf"), device=dev)
     # skipped heads (csrc/scan_heads.hip): unit-valued graphs with a plan table, under a bar
     use_heads = (HEADS and screen is not None and screen.has_plan and screen.ssum is not None and g.val is None
                  and total_half >= HEAD_MIN_PATHS)
     _count_scan(g, screen)
     head_list, head_trouble, head_stale = HEAD_LIST, 0, 0
-    sketch, sketch_void, sketch_ran = SKETCH_PIECES, 0, False
+    sketch, sketch_void = SKETCH_PIECES, 0
     n_rescored = None
-    ht = None
     while True:
         if launches >= MAX_LAUNCHES:
             raise ops._lib.EpsError(f"scan_topk: no usable bar after {launches} launches (k = {k}, capacity {capacity})")
@@ -1088,316 +1341,60 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
                       capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap,
                       sketch=want_sketch)
         launches += 1
-        l_keys, l_vals = res.key, res.val
-        status, pre_thr = None, None
-        rows = None
-        fast = (TAIL_DEVICE and not _sharded(world) and screen is not None and g.val is None and bar is not None and not rescore_all
-                and k2 + (1 << 16) < (1 << 30))
-        if fast:
-            # r06: the step's selections come from score-bucket histograms instead of four-round radix selects: the pre-filter
-            # threshold and the cut are the lower edges of the buckets that hold the k2-th best screening / exact score (<= the exact
-            # order statistics: a few pairs more are re-scored, mirrored and sorted; the K rows are the same -- both are verified
-            # below).  The two orderings: TAIL_SORT.
-            a, b = screen.lower_params(max_degree(g), None if ht is None else ht.d_used)
-            bits = max(1, min(32, int(g.n_rows - 1).bit_length()))
-            room = min(res.capacity, 2 * k2 + (1 << 16))
-            while TAIL_SORT == "library":
-                # The selections from score-bucket histograms (two launches each instead of a four-round cooperative select), the two
-                # orderings by the library sorts: those take their sizes from the host, so the pre-filter's count is read back (the
-                # second host read of the step is the status vector below).  Measured faster than the one-launch cooperative radix sorts
-                # of TAIL_SORT = "radix" on MI355X: a grid-wide hand-over inside a kernel costs ~50 us there, a kernel boundary ~10
-                # (profiles/r06/sort_probe.txt).
-                ops.score_hist(res.key, res.val, res.count_ptr, bar)
-                c_keys, c_vals, n_valid, _, pre_thr = ops.score_pick_compact(res.key, res.val, res.count_ptr, bar, k2, mode=2,
-                                                                             params=(a, b, 4e-6), room=room, want_vals=screen.exact)
-                nv = int(n_valid.item())                                                         # (one word: sizes the sorts)
-                if nv > room:
-                    room = min(res.capacity, nv)
-                    continue
-                if screen.exact:
-                    x_keys, x_vals, swap = c_keys[:nv], c_vals[:nv], False
-                else:
-                    x_keys = ops.sort_pairs_by_u(c_keys[:nv], bits, RESCORE_V_BLOCK)              # (u << 32 | v): runs of equal u
-                    x_vals = ops.rescore_runs(g.rowptr, g.col, screen.fixw, g.n_rows, x_keys)
-                    swap = True
-                ops.score_hist(x_keys, x_vals, None, bar, above=bar)
-                sel_k, sel_v, n_sel, cut, _ = ops.score_pick_compact(x_keys, x_vals, None, bar, k2, above=bar, swap_halves=swap, room=max(nv, 1))
-                # (the status vector as 32-bit words -- views, ONE cat launch, no dtype conversions: [slots lo hi, candidates lo hi,
-                #  n_sel lo hi, cut, kernel status, pre-filter threshold, walked slots lo hi, bar])
-                w32 = torch.cat([res.rec[1:2].view(torch.int32), res.rec[4:5].view(torch.int32), n_sel.view(torch.int32),
-                                 cut.view(torch.int32), res.status, pre_thr.view(torch.int32),
-                                 (res.walked_slots if res.walked_slots is not None else res.rec[1:2]).view(torch.int32),
-                                 bar.view(torch.int32)]).tolist()                                 # the host read of the step
-                u32 = lambda x: x & 0xFFFFFFFF                                                   # noqa: E731
-                table = [[u32(w32[0]) | (w32[1] << 32), u32(w32[2]) | (w32[3] << 32), u32(w32[4]) | (w32[5] << 32), w32[6], w32[7], w32[8],
-                          (u32(w32[9]) | (w32[10] << 32)) if res.walked_slots is not None else 0, w32[11]]]
-                n_rescored = 0 if screen.exact else nv
-                break
-            while TAIL_SORT != "library":
-                ops.score_hist(res.key, res.val, res.count_ptr, bar)
-                c_keys, c_vals, n_valid, _, pre_thr = ops.score_pick_compact(res.key, res.val, res.count_ptr, bar, k2, mode=2,
-                                                                             params=(a, b, 4e-6), room=room, want_vals=screen.exact)
-                if screen.exact:                     # (screening sums that ARE the exact scores: Screen.exact)
-                    x_keys, x_vals, swap = c_keys, c_vals, False
-                else:
-                    x_keys = ops.radix_sort_by_u(c_keys, n_valid, bits, RESCORE_V_BLOCK)          # (u << 32 | v): runs of equal u
-                    x_vals = ops.rescore_runs_dev(g.rowptr, g.col, screen.fixw, g.n_rows, x_keys, n_valid)
-                    swap = True
-                ops.score_hist(x_keys, x_vals, n_valid, bar, above=bar)
-                sel_k, sel_v, n_sel, cut, _ = ops.score_pick_compact(x_keys, x_vals, n_valid, bar, k2, above=bar, swap_halves=swap, room=room)
-                r_pairs, r_scores, n_rows = ops.radix_sort_rows(sel_k, sel_v, n_sel, k, bits, perm)
-                zero = torch.zeros(1, dtype=torch.int64, device=dev)
-                st = torch.cat([res.rec[1:2], res.rec[4:5], n_sel, cut.view(torch.int32).to(torch.int64), res.status.to(torch.int64),
-                                pre_thr.view(torch.int32).to(torch.int64), res.walked_slots if res.walked_slots is not None else zero,
-                                bar.view(torch.int32).to(torch.int64) if bar is not None else zero, n_valid, n_rows])
-                row = st.tolist()                                                                # the host read of the step
-                nv = row[8]
-                if nv <= room:
-                    table = [row[:8]]
-                    n_rescored = 0 if screen.exact else nv
-                    rows = (r_pairs, r_scores, row[9])
-                    break
-                room = min(res.capacity, nv)        # (a level of tied scores at the pre-filter threshold holds more than the room: once more)
-        elif screen is not None:
-            # the one-pass kernel screens with upper bounds: its survivors are re-scored exactly (those that do not exceed the
-            # bar after all drop out), so from here on the list holds eps_filter_scan's scores bit for bit.
-            # Not all of them need it: a screening score s exceeds the exact one by less than what `screen.lower_bound` takes
-            # off (a monotone lower bound of the exact score).  With t = lower(the k_pre-th best screening score of THIS rank's
-            # list), every pair that is not re-scored has an exact score < t; the job-wide cut found below (the k2-th best exact
-            # score among the re-scored pairs of all ranks) is then final iff it is >= every rank's t -- which the status
-            # table verifies.  k_pre = k2 / world: the shards are dealt round-robin out of one heaviest-first order, so a rank's
-            # (k2 / world)-th best sits at the job's k2-th best, and lower() leaves ~4 % of margin; world = 1: the r03 rule.
-            # One launch: select + threshold + compaction, bounded by the list's slot counter (no collective, no pass over the
-            # list's unused capacity).
-            a, b = screen.lower_params(max_degree(g), None if ht is None else ht.d_used)
-            k_pre = 0 if rescore_all else (k2 + world - 1) // world
-            # (the outputs hold 2 x k_pre pairs -- lower() keeps ~10 % more than k_pre -- not a copy of the list's worst-case size;
-            #  a level of tied scores at the threshold may hold more: then the call is repeated with room for all of them)
-            room = res.capacity if rescore_all else min(res.capacity, 2 * k_pre + (1 << 16))
-            room_x = room              # (what the r05 score exchange sends: the same on every rank -- a retry below grows `room` only)
-            c_keys, c_vals, n_valid, _, pre_thr = ops.select_compact(l_keys, l_vals, k_pre, res.count_ptr, mode=2, params=(a, b, 4e-6), room=room)
-            nv = int(n_valid.item())                                                      # (one word: sizes the re-scoring)
-            if nv > room:
-                c_keys, c_vals, n_valid, _, pre_thr = ops.select_compact(l_keys, l_vals, k_pre, res.count_ptr, mode=2, params=(a, b, 4e-6),
-                                                                         room=min(res.capacity, nv))
-                nv = int(n_valid.item())
-            if screen.exact:
-                l_keys, l_vals = c_keys[:nv], c_vals[:nv]        # (screening sums that ARE the exact scores: Screen.exact)
-            else:
-                l_keys, l_vals = rescore_exact(g, screen, c_keys[:nv], bar)
-            n_rescored = 0 if screen.exact else nv
-            status = res.status
-        # the job-wide cut: the k2-th best survivor score over all ranks (-inf when fewer survived); untouched slots are -inf
-        scores_all = None
-        if not fast:                   # (the fast path assembles its own status vector: no conversions on its stream)
-            zero = torch.zeros(1, dtype=torch.int64, device=dev)
-            st_tail = [status.to(torch.int64) if status is not None else zero,                          # kernel status,
-                       pre_thr.view(torch.int32).to(torch.int64) if pre_thr is not None else zero,      # pre-filter threshold bits,
-                       res.walked_slots if res.walked_slots is not None else zero,                      # slots of the walked list,
-                       bar.view(torch.int32).to(torch.int64) if bar is not None else zero]               # the bar's bits (head launches)
-        if fast:
-            pass
-        elif _sharded(world) and screen is not None and not rescore_all and bar is not None and DIST_HIST:
-            # r06 -- ONE exchange for the cut AND the step's status, 25 KB per rank whatever the lists hold: every rank's histogram of
-            # its re-scored scores over order-preserving buckets of their distance to the bar (ops.score_hist_into: the bar is the
-            # same on every rank) behind six status words, all-gathered.  From the same table every rank then derives, in ONE small
-            # launch (ops.score_deal_plan) and without asking again, the job-wide cut -- the lower edge of the bucket that holds the
-            # k2-th best score: a few pairs more than k2 are selected, the K rows are the same --, everybody's selection count, the
-            # splitters of the final ordering (bucket edges) and who sends how many pairs of which range to whom (_deal_rows).
-            # (r05: every rank's SCORES, 2.3 MB per rank, and a replicated select over all of them; r04: four all-reduced histogram
-            #  rounds for the cut, one all-gather for the status, two for the selected pairs.)
-            from . import dist as epd
-            bins = ops.score_bins()
-            head = torch.cat([res.rec[1:2], res.rec[4:5]] + st_tail).view(torch.int32)                 # 6 x int64
-            send = torch.zeros(_XCHG_HEAD + bins, dtype=torch.int32, device=dev)
-            send[:head.numel()] = head
-            ops.score_hist_into(l_keys, l_vals, None, bar, send[_XCHG_HEAD:], above=bar)
-            got = epd._gather_into(send, world).view(world, _XCHG_HEAD + bins)
-            cut, deal_sp, deal_counts, nsel_all = ops.score_deal_plan(got[:, _XCHG_HEAD:], k2, bar)
-            sel_k, sel_v, n_sel = ops.compact_at_least(l_keys, l_vals, cut)
-            heads6 = got[:, :12].contiguous().view(torch.int64)                                          # [world, 6]
-            st_all = torch.cat([heads6[:, :2], nsel_all.unsqueeze(1), cut.view(torch.int32).to(torch.int64).expand(world, 1),
-                                heads6[:, 2:]], 1)
-            flat = torch.cat([st_all.reshape(-1), deal_counts.reshape(-1)]).tolist()            # the host read of the step
-            table = [flat[r * 8:(r + 1) * 8] for r in range(world)]
-            deal_c = [flat[8 * world + r * world:8 * world + (r + 1) * world] for r in range(world)]
-            scores_all = True                     # (marks "the deal plan is at hand" for the ordering below)
-        elif _sharded(world) and screen is not None and not rescore_all:
-            # (no bar -- small candidate sets -- or DIST_HIST off: the r05 exchange of the scores themselves.  Its length must be the
-            #  same on every rank and hold every rank's list: a level of tied scores at a rank's pre-filter threshold may have grown
-            #  that rank's list beyond the room it started with -- ADVICE r05 -- so the ranks agree on the longest list first: one
-            #  all-reduced word)
-            from . import dist as epd
-            room_x = max(room_x, -int(epd.all_reduce_min_(torch.tensor([-int(l_vals.numel())], dtype=torch.int64, device=dev)).item()))
-            # ONE exchange for the cut AND the step's status: every rank's re-scored scores (at most `room`, -inf beyond its own) behind
-            # six status words, all-gathered.  Each rank then finds the job-wide cut itself -- one select launch over the gathered
-            # scores: the same values in the same order everywhere, so the same cut without a broadcast -- and knows every rank's
-            # selection count, the splitters of the final ordering and who sends how much to whom (_deal_rows) without asking again.
-            # (r04: four all-reduced histogram rounds for the cut, one all-gather for the status, two for the selected pairs.)
-            from . import dist as epd
-            head = torch.cat([res.rec[1:2], res.rec[4:5]] + st_tail).view(torch.int32)                 # 6 x int64
-            send = torch.full((_XCHG_HEAD + room_x,), _NEG_INF_BITS, dtype=torch.int32, device=dev)
-            send[:head.numel()] = head
-            send[_XCHG_HEAD:_XCHG_HEAD + l_vals.numel()] = l_vals.view(torch.int32)
-            got = epd._gather_into(send, world).view(world, _XCHG_HEAD + room_x)
-            scores_all = got[:, _XCHG_HEAD:].contiguous().view(torch.float32)
-            cut = ops.select_compact(None, scores_all.reshape(-1), k2, compact=False)[3]
-            sel_k, sel_v, n_sel = ops.compact_at_least(l_keys, l_vals, cut)
-            nsel_all = ((scores_all >= cut) & (scores_all > float("-inf"))).sum(1)
-            heads6 = got[:, :12].contiguous().view(torch.int64)                                          # [world, 6]
-            st_all = torch.cat([heads6[:, :2], nsel_all.unsqueeze(1), cut.view(torch.int32).to(torch.int64).expand(world, 1),
-                                heads6[:, 2:]], 1)
-            # (the splitters of the final ordering and the table of who sends how many pairs of which range to whom ride along
-            #  in the same host read: fixed shapes, nothing here waits for a size)
-            deal_sp, deal_counts = _deal_plan(scores_all, cut, world)
-            flat = torch.cat([st_all.reshape(-1), deal_counts.reshape(-1)]).tolist()            # the host read of the step
-            table = [flat[r * 8:(r + 1) * 8] for r in range(world)]
-            deal_c = [flat[8 * world + r * world:8 * world + (r + 1) * world] for r in range(world)]
+        rows = deal = None
+        if screen is not None:
+            params = screen.lower_params(max_degree(g), None if ht is None else ht.d_used) + (4e-6,)
+        if (TAIL_DEVICE and not _sharded(world) and screen is not None and g.val is None and bar is not None and not rescore_all
+                and k2 + (1 << 16) < (1 << 30)):
+            table, sel_k, sel_v, cut, n_rescored, rows = _device_tail(g, screen, res, bar, k, k2, params, bits, perm)
         else:
-            if not _sharded(world) and screen is not None:
-                sel_k, sel_v, n_sel, cut, _ = ops.select_compact(l_keys, l_vals, k2)          # (one launch: select + compaction)
+            keys, vals, pre_thr, room = res.key, res.val, None, 0
+            if screen is not None:
+                keys, vals, pre_thr, n_rescored, room = _prefilter(g, screen, res, bar, k2, params, world, rescore_all)
+            words = _status_words(res, None if screen is None else res.status, pre_thr, bar)
+            exchange = _sharded(world) and screen is not None and not rescore_all
+            if exchange and bar is not None and DIST_HIST:
+                sel_k, sel_v, cut, table, deal = _cut_from_histograms(keys, vals, words, k2, bar, world)
+            elif exchange:
+                sel_k, sel_v, cut, table, deal = _cut_from_scores(keys, vals, words, k2, room, world)
             else:
-                cut = ops.kth_largest_dist(l_vals, k2, world)
-                sel_k, sel_v, n_sel = ops.compact_at_least(l_keys, l_vals, cut)
-            st = torch.cat([res.rec[1:2], res.rec[4:5], n_sel, cut.view(torch.int32).to(torch.int64)] + st_tail)
-            if _sharded(world):
-                from . import dist as epd
-                table = torch.stack(epd.all_gather_list(st)).tolist()                          # the host read of the step
-            else:
-                table = [st.tolist()]
-        slots_r, ncand_r, nsel_r = [t[0] for t in table], [t[1] for t in table], [t[2] for t in table]
-        if any(t[4] & 8 for t in table):
-            # (status bit 3: a sketch piece had more ids to report than its set holds -- a bar far below what K asks for: the launch is
-            #  void, the call goes on with hashed packed pieces)
-            sketch = False
-            sketch_void += 1
-            launches -= 1                                    # (the repeat is the same launch again, not a corrected bar)
-            if launches + 2 > MAX_LAUNCHES:
-                raise ops._lib.EpsError("scan_topk: launches with sketch pieces kept failing")
-            continue
-        sketch_ran = any(t[4] & 16 for t in table)            # (status bit 4, informational: sketch pieces ran in this launch)
-        if any(t[4] & ~(4 | 16) for t in table):
-            raise ops._lib.EpsError("scan_topk: eps_scan_screen reported a full hash table (status %s)" % [t[4] for t in table])
-        if ht is not None:
-            # The head table was taken without looking at the bar.  A head as heavy as the bar (status bit 2: the bar fell since the
-            # table was built) or a walked list that overflowed: the launch is void -- a table for THIS bar is built (head_cur
-            # dropped: the next _heads_for reads the bar), the list grows; twice in a row: this call goes on without heads.
-            bar_units = _f32_from_bits(table[0][7]) * 2.0 ** screen.shift
-            # (... or the bar fell below the lowest one the table -- and its list of live columns -- was built for)
-            overflow = any(t[6] > walked_cap for t in table)
-            stale = any(t[4] & 4 for t in table) or ht.budget > HEAD_KEEP[1] * bar_units
-            void = overflow or stale
-            if void or not HEAD_KEEP[0] * bar_units <= ht.budget <= HEAD_KEEP[1] * bar_units:
-                screen.head_cur = None                       # (a budget out of range only costs time: the NEXT launch rebuilds)
-            if void:
-                # (two causes, two remedies -- ADVICE r05: a table built for another bar is simply rebuilt; only an overflowing
-                #  walked list grows the list and counts toward giving heads up for this call)
-                if overflow:
-                    head_trouble += 1
-                    head_list *= 2
-                else:
-                    head_stale += 1
-                use_heads = head_trouble < 2 and head_stale < 3
-                launches -= 1                                # (the repeat is the same launch again, not a corrected bar)
-                if launches + 2 > MAX_LAUNCHES:
-                    raise ops._lib.EpsError("scan_topk: launches with skipped heads kept failing")
-                continue
-        n_cand_all, n_sel_all = sum(ncand_r), sum(nsel_r)
-        cut_is_inf = (table[0][3] & 0xFFFFFFFF) == 0xFF800000
-        if screen is not None and not rescore_all and not any(sl > capacity for sl in slots_r):
-            # the pre-filter was sound iff the cut reaches every rank's threshold (floats compared through their bits on the host).
-            # A cut of -inf -- fewer than k2 re-scored pairs job-wide -- is NOT exempt: with uneven shards one rank's
-            # pre-filter may have held back pairs that belong to the k2 best while another rank had too few to fill its share, so
-            # any finite threshold above a -inf cut sends the step round again with everything re-scored.  Only when no rank
-            # filtered at all (every threshold -inf) does -inf mean "fewer than k2 pairs survived": the bar is lowered below.
-            cut_f = float("-inf") if cut_is_inf else _f32_from_bits(table[0][3])
-            if any(cut_f < _f32_from_bits(t[5]) for t in table):
-                rescore_all = True         # (never seen with round-robin shards: a rank's list would have to sit far above the job's)
-                launches -= 1              # (the repeat is the same launch again, not a corrected bar)
-                if launches + 2 > MAX_LAUNCHES:
-                    raise ops._lib.EpsError("scan_topk: the re-scoring pre-filter kept failing")
-                continue
-        if any(sl > capacity for sl in slots_r):
-            # the bar was too low for the list.  What was kept is a subset of the survivors, so the k2-th best score among
-            # it (the cut just computed, job-wide) is a lower bound of the final cut: scan again just below it, with more
-            # room (a level of tied scores -- common-neighbour counts -- may hold far more pairs than K).
-            if not cut_is_inf:
-                bar = torch.nextafter(cut, neg_inf)
+                sel_k, sel_v, cut, table, deal = _cut_local(keys, vals, words, k2, screen is not None, world)
+        v = _verdict(table, capacity, walked_cap, None if ht is None else ht.budget, None if ht is None else screen.shift,
+                     screen is not None, rescore_all, k2, bar is not None, launches, head_trouble, head_stale)
+        launches, head_trouble, head_stale = v.launches, v.head_trouble, v.head_stale
+        if v.drop_heads:
+            screen.head_cur = None
+        if v.action == "done":
+            break
+        if v.action == "sketch off":
+            sketch, sketch_void = False, sketch_void + 1
+        elif v.action == "grow walked list":
+            head_list *= 2
+        elif v.action == "heads off":
+            use_heads = False
+        elif v.action == "rescore all":
+            rescore_all = True
+        elif v.action in ("rescan below cut", "rescan wider"):
+            if v.action == "rescan below cut":
+                bar = torch.nextafter(cut, torch.full_like(cut, float("-inf")))
             wanted *= 4
-            capacity = _capacity(wanted, slack)
-            continue
-        # (a launch with skipped heads counts the candidates its walk touched, not all of them: fewer than k2 selected under a bar
-        #  then always means "lower the bar" -- the launch without one counts them all)
-        if bar is not None and n_sel_all < (k2 if ht is not None else min(k2, n_cand_all)):
-            # fewer than k above the bar: lower it (a quarter of the sample rank each time, then no bar at all)
-            bar = None if launches > 3 else estimate_bar(g, fixw, k, safety=SAFETY * 8 ** (launches - 1), rank=rank, world=world,
-                                                         screen=screen)
+        elif v.action in ("lower bar", "drop bar"):
+            # (a quarter of the sample rank each time, then no bar at all)
+            bar = None if v.action == "drop bar" else estimate_bar(g, fixw, k, safety=SAFETY * 8 ** (launches - 1), rank=rank,
+                                                                   world=world, screen=screen)
             launches += 1
             if bar is None:
                 wanted = 2 * total_half // world
-                capacity = _capacity(wanted, slack)
-            continue
-        break
-    if screen is not None and bar is not None and len(table[0]) > 7:
+        capacity = _capacity(wanted, slack)
+    if screen is not None and bar is not None:
         # (the bar this scan ended with, for the next scan's estimate at the same K: see estimate_bar)
         bar_f = _f32_from_bits(table[0][7])
         if 0.0 < bar_f < float("inf"):
             screen.bar_hint[(k, sample_stride(k), float(SAFETY))] = bar_f
-    keys, vals = sel_k[:nsel_r[rank]], sel_v[:nsel_r[rank]]      # (still in the scanned graph's labels: select_rows maps them back)
-    bits = max(1, min(32, int(g.n_rows - 1).bit_length()))
-    shard_info = None
     if rows is not None:
-        keys = vals = None                          # (the device tail has ordered the rows already)
-    elif _sharded(world) and scores_all is not None and n_sel_all >= DIST_ROWS_MIN:
-        keys, vals = _deal_rows(keys.contiguous(), vals.contiguous(), deal_sp, deal_c, k, bits, perm, rank, world, rows_on)
-        if rows_on == "shards":
-            lens = [2 * sum(deal_c[r][q] for r in range(world)) for q in range(world)]
-            shard_info = (min(sum(lens[:rank]), k), min(sum(lens), k))
-    elif _sharded(world):
-        from . import dist as epd
-        keys, vals = epd.gather_ragged(keys, nsel_r), epd.gather_ragged(vals, nsel_r)
-        if n_sel_all >= DIST_ROWS_MIN:
-            keys, vals = _ordered_rows_distributed(keys.contiguous(), vals.contiguous(), k, bits, perm, rank, world,
-                                                   None if rows_on == "shards" else rows_on)
-        elif rows_on is None or rows_on == rank or rows_on == "shards":
-            keys, vals = ops.select_rows(keys.contiguous(), vals.contiguous(), k, bits, perm)
-        else:
-            keys = vals = None
-        if rows_on == "shards" and keys is not None:
-            # (a short list, or the exchange without a deal plan: every rank holds all rows -- it keeps an even share of them)
-            n_rows = keys.numel()
-            lo_r, hi_r = rank * n_rows // world, (rank + 1) * n_rows // world
-            shard_info = (lo_r, n_rows)
-            keys, vals = keys[lo_r:hi_r], vals[lo_r:hi_r]
-    elif not _sharded(world) and keys.is_cuda:
-        # (one rank: the rows are written as the [2, K] proposal tensor by the sort's last kernel)
-        rows = ops.select_rows_pairs(keys.contiguous(), vals.contiguous(), k, bits, perm)
-        rows = (rows[0], rows[1], rows[0].shape[1])
-        keys = vals = None
-    elif rows_on is None or rows_on == rank or world == 1:
-        keys, vals = ops.select_rows(keys.contiguous(), vals.contiguous(), k, bits, perm)
+        pairs, scores, shard = rows[0][:, :rows[2]], rows[1][:rows[2]], None
     else:
-        keys = vals = None
+        pairs, scores, shard = _ordered_rows(sel_k, sel_v, [t[2] for t in table], deal, k, bits, perm, rank, world, rows_on)
     if stats is not None:
-        # survivors: DIRECTED rows at or above the job-wide cut (what the selection orders); survivor_slots: list slots the
-        # launches handed out (chunks: holes included); bar: None or a 1-element device tensor (float(bar) reads it)
-        # candidates: DIRECTED 2-hop non-edges the filter covered.  A launch with skipped heads only counts those its walk touched
-        # (`touched`); the exact number then comes from `candidate_count` (one counting scan per graph, cached) unless the caller
-        # put count=False into ``stats`` (then candidates = None).
-        touched = 2 * n_cand_all
-        if ht is None:
-            n_all = touched
-            if world == 1:
-                g._cache.setdefault("n_candidates", n_cand_all)
-        else:
-            n_all = 2 * candidate_count(g, screen, fixw, rank, world) if stats.get("count", True) else None
-        stats.update(candidates=n_all, touched=touched, launches=launches, survivors=2 * n_sel_all, heads=ht is not None, shard=shard_info,
-                     sketch=sketch_ran, sketch_void=sketch_void,
-                     head_budget=None if ht is None else ht.budget * 2.0 ** -screen.shift,
-                     walked_slots=sum(t[6] for t in table) if ht is not None else None, rescored=n_rescored,
-                     survivor_slots=sum(min(s_, capacity) for s_ in slots_r), bar=bar)
-    if rows is not None:
-        return rows[0][:, :rows[2]], rows[1][:rows[2]]
-    if keys is None:
-        return None, None
-    return torch.stack([keys & 0xFFFFFFFF, keys >> 32]), vals
+        _step_stats(stats, g, screen, fixw, table, ht, capacity, launches, sketch_void, n_rescored, shard, bar, rank, world)
+    return pairs, scores

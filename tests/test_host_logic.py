@@ -416,3 +416,90 @@ def test_sketch_safe_shift_keeps_a_whole_piece_below_2_32():
         if s < scan.MAX_SCREEN_SHIFT:
             assert ((f_hi >> (40 - s - 1)) + 2) * scan.SKETCH_PIECE_PATHS >= 1 << 32, (w, s)
     assert scan.sketch_safe_shift(int(round(2.0 ** 40 / math.log(2.0)))) == 18      # Adamic-Adar: 1 / ln 2 is the heaviest weight
+
+
+def _status(slots=100, cand=5000, n_sel=60, cut=1.0, status=0, thr=float("-inf"), walked=0, bar=0.5):
+    """One rank's row of scan_topk's status table, as the step's host read returns it (float words as signed int32 bits)."""
+    bits = lambda x: int(np.float32(x).view(np.int32))                    # noqa: E731
+    return [slots, cand, n_sel, bits(cut), status, bits(thr), walked, bits(bar)]
+
+
+def _verdict(table, **kw):
+    """scan._verdict of a one-rank (or given) table: capacity 1000, k2 = 50, screened, under a bar, at the second launch, no heads
+    unless ``head_budget`` is given (then shift 8: the bar of 0.5 is 128 table units, budgets 38.4 .. 74.24 are in range)."""
+    from eps_amd import scan
+    args = dict(capacity=1000, walked_cap=100, head_budget=None, shift=None, screened=True, rescore_all=False, k2=50,
+                bar_set=True, launches=2, head_trouble=0, head_stale=0)
+    if kw.get("head_budget") is not None:
+        args["shift"] = 8
+    args.update(kw)
+    return scan._verdict(table if isinstance(table[0], list) else [table], **args)
+
+
+def test_scan_verdict_repeats_void_launches():
+    """scan._verdict, the step's retry decision: a void launch (sketch set full, head table void, pre-filter unsound) repeats the
+    SAME launch -- it does not count twice --, in the parent's order of checks; unknown status bits raise."""
+    from eps_amd import ops
+    v = _verdict(_status(status=8 | 16))
+    assert (v.action, v.launches, v.drop_heads) == ("sketch off", 1, False)
+    assert _verdict(_status(status=8 | 1)).action == "sketch off"                 # (bit 3 is looked at first)
+    for bad in (1, 2, 32, 1 << 20):
+        with pytest.raises(ops._lib.EpsError, match="full hash table"):
+            _verdict(_status(status=bad | 4), head_budget=64, walked_cap=0)      # (before the head table's verdict)
+    assert _verdict(_status(status=4 | 16)).action == "done"                      # (bit 2 means nothing without heads)
+    # the walked list overflowed: doubled; a second overflow in the call: heads off
+    v = _verdict(_status(walked=101), head_budget=64)
+    assert (v.action, v.launches, v.drop_heads, v.head_trouble, v.head_stale) == ("grow walked list", 1, True, 1, 0)
+    v = _verdict(_status(walked=101), head_budget=64, head_trouble=1)
+    assert (v.action, v.head_trouble) == ("heads off", 2)
+    # a table built for another bar (a head as heavy as the bar, or a budget above HEAD_KEEP[1] x bar): rebuilt, the list unchanged
+    for row, budget in ((_status(status=4), 64), (_status(), 75)):
+        v = _verdict(row, head_budget=budget)
+        assert (v.action, v.launches, v.drop_heads, v.head_trouble, v.head_stale) == ("rebuild heads", 1, True, 0, 1)
+    assert _verdict(_status(status=4), head_budget=64, head_stale=2).action == "heads off"
+    assert _verdict(_status(walked=101, status=4), head_budget=64).action == "grow walked list"     # (an overflow counts as one)
+    # a good launch keeps its result; a budget below HEAD_KEEP[0] x bar drops the table for the next launch only
+    v = _verdict(_status(walked=100), head_budget=64)
+    assert (v.action, v.launches, v.drop_heads) == ("done", 2, False)
+    v = _verdict(_status(), head_budget=38)
+    assert (v.action, v.launches, v.drop_heads) == ("done", 2, True)
+    # the cut below one rank's pre-filter threshold: everything re-scored (the dropped head table is still reported)
+    v = _verdict([_status(cut=1.0, thr=0.9), _status(cut=1.0, thr=1.5)])
+    assert (v.action, v.launches) == ("rescore all", 1)
+    assert _verdict(_status(cut=1.0, thr=1.5), head_budget=38).drop_heads
+    assert _verdict(_status(cut=1.0, thr=1.0)).action == "done"
+    assert _verdict(_status(cut=1.0, thr=1.5), rescore_all=True).action == "done"
+    assert _verdict(_status(cut=1.0, thr=1.5), screened=False).action == "done"
+    # a -inf cut is not exempt while any rank filtered; with no finite threshold it means "too few": the bar is lowered
+    inf = float("-inf")
+    assert _verdict([_status(cut=inf, n_sel=10), _status(cut=inf, thr=0.7, n_sel=10)]).action == "rescore all"
+    assert _verdict([_status(cut=inf, n_sel=10), _status(cut=inf, n_sel=10)]).action == "lower bar"
+
+
+def test_scan_verdict_corrects_the_bar():
+    """scan._verdict after a sound launch: an overflowing list rescans just below the cut with four times the list (under the same
+    bar when the cut is -inf) -- before any pre-filter check; too few pairs above the bar lower it, and drop it after launch 3;
+    and every repeat of the same launch ends the call with EpsError once it would pass MAX_LAUNCHES."""
+    from eps_amd import ops, scan
+    v = _verdict(_status(slots=1001, thr=2.0))
+    assert (v.action, v.launches) == ("rescan below cut", 2)
+    assert _verdict(_status(slots=1001, cut=float("-inf"), n_sel=0)).action == "rescan wider"
+    assert _verdict([_status(), _status(slots=1001)]).action == "rescan below cut"
+    # too few selected: without heads compared with the candidates there are, with heads (a walk counts what it touched) with k2
+    for kw in ({}, {"head_budget": 64}):
+        v = _verdict(_status(n_sel=49), **kw)
+        assert (v.action, v.launches) == ("lower bar", 2)
+        assert _verdict(_status(n_sel=49), launches=3, **kw).action == "lower bar"
+        assert _verdict(_status(n_sel=49), launches=4, **kw).action == "drop bar"
+        assert _verdict(_status(n_sel=50), **kw).action == "done"
+    assert _verdict(_status(n_sel=30, cand=30)).action == "done"
+    assert _verdict(_status(n_sel=30, cand=30), head_budget=64).action == "lower bar"
+    assert _verdict(_status(n_sel=0), bar_set=False).action == "done"
+    assert _verdict([_status(n_sel=25), _status(n_sel=25)]).action == "done"
+    # the MAX_LAUNCHES guard of each repeat
+    last = scan.MAX_LAUNCHES - 1
+    assert _verdict(_status(status=8), launches=last).launches == last - 1
+    for row, kw, msg in ((_status(status=8), {}, "sketch pieces"), (_status(walked=101), {"head_budget": 64}, "skipped heads"),
+                         (_status(status=4), {"head_budget": 64}, "skipped heads"), (_status(thr=2.0), {}, "re-scoring pre-filter")):
+        with pytest.raises(ops._lib.EpsError, match=msg):
+            _verdict(row, launches=scan.MAX_LAUNCHES, **kw)
