@@ -109,6 +109,10 @@ SIGNATURES = {
     "eps_rescore_runs_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "eps_pack_keys": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "eps_unpack_keys": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "eps_two_path_counts": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "eps_katz_workspace_bytes": (_i64, [_i64]),
+    "eps_katz_pair_scores": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_double, _c.c_double,
+                                    _c.c_double, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

@@ -1,5 +1,5 @@
 """Evaluation harness of the rank stage with the reference's names and signatures
-(train_and_eval.py:11-29, :98-156, :158-193, :218-270; adamic_utils.py:27-68), on the HIP scoring
+(train_and_eval.py:11-29, :98-156, :158-193, :218-270, :272-343; adamic_utils.py:27-68), on the HIP scoring
 path.  ``Evaluator`` restates ogb 1.3.1's Hits@K [third-party, parity unpinned]:
 ``kth = topk(y_pred_neg, K)[-1]; hits = mean(y_pred_pos > kth)``; 1.0 when there are fewer than K
 negatives; strict ``>``.
@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .heuristics import AA, get_A, resource_allocation
+from .heuristics import AA, KATZ_BETA, exact_katz, get_A, resource_allocation, truncated_katz
 
 
 class Evaluator:
@@ -131,5 +131,27 @@ def test_resource_allocation(model, data, split_edge, evaluator, batch_size, arg
     pos_test_pred = resource_allocation(A, split_edge['test']['edge'])
     neg_test_pred = resource_allocation(A, split_edge['test']['edge_neg'])
     pos_train_pred = torch.ones(split_edge['train']['edge'].size(0))
+    return _hits_table(args.dataset, evaluator, pos_train_pred, pos_valid_pred, neg_valid_pred, pos_test_pred,
+                       neg_test_pred)
+
+
+def test_katz(model, data, split_edge, evaluator, batch_size, args, device):
+    """train_and_eval.py:272-343.  collab: the truncated series beta*A + 2*beta^2*A^2 + beta^3*A^3 at the pairs (HIP pair
+    kernel, float32 predictions like the reference's SciPy float32 products); every other dataset: inv(I - beta*A) - I at the
+    pairs (dense float64 inverse, float64 predictions).  H_train (``data.adj_t``) scores eval_train and the validation lists,
+    H (``data.full_adj_t``) the test lists; the pairs are taken as stored (no permutation)."""
+    assert args.model == "katz"
+    A = get_A(data.full_adj_t, data.num_nodes)
+    A_train = get_A(data.adj_t, data.num_nodes)
+    score = truncated_katz if args.dataset == "collab" else exact_katz
+
+    def at(G, key, split):
+        return score(G, split_edge[split][key].t(), beta=KATZ_BETA)
+
+    pos_train_pred = at(A_train, 'edge', 'eval_train')
+    pos_valid_pred = at(A_train, 'edge', 'valid')
+    neg_valid_pred = at(A_train, 'edge_neg', 'valid')
+    pos_test_pred = at(A, 'edge', 'test')
+    neg_test_pred = at(A, 'edge_neg', 'test')
     return _hits_table(args.dataset, evaluator, pos_train_pred, pos_valid_pred, neg_valid_pred, pos_test_pred,
                        neg_test_pred)

@@ -7,6 +7,7 @@ types:
 * ``AA(A, edge_index, batch_size=2000)``             <- adamic_utils.py:13-25
 * ``resource_allocation(adj_matrix, link_list, batch_size=32768)``  <- train_and_eval.py:195-216
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
+* ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
 
 Where the reference loops over 2000-pair batches on one CPU thread through SciPy, these upload
 the pair list once, run ``eps_pair_scores`` (csrc/pair_intersect.hip) over all of it and hand
@@ -15,6 +16,7 @@ it does not change results (the reference's batching does not either).  There is
 """
 from __future__ import annotations
 
+from fractions import Fraction
 from typing import Optional, Tuple
 
 import numpy as np
@@ -142,3 +144,112 @@ def common_neighbors(adj: CSRGraph, edges: torch.Tensor) -> torch.Tensor:
     u, v = _as_pairs(edges, g.device, g.n_rows)
     _, cn, _ = pair_scores_streamed(g, u, v, None, want_cn=True)
     return cn
+
+
+# ----------------------------------------------------------------------------------------------------------- Katz
+KATZ_BETA = 0.05                  # train_and_eval.py:284
+EXACT_KATZ_MAX_NODES = 16384      # one dense float64 N x N matrix is 2 GiB at the cap
+
+
+def katz_coefficients(beta: float = KATZ_BETA, iterations: int = 2) -> Tuple[float, float, float]:
+    """Coefficients of A, A^2, A^3 in the reference's truncated series (train_and_eval.py:285-291): ``H = beta*A``, then
+    ``H += beta*(A @ H)`` ``iterations`` times.  Each step adds beta*A*H to the WHOLE running H, so two steps give
+    beta*A + 2*beta^2*A^2 + beta^3*A^3 (not the textbook series).  Computed exactly from the decimal beta, rounded once."""
+    if not 0 <= int(iterations) <= 2:
+        raise EpsError(f"truncated Katz: iterations must lie in [0, 2] (the kernel sums up to A^3), got {iterations}")
+    b = Fraction(repr(float(beta)))
+    c = [b]                                            # c[k] is the coefficient of A^(k+1)
+    for _ in range(int(iterations)):
+        c = [x + y for x, y in zip(c + [Fraction(0)], [Fraction(0)] + [b * x for x in c])]
+    c += [Fraction(0)] * (3 - len(c))
+    return tuple(float(x) for x in c)
+
+
+def _katz_transpose(g: CSRGraph):
+    """(A^T, paths_out, paths_in) of a device graph, cached on it.  A symmetric A (every graph add_edges builds) is its own
+    transpose: the kernel then reads one set of arrays for both ends."""
+    if "katz_t" not in g._cache:
+        from .graph import _coalesce
+        row, col, val = g.coo()
+        rowptr_t, col_t, val_t = _coalesce(col, row, val, g.n_cols, g.n_rows)
+        sym = torch.equal(rowptr_t, g.rowptr) and torch.equal(col_t, g.col) and (
+            val is None or torch.equal(val_t, val))
+        gt = g if sym else CSRGraph(rowptr_t, col_t, val_t, g.n_cols, g.n_rows)
+        p_out = ops.two_path_counts(g.rowptr, g.col)
+        p_in = p_out if sym else ops.two_path_counts(gt.rowptr, gt.col)
+        g._cache["katz_t"] = (gt, p_out, p_in)
+    return g._cache["katz_t"]
+
+
+def truncated_katz(A, edge_index, beta: float = KATZ_BETA, iterations: int = 2, device_out: bool = False) -> torch.Tensor:
+    """The collab branch of test_katz (train_and_eval.py:285-291) read at the pairs: float32[E] of
+    c1*A[u,v] + c2*(A^2)[u,v] + c3*(A^3)[u,v] with ``katz_coefficients(beta, iterations)``, one eps_katz_pair_scores
+    launch set (csrc/katz_pairs.hip) -- neither A^2 nor A^3 is formed.  ``A``: get_A output or SciPy; any square
+    matrix (a non-symmetric one gets its transpose built once and cached).  ``edge_index``: [2,E]."""
+    coeffs = katz_coefficients(beta, iterations)
+    g = _as_graph(A)
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"truncated Katz needs a square adjacency, got {g.sparse_sizes()}")
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    gt, p_out, p_in = _katz_transpose(g)
+    out = ops.katz_pair_scores(g.rowptr, g.col, g.val, gt.rowptr, gt.col, gt.val, p_out, p_in, g.n_rows, u, v, coeffs)
+    return out if device_out else out.cpu()
+
+
+def exact_katz_bytes(n: int) -> int:
+    """Device memory the exact branch needs for an n-node graph: I - beta*A and its inverse, float64 n x n each."""
+    return 2 * 8 * int(n) * int(n)
+
+
+_KATZ_SOLVE_COLUMNS = 512   # right-hand-side columns per triangular solve (see _katz_inverse)
+
+
+def _katz_inverse(g: CSRGraph, beta: float) -> torch.Tensor:
+    """inv(I - beta*A) - I, dense float64 on the device, cached on the graph (test_katz reads one graph's H three times).
+    One LU factorisation (rocSOLVER through torch.linalg), then the identity's columns are solved in blocks of
+    _KATZ_SOLVE_COLUMNS: a single triangular solve over all N columns (what torch.linalg.inv issues) fails in hipBLAS at
+    N = 4267 (HIPBLAS_STATUS_ALLOC_FAILED: it needs more than the workspace torch gives the handle), blocks of 512 run at
+    N = 4267 and at the 16384 cap."""
+    key = ("katz_inv", float(beta))
+    if key not in g._cache:
+        n = g.n_rows
+        m = torch.zeros((n, n), dtype=torch.float64, device=g.device)
+        row, col, _ = g.coo()
+        # beta*A is formed in float32 like the reference's SciPy product, then the arithmetic is float64 (coalesced: one write
+        # per entry)
+        m[row, col] = -(g.values_or_ones() * float(beta)).to(torch.float64)
+        m.diagonal().add_(1.0)
+        lu, piv, info = torch.linalg.lu_factor_ex(m)
+        del m
+        if int(info.item()) != 0:
+            raise EpsError(f"exact Katz: I - {beta}*A is singular (N={n}); the inverse does not exist")
+        h = torch.empty((n, n), dtype=torch.float64, device=g.device)
+        rhs = torch.empty((n, min(n, _KATZ_SOLVE_COLUMNS)), dtype=torch.float64, device=g.device)
+        for s in range(0, n, _KATZ_SOLVE_COLUMNS):
+            e = min(n, s + _KATZ_SOLVE_COLUMNS)
+            b = rhs[:, :e - s].zero_()
+            b[torch.arange(s, e, device=g.device), torch.arange(e - s, device=g.device)] = 1.0
+            h[:, s:e] = torch.linalg.lu_solve(lu, piv, b)
+        del lu, rhs
+        if not bool(torch.isfinite(h).all()):
+            raise EpsError(f"exact Katz: I - {beta}*A is numerically singular (N={n}); the inverse is not finite")
+        h.diagonal().sub_(1.0)
+        g._cache[key] = h
+    return g._cache[key]
+
+
+def exact_katz(A, edge_index, beta: float = KATZ_BETA, device_out: bool = False) -> torch.Tensor:
+    """The non-collab branch of test_katz (train_and_eval.py:293-294): ``inv(I - beta*A) - I`` read at the pairs, float64[E]
+    like the reference.  One dense float64 LU inverse per graph through torch.linalg (a factorisation per graph, not a
+    per-pair hot path); graphs above EXACT_KATZ_MAX_NODES nodes are refused before anything reaches the device."""
+    n = A.n_rows if isinstance(A, CSRGraph) else A.shape[0]
+    if n > EXACT_KATZ_MAX_NODES:
+        raise EpsError(f"exact Katz: N={n} exceeds EXACT_KATZ_MAX_NODES={EXACT_KATZ_MAX_NODES}; the dense inverse would need "
+                       f"{exact_katz_bytes(n) / 2**30:.1f} GiB of device memory (two {n} x {n} float64 matrices)")
+    g = _as_graph(A)
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"exact Katz needs a square adjacency, got {g.sparse_sizes()}")
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    h = _katz_inverse(g, beta)
+    out = h[u.long(), v.long()]
+    return out if device_out else out.cpu()

@@ -142,6 +142,58 @@ def pair_scores(rowptr, col, val, node_w, n_nodes: int, u, v, want_count=True, w
     return count, cn, ws
 
 
+def two_path_counts(rowptr, col) -> torch.Tensor:
+    """paths[x] = sum over the entries w of row x of the length of row w: the two-paths out of every node (int64)."""
+    dev = _need_gpu(rowptr, col)
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    n = rowptr.numel() - 1
+    if n < 0:
+        raise _lib.EpsError("rowptr must hold at least one entry")
+    out = torch.empty(n, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().eps_two_path_counts(_ptr(rowptr), _ptr(col), n, _ptr(out), _stream(dev)),
+                   "eps_two_path_counts")
+    return out
+
+
+KATZ_CHUNK = 1 << 20   # pairs per eps_katz_pair_scores call (its workspace is ~132 bytes per pair)
+
+
+def katz_pair_scores(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_in, n_nodes: int, u, v,
+                     coeffs: Sequence[float]) -> torch.Tensor:
+    """-> float32[E]: c1*A[u,v] + c2*(A^2)[u,v] + c3*(A^3)[u,v] (float64 accumulate, one rounding).  ``(rowptr_t,
+    col_t, val_t)`` is A's transpose (A's own tensors when A is symmetric); ``paths_out`` / ``paths_in`` are
+    ``two_path_counts`` of A and of A^T."""
+    dev = _need_gpu(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_in, u, v)
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
+    _chk(rowptr_t, torch.int64, "rowptr_t"); _chk(col_t, torch.int32, "col_t"); _chk(val_t, torch.float32, "val_t")
+    _chk(paths_out, torch.int64, "paths_out"); _chk(paths_in, torch.int64, "paths_in")
+    _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v")
+    if u.numel() != v.numel():
+        raise _lib.EpsError("u and v differ in length")
+    if rowptr.numel() != n_nodes + 1 or rowptr_t.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"katz_pair_scores: A and A^T must both be [{n_nodes},{n_nodes}]")
+    if paths_out.numel() != n_nodes or paths_in.numel() != n_nodes:
+        raise _lib.EpsError(f"katz_pair_scores: two-path counts must hold {n_nodes} entries")
+    c = [float(x) for x in coeffs]
+    if len(c) != 3:
+        raise _lib.EpsError(f"katz_pair_scores: expected three coefficients, got {len(c)}")
+    n = u.numel()
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(lib.eps_katz_workspace_bytes(min(n, KATZ_CHUNK))) + 7) // 8, dtype=torch.int64, device=dev)
+        for s in range(0, n, KATZ_CHUNK):
+            e = min(n, s + KATZ_CHUNK)
+            _lib.check(lib.eps_katz_pair_scores(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(rowptr_t), _ptr(col_t), _ptr(val_t),
+                                                _ptr(paths_out), _ptr(paths_in), n_nodes, _ptr(u[s:e]), _ptr(v[s:e]), e - s,
+                                                c[0], c[1], c[2], _ptr(ws), _ptr(out[s:e]), _stream(dev)),
+                       "eps_katz_pair_scores")
+    return out
+
+
 def expand_max_nodes() -> int:
     return int(_lib.load().eps_expand_max_nodes())
 

@@ -16,7 +16,7 @@ from pathlib import Path
 import torch
 
 from .datasets import get_data
-from .evaluate import evaluators, hits, test, test_adamic, test_resource_allocation
+from .evaluate import evaluators, hits, test, test_adamic, test_katz, test_resource_allocation
 from .graph import add_edges
 from .runlog import Logger
 from .models import build_model, default_model_configs
@@ -118,13 +118,11 @@ def _load_proposals(args, split_edge) -> torch.Tensor:
     return splice_valid_proposals(rows, split_edge['valid']['edge']) if args.valid_proposal else rows
 
 
-_HEURISTIC_EVAL = {"adamic_ogb": test_adamic, "resource_allocation": test_resource_allocation}
+_HEURISTIC_EVAL = {"adamic_ogb": test_adamic, "resource_allocation": test_resource_allocation, "katz": test_katz}
 
 
 def _evaluate(args, model, data, split_edge, evaluator, device):
     """{Hits@K: (train, valid, test)} of the model on the current graphs (the dispatch of rank.py:337-349)."""
-    if args.model == "katz":
-        raise NotImplementedError("katz (sparse inverse) is outside the accelerated path")
     if args.model in _HEURISTIC_EVAL:
         return _HEURISTIC_EVAL[args.model](model, data, split_edge, evaluator, args.batch_size, args, device)
     return test(model, data, split_edge, evaluator, args.batch_size or (1 << 16), args, device)

@@ -631,6 +631,22 @@ int eps_pack_keys(const float *score, const int64_t *ids_or_null, int64_t id_bas
 int eps_unpack_keys(const int64_t *keys, int64_t n, float *score_or_null, int64_t *id_or_null,
                     void *stream);
 
+/* ---- Truncated Katz at pairs (csrc/katz_pairs.hip) --------------------------------------------
+ * Replaces the collab branch of train_and_eval.py:272-343 (test_katz): `H = beta*A; H += beta*(A @ H)`
+ * twice, read at the evaluation pairs -- without forming A^2 or A^3:
+ *   out[p] = c1*A[u,v] + c2*(A^2)[u,v] + c3*(A^3)[u,v]          (float64 accumulate, float32 result)
+ * A is any square CSR [n_nodes x n_nodes] (values or NULL); rowptr_t / col_t / val_t is its transpose
+ * (pass A's own pointers when A is symmetric).  paths_out = eps_two_path_counts(A), paths_in =
+ * eps_two_path_counts(A^T) (the same array for a symmetric A): they decide, per pair, from which end the
+ * three-hop walk starts.  u, v: int32[n_pairs] in [0, n_nodes).  workspace: device, 8-byte aligned,
+ * contents arbitrary, eps_katz_workspace_bytes(n_pairs) bytes.  Bitwise deterministic. */
+int eps_two_path_counts(const int64_t *rowptr, const int32_t *col, int64_t n_nodes, int64_t *paths, void *stream);
+int64_t eps_katz_workspace_bytes(int64_t n_pairs);
+int eps_katz_pair_scores(const int64_t *rowptr, const int32_t *col, const float *val, const int64_t *rowptr_t,
+                         const int32_t *col_t, const float *val_t, const int64_t *paths_out, const int64_t *paths_in,
+                         int64_t n_nodes, const int32_t *u, const int32_t *v, int64_t n_pairs, double c1, double c2,
+                         double c3, void *workspace, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
