@@ -9,7 +9,7 @@ import subprocess
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("EPS_LIB_PATH") or os.path.join(_HERE, "libeps_hip.so")  # override: kernel A/B experiments
+LIB_PATH = os.path.join(_HERE, "libeps_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 _c = ctypes

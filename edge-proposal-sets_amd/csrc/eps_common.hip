@@ -92,26 +92,6 @@ int eps_take_counters8(unsigned int **counters, hipStream_t stream, const char *
     return EPS_OK;
 }
 
-// Eight counters on eight 256-byte lines (r06): same-address atomics are served at ~11 ns each by the L2, and counters that share
-// a line queue behind each other like one -- a list of 6 M pairs handed out in 64-pair tickets spent 1 ms of its 4.4 on ONE word.
-// The kernel draws from the counter of its XCD (ticket t of counter y = unit t * 8 + y) and helps the others when its own runs out.
-__device__ unsigned int g_work_counter8s[EPS_COUNTER_SLOTS][8 * EPS_SPREAD_STRIDE];
-static std::atomic<unsigned int> g_counter8s_turn{0};
-
-int eps_take_counters8_spread(unsigned int **counters, hipStream_t stream, const char *who)
-{
-    if (hipGetSymbolAddress((void **)counters, HIP_SYMBOL(g_work_counter8s)) != hipSuccess) {
-        eps_set_error("%s: cannot resolve the work counters", who);
-        return EPS_ELAUNCH;
-    }
-    *counters += 8 * EPS_SPREAD_STRIDE * (g_counter8s_turn.fetch_add(1) % EPS_COUNTER_SLOTS);
-    if (hipMemsetAsync(*counters, 0, 8 * EPS_SPREAD_STRIDE * sizeof(unsigned int), stream) != hipSuccess) {
-        eps_set_error("%s: cannot reset the work counters", who);
-        return EPS_ELAUNCH;
-    }
-    return EPS_OK;
-}
-
 // ---- loading the library's code objects ahead of their first use ---------------------------------------------------------------
 // The HIP runtime loads a translation unit's code object at the first launch of one of its kernels; a fresh process pays 10-30 ms
 // for each of the larger ones (the rocPRIM sorts) inside whatever step happens to come first -- and filter.py is one fresh

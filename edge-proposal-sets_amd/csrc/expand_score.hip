@@ -40,9 +40,7 @@
 #define EX_THREADS 1024
 #define EX_WAVES (EX_THREADS / 64)
 #define EX_FIXED_SHIFT 40
-#ifndef EX_RING
 #define EX_RING 2           // first units of a wave's next rows in flight (1: 60 % slower list pass; 4, 8: no faster)
-#endif
 #define EX_LONGQ 1024       // rows longer than one unit queued per column and pass (static LDS)
 #define EX_MAX_WPT 26       // bitmap words per thread: 26 * 1024 words * 5.5 B = 143 KiB + 10 KiB of tables
 #define EX_RANGES 512       // id ranges per column: path histogram and tile plan

@@ -28,30 +28,19 @@
 // candidate instead of the survivors above a bar.
 #include "eps_common.h"
 #include <string.h>
-#include <stdlib.h>
 
 // Geometry (compile-time; the shipped values are the measured best on the ppa-sized graphs).  FS_UR must be 2 * FS_THREADS.
-#ifndef FS_THREADS
 #define FS_THREADS 1024
-#endif
-#ifndef FS_WG_PER_CU
 #define FS_WG_PER_CU 1       // workgroups resident per CU: the LDS is split between them
-#endif
 #define FS_WAVES (FS_THREADS / 64)
 #define FS_FIXED_SHIFT 40
-#ifndef FS_RC
 #define FS_RC 512            // rows (neighbours w of v) described per round
-#endif
 #define FS_UR (2 * FS_THREADS)   // 64-entry units per round (two list entries per thread)
 #define FS_UPAD 384          // list entries past the last unit a prefetching wave may touch: they name the empty row
-#ifndef FS_RANGES
 #define FS_RANGES 512        // id ranges per column: path histogram and tile plan
-#endif
 #define FS_CHUNK 8192        // survivor slots reserved per global atomic
 #define FS_SVCAP 384         // survivors of a column parked in LDS until its tiles are done (more: resolved on the spot)
-#ifndef FS_MAX_TILE_BITS
 #define FS_MAX_TILE_BITS 12  // candidate ranks per tile <= 4096 (8-byte accumulators in LDS)
-#endif
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -543,21 +532,12 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             } else {
                 // the list: thread per bitmap word (neighbouring lanes -> neighbouring ranks), ascending u
                 fs_barrier();                             // rank tables complete
-#ifdef FS_ABL_NOULIST      // (timing-only ablations, tools/r06_full_list_ablate.sh: the outputs are wrong)
-                if (p.no_pad == 7)
-#endif
                 for (int wi = tid; wi < words_v; wi += FS_THREADS) {
                     uint32_t bits = bm[wi];
                     if (bits) {
                         uint32_t run = base32[wi >> 3] + pre8[wi];
                         do {
-#if defined(FS_ABL_ULIST_NOSTORE)
-                            asm volatile("" ::"v"(win_lo + wi * 32 + __builtin_ctz(bits)), "v"(run++));
-#elif defined(FS_ABL_ULIST_SMALL)
-                            p.cand_u[(obase + run++) & 0x3FFFF] = win_lo + wi * 32 + __builtin_ctz(bits);
-#else
                             p.cand_u[obase + run++] = win_lo + wi * 32 + __builtin_ctz(bits);
-#endif
                             bits &= bits - 1;
                         } while (bits);
                     }
@@ -665,13 +645,8 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                     // bounds the graph's scores before it takes this path -- candidates.fused_scores_fit)
                     if ((a0 | a1) < 0) atomicOr(p.status, 4u);
                     float *o = p.out_score + obase + r0 + i;
-#ifdef FS_ABL_NOSCORESTORE
-                    if (a0 == 0x7fffffffffffffffll)
-#endif
-                    {
                     o[0] = (float)((double)a0 * (1.0 / (double)(1ll << FS_FIXED_SHIFT)));
                     if (i + 1 < nslots) o[1] = (float)((double)a1 * (1.0 / (double)(1ll << FS_FIXED_SHIFT)));
-                    }
                 } else {
                     if (a0 >= thr_fix) survivor(i, a0);
                     if (a1 >= thr_fix && i + 1 < nslots) survivor(i + 1, a1);
@@ -758,9 +733,6 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                             // the common lane: four candidates of one tile -> four consecutive records, ONE 16-byte store
                             // (dword-aligned; four scattered 4-byte stores cost four write requests per 64-byte chunk)
                             const uint32_t p0 = atomicAdd(&tile_cur[(uint32_t)t_lo + tfirst], 4u);
-#ifdef FS_ABL_NORECSTORE
-                            if (p0 == 0xdeadbeefu)
-#endif
                             fs_store4(my_scratch + p0, rank[0] | krec, rank[1] | krec, rank[2] | krec, rank[3] | krec);
                         } else {
                         if (tfirst == tlast || ncand == 0) {
@@ -776,9 +748,6 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                         // one store per entry, no branch: what is not a candidate of the window lands in the trash line
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-#ifdef FS_ABL_NORECSTORE
-                            if (pos[e] == 0xdeadbeefu)
-#endif
                             my_scratch[cand[e] ? pos[e] : p.cap_records + lane] = rank[e] | krec;
                         }
                     });
@@ -804,9 +773,6 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 };
                 auto add = [&](uint32_t r, bool live) {
                     if (!live) return;                       // (mostly whole waves: the tail of a bucket)
-#ifdef FS_ABL_NOACC
-                    if (r != 0xdeadbeefu) return;
-#endif
                     const uint32_t k = r >> p.tile_bits;
                     const long long fx = single ? vwfix[k] : my_gfix[k];
                     atomicAdd(&acc[r & tile_mask], (unsigned long long)fx);
@@ -984,10 +950,8 @@ static int fs_range_shift(int64_t ids, int tile_bits)
 
 static bool fs_pick_geometry(int64_t n_nodes, fs_geometry *g)
 {
-    // (EPS_FS_MIN_WIN: geometry experiments -- more, narrower id windows than the LDS asks for)
-    static const int64_t min_win = [] { const char *e = getenv("EPS_FS_MIN_WIN"); return e && atoi(e) > 0 ? (int64_t)atoi(e) : (int64_t)1; }();
     for (int tile_bits = FS_MAX_TILE_BITS; tile_bits >= 9; --tile_bits)
-        for (int64_t n_win = min_win; n_win <= 4096; ++n_win) {
+        for (int64_t n_win = 1; n_win <= 4096; ++n_win) {
             const int64_t words = (((n_nodes + n_win - 1) / n_win + 31) / 32 + 1023) / 1024 * 1024;
             const int64_t win_ids = words * 32;
             if ((n_nodes + win_ids - 1) / win_ids != n_win) continue;        // rounding made a window superfluous

@@ -18,9 +18,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define G_BM 128
 #define G_BN 128
-#ifndef G_BK
 #define G_BK 16  // 40 KiB of LDS per workgroup -> four resident workgroups per CU on the aligned path (128 VGPRs); 32 and 64 measured slower
-#endif
 #define G_LD (G_BK + 4)
 #define G_F4 (G_BK / 4)          // float4 per tile row
 #define G_NLD (G_BM * G_F4 / 256)  // float4 per thread and operand

@@ -17,14 +17,10 @@
 // =====================================================================================
 #define PG_THREADS 1024
 #define PG_WAVES (PG_THREADS / 64)
-#ifndef PG_CHUNK
 #define PG_CHUNK 16384
-#endif
 #define PG_QCAP 512             // per-wave hit queue entries (2 KiB)
 #define PG_MAX_WORDS (1 << 15)  // 2^20 bits = 128 KiB
-#ifndef PG_RING
 #define PG_RING 4               // pairs whose row loads are kept in flight per wave
-#endif
 
 // Bitmap test of one row u against the chunk's column v with the weights gathered INLINE (a dependent
 // global load per hit): used for weighted graphs, float64 weights, hashed bitmaps and oversized pairs.

@@ -23,18 +23,14 @@
 //     binary search), so a degree-100k hub costs log2(d) probes per element of the short row instead of a full read.
 // HBM traffic is the algorithmic minimum: both rows once, coalesced; rowptr/pair/outputs once.
 #include "pair_common.h"
-#include <stdlib.h>
 
 #define PI_WAVES 4           // waves per workgroup
 #define PI_CAP 1024          // long-row entries staged per wave and pass (4 KiB of LDS per wave)
 #define PI_QCAP 256          // per-wave hit queue (1 KiB): deferred node_w gathers
 #define PI_INPLACE_RATIO 32  // long row searched in place when long > PI_CAP && long >= ratio*short
-#ifndef PI_TICKET
 #define PI_TICKET 4          // consecutive 64-pair chunks per ticket of the launch that scores the longer pairs (PART 2)
-#endif
-#ifndef PI_SMALL
 #define PI_SMALL 128         // pairs whose LONGER row has at most this many entries are scored four at a time (16 lanes each).
-#endif                       // r06, 2^24 pairs of the ppa-like graph, uniform / stored edges: 64: 3.55 / 10.64 ms, 128: 3.33 / 10.41, 256: 5.20 / 11.81
+                             // r06, 2^24 pairs of the ppa-like graph, uniform / stored edges: 64: 3.55 / 10.64 ms, 128: 3.33 / 10.41, 256: 5.20 / 11.81
 #define PI_SMALL_LG (PI_SMALL == 256 ? 8 : PI_SMALL == 128 ? 7 : 6)
 
 // Lower bound over a sorted LDS array of 2^lg entries (padded with INT_MAX): fully unrolled, branch-free steps,
@@ -420,20 +416,10 @@ static int launch_pair_scores(const int64_t *rowptr, const int32_t *col, const f
         if (crc) return crc;
         crc = eps_take_counters8(&cls, stream, "eps_pair_scores");
         if (crc) return crc;
-        // (EPS_PAIR_SHAPE=split | single in the environment pins the shape for same-box A/Bs: tools/eval_pairs_bench.py)
-        static const int pinned = [] { const char *e = getenv("EPS_PAIR_SHAPE"); return !e ? 0 : (e[0] == 's' && e[1] == 'p') ? 1 : 2; }();
-        if (pinned) {
-            const unsigned int words[2] = {pinned == 1 ? 1u : 0u, 1u};       // {small, all}: all small -> split; none -> one at a time
-            if (hipMemcpyAsync(cls, words, sizeof(words), hipMemcpyHostToDevice, stream) != hipSuccess) {
-                eps_set_error("eps_pair_scores: cannot pin the launch shape");
-                return EPS_ELAUNCH;
-            }
-        } else {
-            const int64_t sampled = (n_chunks + PI_CLS_STRIDE - 1) / PI_CLS_STRIDE;
-            int64_t cb = (sampled + PI_WAVES - 1) / PI_WAVES;
-            if (cb > max_blocks) cb = max_blocks;
-            hipLaunchKernelGGL(pair_classify_kernel, dim3((unsigned)cb), block, 0, stream, rowptr, u, v, n_pairs, cls);
-        }
+        const int64_t sampled = (n_chunks + PI_CLS_STRIDE - 1) / PI_CLS_STRIDE;
+        int64_t cb = (sampled + PI_WAVES - 1) / PI_WAVES;
+        if (cb > max_blocks) cb = max_blocks;
+        hipLaunchKernelGGL(pair_classify_kernel, dim3((unsigned)cb), block, 0, stream, rowptr, u, v, n_pairs, cls);
         // (the split only runs on lists of mostly small pairs, where the launch of the longer pairs finds little to do: tickets of
         //  PI_TICKET chunks whatever the list's length -- 3 M negatives drew 47 k single-chunk tickets for 0.5 of their 1.16 ms)
         if (hw) {

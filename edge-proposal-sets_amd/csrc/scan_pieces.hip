@@ -38,28 +38,17 @@
 #include "eps_common.h"
 #include "scan_common.h"
 #include <string.h>
-#include <stdlib.h>
 
 #define SP_EMPTY 0u             // an empty key word; a key is stored as id + 1, so a clean table is all zeros in BOTH modes
 #define SP_MAXP (SP_M + 1)
 #define SP_UBITS 8192           // units per range of the unit -> row bitmap (64 lanes x 128 bits: one uint4 per lane)
-#ifndef SP_SB
 #define SP_SB 4                 // uint4 reads a thread issues together in the table sweeps
-#endif
-#ifndef SP_PACKED_X8
 #define SP_PACKED_X8 8u         // a packed piece holds at most this many eighths of 2^table_bits paths
-#endif
-#ifndef SP_MODE_RATIO
-#define SP_MODE_RATIO_WIDE 8000u   // ... in a plan for sketch launches (eps_scan_plan, variant bit 24)
 #define SP_MODE_RATIO 2270u     // fixed cost of a piece in hashed-path units (the planner's direct-vs-packed choice); r05: 1000 / 4000 re-measured
-#endif
-#ifndef SP_BATCH
+#define SP_MODE_RATIO_WIDE 8000u   // ... in a plan for sketch launches (eps_scan_plan, variant bit 24)
 #define SP_BATCH 8              // columns per ticket in the light tail of the column order
-#endif
-#ifndef SP_G
 #define SP_EM 128               // slots of the per-workgroup set of ids a SKETCH piece has reported (a power of two)
 #define SP_G 1                  // units (of 4 entries) a lane looks up, loads and inserts together
-#endif
 
 typedef int sp_v4i __attribute__((ext_vector_type(4)));
 
@@ -722,15 +711,6 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                     lid[i] = id - (uint32_t)lo_id;
                                     h[i] = mixv[i] >> (32 - bits);
                                 }
-#ifdef SP_ABL_PACKED_NOHASH
-                                // (timing-only ablation, tools/r06_packed_nohash.sh: what a PERFECT table for the sparse tail -- one
-                                //  non-returning add per path, no key, no probing -- would leave of the launch; the results are wrong.
-                                //  This is the measurement the sketch pieces came from: 8.96 -> 7.10 ms, profiles/r06/scan_structures.txt)
-#pragma unroll
-                                for (int i = 0; i < E; ++i)
-                                    if (pend & (1u << i)) atomicAdd(&lds[h[i]], f[i >> 2].fx);
-                                pend = 0u;
-#endif
 #pragma unroll
                                 for (int wide = 0; wide < 2; ++wide) {           // (two wide rounds: a fifth of the entries miss the first)
 #pragma unroll
@@ -1309,24 +1289,15 @@ extern "C" int eps_scan_row_sums(const int64_t *rowptr, const int32_t *col, cons
 // run against it -- one wave per pair, coalesced -- and sums the exact weights of the hits in float64.  The weights are
 // multiples of 2^-40 below 2^12, so the float64 sum is exact whatever the order: (float)sum is eps_filter_scan's score, bit
 // for bit (adamic_utils.py:13-25 / train_and_eval.py:195-216 / models.py:536-542 with the engine's fixed-point definition).
-#ifndef RS_THREADS
 #define RS_THREADS 1024
-#endif
 #define RS_CHUNK 256
 #define RS_BITS (1 << 20)       // ids per bitmap window: 128 KiB of LDS
 #define RS_SHORT 512            // rows up to this long go through rescore_short_kernel
-#ifndef RS_GROUP
 #define RS_GROUP 128            // consecutive 256-pair chunks that go to the same XCD (32 k pairs: most of a block of 2^9 v)
-#endif
-#ifndef RS_GB
 #define RS_GB 4                 // weight gathers of a trip issued together (r06: 16 x 64-bit partial sums in flight were 32 of the kernel's 94 VGPRs)
-#endif
-#ifndef RS_MINW
 #define RS_MINW 8               // waves per SIMD the kernel is compiled for: 8 = two 1024-thread workgroups per CU (<= 64 VGPRs)
-#endif
-#ifndef RS_NB
 #define RS_NB 8                 // entries of N(v) a lane has in flight per trip: a trip is three dependent latencies (row, bitmap,
-#endif                          // weights) and the survivors' rows are long (~1100 entries on the ppa-like graph: 2.2 G entries to stream
+                                // weights) and the survivors' rows are long (~1100 entries on the ppa-like graph: 2.2 G entries to stream
                                 // for 2 M pairs -- 4 / 8 / 12 / 16 in flight: 6.4 / 5.5 / 5.4 / 5.1 ms for all 4.85 M pairs)
 
 __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -1449,11 +1420,7 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
                                 const int32_t w = wv[b >> 2][b & 3];
                                 const uint32_t x = (uint32_t)(w - wlo);
                                 const bool hit = i < ve && x < (uint32_t)RS_BITS && ((bm[x >> 5] >> (x & 31)) & 1u);
-#ifdef RS_ABL_NOWEIGHT           /* (timing-only ablation, wrong results: what the dependent weight gathers of a trip cost) */
-                                add[bb] = hit ? 1ll : 0ll;
-#else
                                 add[bb] = hit ? (long long)fixw[w] : 0ll;
-#endif
                             }
 #pragma unroll
                             for (int bb = 0; bb < RS_GB; ++bb) acc += add[bb];
@@ -1854,7 +1821,7 @@ static void sp_plan_geometry(sp_params &p, const uint16_t *cuts, const uint32_t 
     p.packed_paths = (SP_PACKED_X8 << bits) / 8u;      // (8: load factor 1/2 of the 2^(bits + 1)-word table)
     p.packed_dmax = shift > 8 ? (shift - 8 < 24 ? shift - 8 : 24) : 0;      // (weights keep at least 2^-8 resolution ...
     if (dmax_arg >= 0 && dmax_arg < p.packed_dmax) p.packed_dmax = dmax_arg;   //  ... or what the caller asks for: see SP_VARIANT_DMAX)
-    // measured on the ppa-like graph (tools/r03_screen_ab.py): 1500 -> 23.8 ms, 2270 -> 23.5, 4000 -> 23.7; packed_paths 3584 / 4096 /
+    // measured on the ppa-like graph (r03): 1500 -> 23.8 ms, 2270 -> 23.5, 4000 -> 23.7; packed_paths 3584 / 4096 /
     // 5120 -> 24.0 / 23.5 / 24.1 ms
     p.mode_ratio = SP_MODE_RATIO;
     p.shift = shift;
@@ -2043,10 +2010,8 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
             : (variant == 0 ? scan_piece_kernel<512, false, false, false> : variant == 1 ? scan_piece_kernel<1024, false, false, false>
                                                                                          : scan_piece_kernel<256, false, false, false>);
     // (the step's main launch: every table present -> the body compiled for exactly that; with the column pack, its set-up as well)
-    // (EPS_SCAN_GENERIC=1 in the environment keeps the generic body for same-box A/Bs: tools/r05_heads_ab.py)
-    static const bool generic_only = [] { const char *e = getenv("EPS_SCAN_GENERIC"); return e && e[0] == '1'; }();
-    const bool full = !generic_only && !val && variant == 2 && plan && colrec && rowrec && heads && ssum;
-    EPS_REQUIRE(!pack || full || generic_only, "eps_scan_screen: the column pack serves the main launch only (variant 2, plan, records, heads, sum bounds)");
+    const bool full = !val && variant == 2 && plan && colrec && rowrec && heads && ssum;
+    EPS_REQUIRE(!pack || full, "eps_scan_screen: the column pack serves the main launch only (variant 2, plan, records, heads, sum bounds)");
     if (full) kern = pack ? scan_piece_kernel<256, false, true, true> : scan_piece_kernel<256, false, true, false>;
     if (p.sketch && variant == 2)      // (the 256-thread geometry only: the one the step's main launch runs in)
         kern = full ? (pack ? scan_piece_kernel<256, false, true, true, true> : scan_piece_kernel<256, false, true, false, true>)

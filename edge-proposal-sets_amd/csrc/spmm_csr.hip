@@ -13,9 +13,7 @@
 
 #include <type_traits>
 
-#ifndef SP_FLIGHT
 #define SP_FLIGHT 32   // neighbour rows in flight per wave (2: 7.3 ms, 4: 6.6, 8: 6.5, 16: 6.3, 32: 6.0 per ppa-like layer)
-#endif
 
 template <int VEC>
 struct VecT;

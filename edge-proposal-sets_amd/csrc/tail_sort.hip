@@ -603,7 +603,6 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
         // ---- A: digit histogram of this workgroup's chunk, published with the pass's tag ---------------------------------------
         if (tid < 256) s_hist[tid] = 0u;
         __syncthreads();
-#ifndef TS_ABL_NOHIST
         for (int64_t i0 = lo + (tid & ~63); i0 < hi; i0 += TS_T) {
             const int64_t i = i0 + lane;
             const bool live = i < hi;
@@ -613,7 +612,6 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
             const unsigned long long peers = ts_match8(d, live);
             if (live && (peers & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&s_hist[d], (uint32_t)__popcll(peers));
         }
-#endif
         __syncthreads();
         const uint32_t tag = (uint32_t)(ip + 1) << 24;
         if (tid < 256) __atomic_store_n(&st->hist[b][tid], tag | s_hist[tid], __ATOMIC_RELAXED);
@@ -648,7 +646,6 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
         // ---- C: stable ranking + scatter, tile by tile -----------------------------------------------------------------------
         uint64_t *dst_k = p.buf_k[cur ^ 1];
         uint32_t *dst_v = has_val ? p.buf_v[cur ^ 1] : nullptr;
-#ifndef TS_ABL_NOSCATTER
         for (int64_t t0 = lo; t0 < hi; t0 += TS_TILE) {
             for (int i = lane; i < 256; i += 64) s_cnt[wib][i] = 0u;
             uint64_t key[TS_KPT];
@@ -696,7 +693,6 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
                 }
             __syncthreads();
         }
-#endif
         cur ^= 1;
         epoch += 1;
         ts_grid_sync(&st->arrive, epoch * G);

@@ -436,7 +436,7 @@ def reverse_positions(rowptr: torch.Tensor, col: torch.Tensor, with_stats: bool 
 
 
 REVPOS_SORT_MIN = 1 << 62      # stored entries from which the reverse positions come out of a sort instead of searches: never by default --
-                               # measured 3.56 vs 3.37 ms on the ppa-like graph (tools/r06_revpos_time.py, profiles/r06/revpos_sorted.txt)
+                               # measured 3.56 vs 3.37 ms on the ppa-like graph (profiles/r06/revpos_sorted.txt)
 
 
 def reverse_positions_symmetric(rowptr: torch.Tensor, col: torch.Tensor):

@@ -63,8 +63,6 @@ SKETCH_PIECES = True          # in the main launch (heads, under a bar) the pack
 SKETCH_MIN_PATHS = 1.5        # ... when the bar is at least this many of the HEAVIEST node weight: a tail candidate then needs several paths to
                               # reach it and most sketch pieces end at their read sweep; resource allocation (weights up to 1 under a bar of 0.085
                               # on the ppa-like graph: one path through a light node passes) looks at nearly every piece again -- 10.3 vs 9.9 ms hashed
-SKETCH_WIDE = True            # ... and their head tables carry a plan whose packed pieces hold 8192 paths instead of 4096 (a sketch piece has
-                              # no keys to run out of slots for): 1.20 M -> 0.98 M pieces on the ppa-like graph, 7.25 -> 6.75 ms
 SKETCH_SET = 0                # slots of a sketch piece's set of reported ids (a power of two <= 64; 0 = the kernel's 128): tests shrink it
 LAZY_PLAN = True              # the whole-graph plan table (no skipped heads) is built when a launch first wants it; the bar sample plans itself
 BATCH_MIN_COLUMNS = 1 << 16   # lists shorter than this are handed out one column at a time throughout
@@ -195,9 +193,9 @@ def scan_graph(g: CSRGraph, build: bool = False):
     old id perm[i]); perm is None when the graph is scanned as it is.  The symmetric scheme gives column v the endpoints
     u < v, so the labelling decides how the half paths spread over the columns: as generated the ppa-like graph has columns
     of up to 3.7 M half paths (several rounds of row descriptors, several windows of tiles, buckets far beyond the L2);
-    hubs first no column has more than 64 k -- the same 8.35 G paths in uniform columns: 47.8 -> 44.8 ms per scan
-    (tools/scan_ab.py RELABEL=1).  Scores do not depend on the labels (order-independent fixed-point sums).
-    Relabelling sorts the stored entries once (9 ms for 42.5 M, tools/r03_cold_scan.py) and the one-pass kernel
+    hubs first no column has more than 64 k -- the same 8.35 G paths in uniform columns: 47.8 -> 44.8 ms per scan.
+    Scores do not depend on the labels (order-independent fixed-point sums).
+    Relabelling sorts the stored entries once (9 ms for 42.5 M, profiles/r03/cold_scan.txt) and the one-pass kernel
     (csrc/scan_pieces.hip) needs the even columns it gives, so even ONE scan repays it (first scan of a fresh ppa-like
     graph 57 ms as labelled, 46 ms relabelled with every table built; every later scan 52 vs 23 ms -- in a process whose
     allocator is cold the relabelled path's extra first-time hipMalloc costs ~30 ms more: profiles/r03/cold_scan.txt):
@@ -541,14 +539,12 @@ def column_records(g: CSRGraph, screen: Screen, columns: torch.Tensor, plan, hea
     return cache[key]
 
 
-COLUMN_PACK = True            # the main launch sets a column up from ONE stream of 32-byte records (ops.scan_column_pack) -- from a
-                              # graph's second scan on: 32 B per stored entry (1.4 GB on the ppa-like graph, 1.5 ms to build per head
-                              # table) is not what a one-shot filter.py run should pay
-
-
 def column_pack(g: CSRGraph, screen: Screen, ht: HeadTables) -> Optional[torch.Tensor]:
-    """The per-column pack of the head table's plan (cached on it), or None: not for a graph's first scan, not without row records."""
-    if not COLUMN_PACK or screen.rowrec is None or g._cache.get("scan_calls", 0) < 2:
+    """The per-column pack of the head table's plan (cached on it), or None: not for a graph's first scan, not without row records.
+    With it the main launch sets a column up from ONE stream of 32-byte records (ops.scan_column_pack); from a graph's second scan
+    on only, since 32 B per stored entry (1.4 GB on the ppa-like graph, 1.5 ms to build per head table) is not what a one-shot
+    filter.py run should pay."""
+    if screen.rowrec is None or g._cache.get("scan_calls", 0) < 2:
         return None
     if ht.pack is None:
         ht.pack = ops.scan_column_pack(g.rowptr, g.col, reverse_positions(g), screen.rowrec, ht.plan)
@@ -1334,7 +1330,7 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
             return bool(sketch and screen is not None and screen_variant(g) == 2 and not screen.exact
                         and (int(screen.w_max_units) + 2) * SKETCH_PIECE_PATHS < 1 << 32     # (no slot can wrap: screen_weights saw to it)
                         and budget >= HEAD_BETA * SKETCH_MIN_PATHS * screen.w_max_units)
-        ht = (_heads_for(g, screen, bar, lambda budget: sketch_for(budget) and SKETCH_WIDE) if use_heads and bar is not None else None)
+        ht = (_heads_for(g, screen, bar, sketch_for) if use_heads and bar is not None else None)
         want_sketch = ht is not None and sketch_for(ht.budget)
         walked_cap = max(1, min(int(head_list * capacity), ops.SURVIVOR_SLOTS_MAX)) if ht is not None else 0
         res = _launch(g, fixw, mine if ht is None else live_columns(g, screen, ht, rank, world), float("-inf") if bar is None else bar,
