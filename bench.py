@@ -2,8 +2,14 @@
 """Headline benchmark: candidate edges scored per second on a ppa-like graph (BASELINE.json configs[2]:
 "ogbl-ppa Adamic-Adar scoring of full non-edge candidate set, 1xMI355X").
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: it builds the graph and its per-graph tables, runs the W
+warm-up steps and the K timed steps, writes --dump-outputs, and prints the result line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, the configuration).  --full adds everything else described below: the roofline, the step
+breakdown, prep / cold / sustained / weak figures, the secondary legs and the CPU baseline (about a minute more on 1 GPU).
+The warm-up and timed steps are the same in both modes, so `value` and `ms_per_step` compare across them.
 
 --dump-outputs DIR writes the rows the last timed step returned (scan.scan_topk's pairs and scores) as DIR/pairs.npy and
 DIR/scores.npy; the graph is seeded, so two builds run with the same arguments can be compared output for output.
@@ -26,7 +32,7 @@ Workload (synthetic, seeded; no dataset / network exists on either box)
           one all-gather of the selected pairs are the collectives, and the final ordering is dealt over the ranks by score
           range -- the north-star target ("sharded candidate set").  "weak" (--scaling weak): every rank runs the full
           single-GPU workload on its own replica (per-GPU work fixed).
-Reported next to it: the roofline of the dominant kernel (scan_piece_kernel<256,false,true>; HIP events on its stream), what
+Reported next to it with --full: the roofline of the dominant kernel (scan_piece_kernel<256,false,true>; HIP events on its stream), what
 the step spends outside it (`serial_ms`; for N > 1 `replicated_ms`: everything that does not shrink with N), a sustained run
 of >= 5 s, secondary legs for the other hot-path kernels (pair intersection, SpMM, GEMM, decode) and one leg per BASELINE
 config (bench_configs.py) with their SURVEY 8(d) rooflines, and the reference's CPU path (SciPy mirror of adamic_utils.AA)
@@ -362,12 +368,16 @@ def parse_args(argv=None):
                     help="N > 1: 'strong' (default) shards the columns of ONE graph over the ranks; 'weak' = one replica of the "
                          "whole job per rank")
     ap.add_argument("--keep_top", type=int, default=KEEP_TOP)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary kernel legs")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the per-config end-to-end legs (bench_configs.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the headline: roofline, step "
+                         "breakdown, prep / cold / sustained / weak figures, secondary legs, CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary kernel legs")
+    ap.add_argument("--no-config-legs", action="store_true",
+                    help="with --full: skip the per-config end-to-end legs (bench_configs.py)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (tests on a 1-GPU box: gloo)")
     ap.add_argument("--one-device", action="store_true", help="every rank on cuda:0 (tests on a 1-GPU box, with --backend gloo)")
-    ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the extra sustained loop (0: skip)")
+    ap.add_argument("--sustain", type=float, default=5.0, help="with --full: seconds of the extra sustained loop (0: skip)")
     ap.add_argument("--nodes", type=int, default=576_289, help="graph size (tests use a small one)")
     ap.add_argument("--edges", type=int, default=21_231_931)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -507,6 +517,7 @@ def run(args):
     for _ in range(args.warmup):
         step()
     # the timed region: HIP events around the scan launches only (the dominant kernel: `roofline.kernel_ms`), on their stream.
+    # A plain run records them too and reads none of them: the timed steps are the same with and without --full.
     # The interpreter's cyclic collector is off inside the timed loops, as in `timeit`: a generation-2 pass of this process
     # (torch + the graph objects) stops the host for 30-45 ms, which lands in one step out of a hundred and moved the 100-step
     # average by 0.3-0.4 ms from run to run (tools/r05_loop_probe.py: median step 14.21 ms with and without it)
@@ -524,6 +535,78 @@ def run(args):
     dumped = None
     if args.dump_outputs and rank == 0:                         # (strong scaling: the rows are gathered on rank 0, rows_on=0)
         dumped = dump_outputs(args.dump_outputs, out["r"][0], out["r"][1], g.n_rows)
+    if world > 1:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = t.item()
+    n_cand = stats["candidates"]                   # directed candidates of the graph (kernel-counted)
+    job_cand = n_cand if strong or world == 1 else n_cand * world
+    bar = None if stats["bar"] is None else float(stats["bar"])
+    ms_step = dt / args.steps * 1e3
+
+    line = None
+    if rank == 0:
+        n_cu, dev_name = ops.device_info()
+        line = {
+            "metric": "candidate edges scored/sec on ogbl-ppa (ppa-like synthetic): Adamic-Adar over the FULL 2-hop non-edge "
+                      "candidate set + top-4M selection",
+            "value": job_cand * args.steps / dt,
+            "unit": "edges/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ranks": ranks_seen,
+            "distinct_devices": len({(r["device_index"], r["pci_bus_id"], r["uuid"]) for r in ranks_seen}),
+            "ms_per_step": ms_step,
+            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "dtype": "int64", "data": "synthetic",
+            "value_unordered_pairs_per_s": job_cand / 2 * args.steps / dt,
+            "full": args.full,
+            "dump_outputs": dumped,
+            "config": {"workload": "configs[2] ppa-like S3, full candidate set: N=%d, nnz=%d, %d directed 2-hop non-edge "
+                                   "candidates per graph, filter.py --model adamic_ogb --keep_top %d (scan.scan_topk)"
+                                   % (g.n_rows, g.nnz(), n_cand, args.keep_top),
+                       "candidates_per_step_all_ranks": job_cand, "two_hop_half_paths": half_paths_total,
+                       "arithmetic": "screening: u32 sums of weights rounded up to 2^-shift; reported scores: exact 2^-40 fixed-point "
+                                     "sums (float64 of multiples of 2^-40: order-independent), rounded to f32",
+                       "keep_top": args.keep_top, "bar": bar, "survivors": stats["survivors"],
+                       "launches_per_step": stats["launches"], "graph_replicated": True, "device": dev_name, "n_cu": n_cu,
+                       "notes": {"value": "DIRECTED candidates (both rows of the proposal file carry the score); each unordered "
+                                          "pair is computed once: value_unordered_pairs_per_s.  'Scored' means: every candidate's sum "
+                                          "over its common neighbours is accumulated -- SCREENED with >= upper bounds at 15 / 31 bits "
+                                          "(weights rounded up to 2^-shift) -- and the survivors that can reach the top-K get their "
+                                          "EXACT 2^-40 fixed-point score (eps_rescore_runs); r05: under the bar a column's heaviest hub "
+                                          "rows are not walked at all -- their weights (at most half the bar per column) enter every "
+                                          "pair of the column as a BOUND, and the slots that pass get the exact head term from the hub "
+                                          "row bitmaps (eps_scan_refine) -- so a candidate reached through hub rows only is bounded, "
+                                          "never touched (roofline.skipped_heads); r06: in the sparse tail of the id space a piece of a column keeps NO keys -- its paths add "
+                                          "into two hashed half tables and a candidate's sum is bounded by the smaller of its two slots (a count-min sketch: an "
+                                          "upper bound too; ids that reach the bar are reported from a second look at the paths and re-scored exactly); the K rows are identical to the exact "
+                                          "scan's (eps_filter_scan: tests, profiles/r03/two_kernels_same_list.txt).  The literal "
+                                          "filter.py:113-165 -- every candidate's exact score written out -- is the leg "
+                                          "full_list_every_candidate_scored (--full)",
+                                 "data": "synthetic stand-in (seeded R-MAT of ogbl-ppa's size): no dataset exists on the build or the GPU "
+                                         "box, so Hits@100 parity is shown on a held-out split of the stand-in (--full: cpu_baseline.hits_at_100) "
+                                         "and the published 53.24 (README.md:11-17) is reachable only through the $EPS_DATA_ROOT/ppa.pt "
+                                         "hook (--full: legs.real_ppa)",
+                                 "gc": "the interpreter's cyclic garbage collector is off inside the timed loop and, with --full, the sustained one (gc.collect() "
+                                       "before, re-enabled after), as `timeit` does: a generation-2 pass stops this process's host thread "
+                                       "for 30-45 ms, one step in a hundred or so (tools/r05_loop_probe.py)",
+                                 "full": "false: a plain run -- set-up, warm-up, the timed steps, --dump-outputs and this line; true: "
+                                         "--full, everything else the benchmark measures and checks measured after the timed steps"}},
+        }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        gc.enable()
+        finish()
+        return
+
+    # --full from here on: everything else the benchmark measures and checks, after the timed steps and with their outputs dumped
     # where the rest of a step goes (`step_breakdown_ms`, `sharded_ms_per_rank`): a second, short loop with events around EVERY
     # library call -- some forty event records per step, which cost the host 0.4 ms a step when they sat in the timed region
     bd_steps = max(1, min(args.steps, 20))
@@ -553,10 +636,6 @@ def run(args):
         sync()
         cold_ms = (time.perf_counter() - tc) * 1e3
         del g_cold, w_cold
-    if world > 1:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = t.item()
     half = g.n_rows // (2 * sworld)
     scans = [e for e in events if e[0] in ("scan_piece_kernel", "filter_scan_kernel")]
     kernel_name = sorted({name for name, a, b, ncol in scans if ncol > half})
@@ -574,9 +653,6 @@ def run(args):
     if world > 1:
         from eps_amd import dist as epd
         per_rank = torch.stack(epd.all_gather_list(torch.tensor([kern_ms, samp, sharded_ms], device=dev, dtype=torch.float64))).tolist()
-    n_cand = stats["candidates"]                   # directed candidates of the graph (kernel-counted)
-    job_cand = n_cand if strong or world == 1 else n_cand * world
-    bar = None if stats["bar"] is None else float(stats["bar"])
 
     # N > 1, strong: the weak figure (every rank the whole job on its own replica) as a secondary key, from a short loop
     weak_value = None
@@ -618,9 +694,7 @@ def run(args):
                      "sclk_mhz_mean": (sum(clk.samples) / len(clk.samples)) if clk.samples else None,
                      "sclk_mhz_min": min(clk.samples) if clk.samples else None, "sclk_samples": len(clk.samples)}
 
-    line = None
     if rank == 0:
-        n_cu, dev_name = ops.device_info()
         # dominant kernel: the scan's main launch (eps_scan_screen, or eps_filter_scan where the piece kernel does not apply).
         # Algorithmic bytes per launch: every two-hop half path read once (4 B), the per-(v,w) descriptors
         # (col 4 + revpos 4 + rowptr 8 + weight 8), rowptr of the columns, and the survivors (12 B each); the per-rank
@@ -654,22 +728,10 @@ def run(args):
             pmc = json.load(open(tpath)).get(f"{kernel_name}/ppa_like/{g.n_rows}") or {}
             if not isinstance(pmc, dict):
                 pmc = {"traffic": pmc}
-        ms_step = dt / args.steps * 1e3
-        line = {
-            "metric": "candidate edges scored/sec on ogbl-ppa (ppa-like synthetic): Adamic-Adar over the FULL 2-hop non-edge "
-                      "candidate set + top-4M selection",
-            "value": job_cand * args.steps / dt,
-            "unit": "edges/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ranks": ranks_seen,
-            "distinct_devices": len({(r["device_index"], r["pci_bus_id"], r["uuid"]) for r in ranks_seen}),
-            "ms_per_step": ms_step,
+        line.update({
             # (the two figures next to the steady-state step that the driver's stored tail used to cut off)
             "cold_ms_per_step": cold_ms,
             "sustained_ms_per_step": None if sustained is None else sustained["ms_per_step"],
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "int64", "data": "synthetic",
-            "value_unordered_pairs_per_s": job_cand / 2 * args.steps / dt,
             "weak_value": weak_value,
             "prep_ms": prep_ms,
             "kernel_ms_per_rank": [r[0] for r in per_rank], "sample_ms_per_rank": [r[1] for r in per_rank],
@@ -678,53 +740,6 @@ def run(args):
             "replicated_ms": ms_step - max(r[2] for r in per_rank),
             "step_breakdown_ms": per_step,
             "sustained": sustained,
-            "dump_outputs": dumped,
-            "config": {"workload": "configs[2] ppa-like S3, full candidate set: N=%d, nnz=%d, %d directed 2-hop non-edge "
-                                   "candidates per graph, filter.py --model adamic_ogb --keep_top %d (scan.scan_topk)"
-                                   % (g.n_rows, g.nnz(), n_cand, args.keep_top),
-                       "candidates_per_step_all_ranks": job_cand, "two_hop_half_paths": half_paths_total,
-                       "arithmetic": "screening: u32 sums of weights rounded up to 2^-shift; reported scores: exact 2^-40 fixed-point "
-                                     "sums (float64 of multiples of 2^-40: order-independent), rounded to f32",
-                       "keep_top": args.keep_top, "bar": bar, "survivors": stats["survivors"],
-                       "launches_per_step": stats["launches"], "graph_replicated": True, "device": dev_name, "n_cu": n_cu,
-                       "notes": {"value": "DIRECTED candidates (both rows of the proposal file carry the score); each unordered "
-                                          "pair is computed once: value_unordered_pairs_per_s.  'Scored' means: every candidate's sum "
-                                          "over its common neighbours is accumulated -- SCREENED with >= upper bounds at 15 / 31 bits "
-                                          "(weights rounded up to 2^-shift) -- and the survivors that can reach the top-K get their "
-                                          "EXACT 2^-40 fixed-point score (eps_rescore_runs); r05: under the bar a column's heaviest hub "
-                                          "rows are not walked at all -- their weights (at most half the bar per column) enter every "
-                                          "pair of the column as a BOUND, and the slots that pass get the exact head term from the hub "
-                                          "row bitmaps (eps_scan_refine) -- so a candidate reached through hub rows only is bounded, "
-                                          "never touched (roofline.skipped_heads); r06: in the sparse tail of the id space a piece of a column keeps NO keys -- its paths add "
-                                          "into two hashed half tables and a candidate's sum is bounded by the smaller of its two slots (a count-min sketch: an "
-                                          "upper bound too; ids that reach the bar are reported from a second look at the paths and re-scored exactly); the K rows are identical to the exact "
-                                          "scan's (eps_filter_scan: tests, profiles/r03/two_kernels_same_list.txt).  The literal "
-                                          "filter.py:113-165 -- every candidate's exact score written out -- is the leg "
-                                          "full_list_every_candidate_scored",
-                                 "data": "synthetic stand-in (seeded R-MAT of ogbl-ppa's size): no dataset exists on the build or the GPU "
-                                         "box, so Hits@100 parity is shown on a held-out split of the stand-in (cpu_baseline.hits_at_100) "
-                                         "and the published 53.24 (README.md:11-17) is reachable only through the $EPS_DATA_ROOT/ppa.pt "
-                                         "hook (legs.real_ppa)",
-                                 "replicated_ms": "ms_per_step minus the slowest rank's sharded work (both scan launches, its local "
-                                                  "selects, the sort and exact re-scoring of its survivors -- HIP events, step_breakdown_ms, taken in a "
-                                                  "second loop of <= 20 steps right after the timed region, which itself carries events around "
-                                                  "the scan launches only): "
-                                                  "collectives, host reads, the gathered selection and this rank's range of the final "
-                                                  "ordering -- what does not shrink with N",
-                                 "gc": "the interpreter's cyclic garbage collector is off inside the timed and the sustained loop (gc.collect() "
-                                       "before, re-enabled after), as `timeit` does: a generation-2 pass stops this process's host thread "
-                                       "for 30-45 ms, one step in a hundred or so (tools/r05_loop_probe.py)",
-                                 "sustained": "the same step repeated for >= --sustain seconds after the timed region; sclk from rocm-smi "
-                                              "samples taken by a child process during the loop (null when the tool is unavailable)",
-                                 "prep_ms": "hubs-first relabelled copy + revpos / half paths / column order / fixed-point "
-                                            "weights / window tables / sum bounds / plan table / sample, built once per graph, "
-                                            "OUTSIDE the timed region (timed on a fresh graph object after the loop: allocator warm)",
-                                 "cold_ms_per_step": "first scan of a FRESH graph object incl. relabelling and every per-graph table, "
-                                                     "measured after the timed loop (code objects loaded, allocator warm); a "
-                                                     "one-shot filter.py process pays its first-time hipMalloc and code-object "
-                                                     "loads on top: profiles/r03/cold_scan.txt",
-                                 "serial_ms": "ms_per_step - slowest rank's main kernel - its sample launch: bar, selection, "
-                                              "collectives, host"}},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "hbm_frac": achieved / HBM_PEAK_GBPS, "traffic": pmc.get("traffic"),
                          "binds": pmc.get("binds"),
@@ -745,7 +760,25 @@ def run(args):
                                  "two-hop half path + 24 B per stored entry + survivors; `traffic` = fabric bytes per launch "
                                  "(2 x FETCH_SIZE + WRITE_SIZE) and `issue` = VALU / LDS occupancy of the same launch, from the "
                                  "rocprofv3 PMC passes committed under profiles/ (profiles/traffic.json)"},
-        }
+        })
+        line["config"]["notes"].update({
+            "replicated_ms": "ms_per_step minus the slowest rank's sharded work (both scan launches, its local "
+                             "selects, the sort and exact re-scoring of its survivors -- HIP events, step_breakdown_ms, taken in a "
+                             "second loop of <= 20 steps right after the timed region, which itself carries events around "
+                             "the scan launches only): "
+                             "collectives, host reads, the gathered selection and this rank's range of the final "
+                             "ordering -- what does not shrink with N",
+            "sustained": "the same step repeated for >= --sustain seconds after the timed region; sclk: shader-clock "
+                         "samples a child process takes during the loop (_ClockSampler; null when none could be read)",
+            "prep_ms": "hubs-first relabelled copy + revpos / half paths / column order / fixed-point "
+                       "weights / window tables / sum bounds / plan table / sample, built once per graph, "
+                       "OUTSIDE the timed region (timed on a fresh graph object after the loop: allocator warm)",
+            "cold_ms_per_step": "first scan of a FRESH graph object incl. relabelling and every per-graph table, "
+                                "measured after the timed loop (code objects loaded, allocator warm); a "
+                                "one-shot filter.py process pays its first-time hipMalloc and code-object "
+                                "loads on top: profiles/r03/cold_scan.txt",
+            "serial_ms": "ms_per_step - slowest rank's main kernel - its sample launch: bar, selection, "
+                         "collectives, host"})
     if rank == 0 and world == 1 and not args.no_legs:
         line["legs"] = {"pair_intersection": leg_pair_kernel(torch, g, w, ops, candidates)}
         line["legs"].update(leg_gnn(torch, g, ops))
@@ -757,11 +790,7 @@ def run(args):
         line["cpu_baseline"] = cpu_baseline(torch, g, w, ops, candidates, out["r"][0], out["r"][1])
         line["cpu_baseline"]["gpu_over_cpu_1core"] = line["value"] / line["cpu_baseline"]["value"]
         line["cpu_baseline"]["gpu_over_cpu_all_cores"] = line["value"] / line["cpu_baseline"]["all_cores"]["value"]
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -18,6 +18,11 @@ def test_steps_and_warmup_are_validated():
     assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+
+
 def test_dump_writes_what_the_step_returns(tmp_path):
     gen = torch.Generator().manual_seed(0)
     pairs = torch.randint(0, 1000, (2, 500), generator=gen, dtype=torch.int64)

@@ -114,8 +114,8 @@ def test_bench_two_ranks_child_process(dev, tmp_path, scaling):
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--scaling", scaling, "--nodes", "30000", "--edges", "600000", "--keep_top", "20000", "--no-cpu", "--no-legs",
-           "--backend", "gloo", "--one-device", "--sustain", "0.3"]
+           "--scaling", scaling, "--nodes", "30000", "--edges", "600000", "--keep_top", "20000", "--full", "--no-cpu",
+           "--no-legs", "--backend", "gloo", "--one-device", "--sustain", "0.3"]
     out = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -138,13 +138,40 @@ def test_bench_self_launch_from_plain_shell(dev, tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--nodes", "30000",
-           "--edges", "600000", "--keep_top", "20000", "--no-cpu", "--no-legs", "--backend", "gloo", "--one-device", "--sustain", "0.3"]
+           "--edges", "600000", "--keep_top", "20000", "--full", "--no-cpu", "--no-legs", "--backend", "gloo", "--one-device",
+           "--sustain", "0.3"]
     out = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0 and line["weak_value"] > 0
     assert len(line["kernel_ms_per_rank"]) == 2 and "serial_ms" in line and "prep_ms" in line
     assert 0 < line["roofline"]["frac"] <= 1 and line["value_unordered_pairs_per_s"] * 2 == pytest.approx(line["value"])
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_the_headline_alone(dev, tmp_path, gpus):
+    """Without --full the bench times its steps, writes --dump-outputs and prints the headline line, and measures nothing
+    else: no roofline, breakdown, prep / cold / sustained / weak figure, leg or CPU baseline."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--nodes",
+           "30000", "--edges", "600000", "--keep_top", "20000", "--backend", "gloo", "--one-device", "--dump-outputs", "out"]
+    out = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in line
+    assert line["full"] is False and line["n_gpus"] == gpus and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(line["config"]["candidates_per_step_all_ranks"] / line["ms_per_step"] * 1e3)
+    for key in ("roofline", "step_breakdown_ms", "prep_ms", "cold_ms_per_step", "sustained", "weak_value", "legs", "cpu_baseline"):
+        assert key not in line
+    pairs, scores = np.load(tmp_path / "out" / "pairs.npy"), np.load(tmp_path / "out" / "scores.npy")
+    assert pairs.shape == (2, 20000) and scores.shape == (20000,) and line["dump_outputs"]["rows"] == 20000
+    assert bool((scores[:-1] >= scores[1:]).all())
 
 
 def _relabelled_scan_rank_main(rank, world, port, workdir, dist_rows_min=0, rows_on=None, kind="aa", k=30000, dist_hist=True,
