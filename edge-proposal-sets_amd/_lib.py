@@ -32,6 +32,7 @@ SIGNATURES = {
     "eps_expand_count": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "eps_expand_fill": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "eps_expand_fill_tiled": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "eps_expand_fill_signed": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "eps_expand_workspace_bytes": (_i64, [_i64]),
     "eps_filter_scan_max_nodes": (_i64, []),
     "eps_filter_scan_workspace_bytes": (_i64, [_i64]),
@@ -113,6 +114,8 @@ SIGNATURES = {
     "eps_katz_workspace_bytes": (_i64, [_i64]),
     "eps_katz_pair_scores": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_double, _c.c_double,
                                     _c.c_double, _vp, _vp, _vp]),
+    "eps_cos_node_features": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "eps_edge_cosines": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

@@ -189,16 +189,18 @@ def _unit_expand(g: CSRGraph, v_lo: int, v_hi: int, node_w, want_score: bool, wa
 
 
 def expand_block_lazy(g: CSRGraph, v_lo: int, v_hi: int, node_w: Optional[torch.Tensor] = None, want_cn: bool = False,
-                      want_score: bool = False, count_free: bool = False, cut=None) -> ColumnBlock:
+                      want_score: bool = False, count_free: bool = False, cut=None, signed: bool = False) -> ColumnBlock:
     """``expand_block`` for consumers that read the pairs of a few candidates only (HIP expansion required).
     ``count_free``: lay the columns out by the upper bound ``segment_bounds`` instead of running the counting pass (one
     walk over the two-hop paths and a host synchronisation less; the arrays are then padded).  Measured on the ppa-like
     graphs: the expansion itself gets 9 % faster, but every later pass over the block (top-K cut) reads paths/candidates
     = 1.3x to 2.8x more entries, which costs as much or more -- so the filter stage keeps the counted layout.
     ``cut=(threshold, capacity)``: let the kernel report the candidates above the streaming top-K's bar (see
-    ``ops.expand_candidates``); with ``want_score=False`` the block then has no score array at all."""
+    ``ops.expand_candidates``); with ``want_score=False`` the block then has no score array at all.
+    ``signed``: the graph's values may be negative (the cosine graph): eps_expand_fill_signed, range checked by the caller
+    (``fused_scores_fit``)."""
     from . import ops
-    if not want_cn and not count_free and cut is None:
+    if not want_cn and not count_free and cut is None and not signed:
         r = _unit_expand(g, v_lo, v_hi, node_w, want_score, want_v=False)
         if r is not None:
             return ColumnBlock(v_lo, r[0], r[1], None, r[4])
@@ -208,7 +210,7 @@ def expand_block_lazy(g: CSRGraph, v_lo: int, v_hi: int, node_w: Optional[torch.
         kw = dict(colptr_ub=(pre[v_lo:v_hi + 1] - pre[v_lo]).contiguous(), total_ub=int(pre_host[v_hi] - pre_host[v_lo]))
     r = ops.expand_candidates(g.rowptr, g.col, g.val, node_w, g.n_rows, v_lo, v_hi, want_cn=want_cn,
                               want_score=want_score, want_v=False, col_order=heaviest_first(g, v_lo, v_hi),
-                              max_paths=max_paths_of(g), cut=cut, **kw)
+                              max_paths=max_paths_of(g), cut=cut, signed=signed, **kw)
     return ColumnBlock(v_lo, r[0], r[1], r[3], r[4], counts=r.counts, survivors=r.survivors)
 
 

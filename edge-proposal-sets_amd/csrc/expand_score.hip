@@ -197,7 +197,10 @@ __device__ __forceinline__ void for_each_path(const int64_t *__restrict__ rowptr
 }
 
 
-template <bool FILL, bool HAS_VAL, bool HAS_W, bool WINDOWED>
+// SIGNED: the terms may be negative (cosine-weighted common neighbours): the sums are still exact -- two's complement
+// addition is associative -- but a negative sum is no longer a sign of overflow, so the backstop below is dropped and the
+// range guarantee is the host's bound alone (candidates.fused_score_bound sums |terms|).
+template <bool FILL, bool HAS_VAL, bool HAS_W, bool WINDOWED, bool SIGNED = false>
 __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const float *__restrict__ node_w, int32_t n_nodes, int32_t v_lo, int32_t v_hi, const int32_t *__restrict__ col_order,
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
                     if (want_sum) {
                         // the heuristics' terms are non-negative: a negative sum is one that wrapped past 2^23 (backstop; the
                         // host checks a bound of the graph's scores before it takes this path -- candidates.fused_scores_fit)
-                        if ((long long)acc[i] < 0 && overflow) atomicOr(overflow, 4u);
+                        if (!SIGNED && (long long)acc[i] < 0 && overflow) atomicOr(overflow, 4u);
                         const float sc = (float)((double)(long long)acc[i] * (1.0 / (double)(1ll << EX_FIXED_SHIFT)));
                         if (out_score) out_score[wbase + r0 + i] = sc;
                         if (cut && sc > cut_thr) {      // top-K cut in the kernel: report the few candidates above the bar
@@ -579,11 +582,12 @@ extern "C" int eps_expand_fill(const int64_t *rowptr, const int32_t *col, const 
                                  cand_v, cn, score, cut, workspace, workspace_bytes, 0, stream);
 }
 
-extern "C" int eps_expand_fill_tiled(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w,
-                                     int64_t n_nodes, int64_t v_lo, int64_t v_hi, const int32_t *col_order,
-                                     const int64_t *colptr, int64_t *cand_count, int32_t *cand_u, int32_t *cand_v,
-                                     int32_t *cn, float *score, eps_score_cut *cut, void *workspace,
-                                     int64_t workspace_bytes, int32_t tile_ranks, void *stream)
+template <bool SIGNED>
+static int expand_fill_launch(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w,
+                              int64_t n_nodes, int64_t v_lo, int64_t v_hi, const int32_t *col_order,
+                              const int64_t *colptr, int64_t *cand_count, int32_t *cand_u, int32_t *cand_v,
+                              int32_t *cn, float *score, eps_score_cut *cut, void *workspace,
+                              int64_t workspace_bytes, int32_t tile_ranks, void *stream)
 {
     EPS_REQUIRE(n_nodes >= 0 && v_lo >= 0 && v_hi >= v_lo && v_hi <= n_nodes, "eps_expand_fill: bad column range");
     if (v_hi == v_lo) return EPS_OK;
@@ -618,7 +622,7 @@ extern "C" int eps_expand_fill_tiled(const int64_t *rowptr, const int32_t *col, 
     const bool hv = val != nullptr, hw = node_w != nullptr;
 #define EX_LAUNCH(HV, HW, W)                                                                                           \
     do {                                                                                                               \
-        auto kern = expand_kernel<true, HV, HW, W>;                                                                    \
+        auto kern = expand_kernel<true, HV, HW, W, SIGNED>;                                                                    \
         if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=           \
             hipSuccess) {                                                                                              \
             eps_set_error("eps_expand_fill: cannot reserve %zu bytes of LDS", lds);                                    \
@@ -644,6 +648,26 @@ extern "C" int eps_expand_fill_tiled(const int64_t *rowptr, const int32_t *col, 
 #undef EX_LAUNCH
     EPS_CHECK_LAUNCH("eps_expand_fill");
     return EPS_OK;
+}
+
+extern "C" int eps_expand_fill_tiled(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w,
+                                     int64_t n_nodes, int64_t v_lo, int64_t v_hi, const int32_t *col_order,
+                                     const int64_t *colptr, int64_t *cand_count, int32_t *cand_u, int32_t *cand_v,
+                                     int32_t *cn, float *score, eps_score_cut *cut, void *workspace,
+                                     int64_t workspace_bytes, int32_t tile_ranks, void *stream)
+{
+    return expand_fill_launch<false>(rowptr, col, val, node_w, n_nodes, v_lo, v_hi, col_order, colptr, cand_count, cand_u,
+                                     cand_v, cn, score, cut, workspace, workspace_bytes, tile_ranks, stream);
+}
+
+extern "C" int eps_expand_fill_signed(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w,
+                                      int64_t n_nodes, int64_t v_lo, int64_t v_hi, const int32_t *col_order,
+                                      const int64_t *colptr, int64_t *cand_count, int32_t *cand_u, int32_t *cand_v,
+                                      int32_t *cn, float *score, eps_score_cut *cut, void *workspace,
+                                      int64_t workspace_bytes, int32_t tile_ranks, void *stream)
+{
+    return expand_fill_launch<true>(rowptr, col, val, node_w, n_nodes, v_lo, v_hi, col_order, colptr, cand_count, cand_u,
+                                    cand_v, cn, score, cut, workspace, workspace_bytes, tile_ranks, stream);
 }
 
 // (one empty kernel per translation unit: launching it makes the HIP runtime load this unit's code object -- eps_warm_up)

@@ -22,7 +22,7 @@ import torch
 from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
-from .heuristics import node_weight_table, pair_scores_streamed
+from .heuristics import cosine_graph, node_weight_table, pair_scores_streamed, sigmoid_raw_cut
 from .models import build_model, default_model_configs
 
 
@@ -169,13 +169,70 @@ def _sum_over_ranks(x: int) -> int:
 CUT_CAPACITY = 1 << 23     # survivors per block the expansion kernel may report (96 MB); more -> the block is redone in full
 
 
+COSINE_MODELS = ('simplecos', 'mlpcos')
+COSINE_FUSED = True        # cosine filters: fused signed expansion (False: candidate lists + the pair kernel, for comparisons)
+LAST_COSINE_CUTS = []      # the last fused cosine run, per column block: (v_lo, v_hi, raw threshold or None, "scored" / "cut" / "skipped")
+
+
+def cosine_blocks(args, model, data, blocks, bar=None, fused: bool = True):
+    """``scored_blocks`` of the cosine filters (models.py:556-575): candidates of the graph as it is, scores
+    sigmoid(sum_w c[u,w] * c[v,w]) with c the stored cosines of ``heuristics.cosine_graph``.  The fused expansion walks
+    the cosine graph (same pattern, so the same candidates in the same order) with node_w = 1 through the SIGNED entry
+    point -- cosines may be negative, which is why these filters skip the threshold scan, whose screen bounds sums from
+    above.  The kernel's cut compares raw sums, so the streaming top-K's bar is translated first
+    (``heuristics.sigmoid_raw_cut``: conservative, +inf once the bar has saturated at 1.0).  ``fused=False``, or sums
+    whose bound leaves the fixed-point range: candidate lists + the pair kernel (the model's own forward)."""
+    g = data.adj_t
+    LAST_COSINE_CUTS.clear()
+    gc = cosine_graph(g, model.cosine_input(data.x))
+    ones = torch.ones(g.n_rows, dtype=torch.float32, device=g.device)
+    if fused and not (candidates.hip_expand_available(gc) and candidates.fused_scores_fit(gc, ones)):
+        print(f'fused scoring disabled: score bound {candidates.fused_score_bound(gc, ones):.3e} >= 2^22')
+        fused = False
+    if not fused:
+        for v_lo, v_hi in blocks:
+            pairs = candidates.expand_block(g, v_lo, v_hi)[0]
+            yield v_lo, v_hi, pairs, (score_block(args, model, data, pairs) if pairs.shape[1] else None)
+        return
+    print(f'fused candidate generation + signed scoring ({args.model})')
+    for v_lo, v_hi in blocks:
+        thr = bar() if bar is not None else None
+        raw_thr = None if thr is None else sigmoid_raw_cut(thr)
+        if raw_thr == float("inf"):
+            # the K-th score is 1.0f and no float32 sigmoid exceeds it: no later candidate can enter the top-K (an equal
+            # score of a later candidate never displaces an earlier one), so the remaining columns are not expanded
+            LAST_COSINE_CUTS.append((v_lo, blocks[-1][1], raw_thr, "skipped"))
+            print(f'bar saturated at 1.0: columns [{v_lo}, {blocks[-1][1]}) skipped')
+            return
+        blk = None
+        if raw_thr is not None:
+            blk = candidates.expand_block_lazy(gc, v_lo, v_hi, ones, want_score=False, cut=(raw_thr, CUT_CAPACITY),
+                                               count_free=True, signed=True)
+            if blk.survivors is None:
+                blk = None
+            else:
+                pos, raw = blk.survivors
+                blk.survivors = (pos, torch.sigmoid(raw))
+        if blk is None:
+            blk = candidates.expand_block_lazy(gc, v_lo, v_hi, ones, want_score=True, signed=True)
+            blk.score = torch.sigmoid(blk.score)
+            LAST_COSINE_CUTS.append((v_lo, v_hi, raw_thr, "scored"))
+        else:
+            LAST_COSINE_CUTS.append((v_lo, v_hi, raw_thr, "cut"))
+        yield v_lo, v_hi, blk, blk.score
+
+
 def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = None, bar=None):
     """(v_lo, v_hi, pairs, scores) per column block.  Heuristic filters whose scoring graph IS the candidate graph
     (AA: filter.py:122-126; CN 'simple': :116-121 with models.py:536-542) come out of the fused expansion already
-    scored; RA scores on the train-only graph (filter.py:130-141) and GNN filters decode the block's pairs."""
+    scored; RA scores on the train-only graph (filter.py:130-141) and GNN filters decode the block's pairs; the cosine
+    filters score the cosine graph (``cosine_blocks``)."""
     g = data.adj_t
     col_hi = g.n_rows if col_hi is None else col_hi
     blocks = [(max(lo, col_lo), min(hi, col_hi)) for lo, hi in candidates.column_blocks(g) if lo < col_hi and hi > col_lo]
+    if args.model in COSINE_MODELS:
+        yield from cosine_blocks(args, model, data, blocks, bar, fused=COSINE_FUSED and candidates.hip_expand_available(g))
+        return
     node_w = fused_node_weights(args, g, ra_graph) if candidates.hip_expand_available(g) else None
     if node_w is not None and not candidates.fused_scores_fit(g, node_w):
         # weights so large that a score could leave the fused kernels' fixed-point range: float32 / float64 pair kernels
@@ -283,7 +340,7 @@ def run(args) -> str:
             print('dense common-neighbour product (A A^T on the f32 MFMA)')
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    if 0 < keep <= scan.MAX_K and scan.scan_plausible(data.adj_t):
+    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS and scan.scan_plausible(data.adj_t):
         # (the hubs-first copy first: the symmetry check of scan_available then reads the COPY's reverse positions -- the table
         #  the scan needs anyway -- instead of building one for the graph as labelled, 3-5 ms on a ppa-sized graph)
         scan.scan_graph(data.adj_t, build=True)

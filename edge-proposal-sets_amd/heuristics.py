@@ -8,6 +8,7 @@ types:
 * ``resource_allocation(adj_matrix, link_list, batch_size=32768)``  <- train_and_eval.py:195-216
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
+* ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
 
 Where the reference loops over 2000-pair batches on one CPU thread through SciPy, these upload
 the pair list once, run ``eps_pair_scores`` (csrc/pair_intersect.hip) over all of it and hand
@@ -144,6 +145,73 @@ def common_neighbors(adj: CSRGraph, edges: torch.Tensor) -> torch.Tensor:
     u, v = _as_pairs(edges, g.device, g.n_rows)
     _, cn, _ = pair_scores_streamed(g, u, v, None, want_cn=True)
     return cn
+
+
+# ------------------------------------------------------------------------------------------- cosine common neighbours
+def cosine_graph(adj: CSRGraph, x: torch.Tensor) -> CSRGraph:
+    """The graph whose value at stored entry (u, w) is cos(x'_u, x'_w), x' = x + (adj @ x) / (rowsum(adj) + 1e-6)
+    (models.py:556-562; adj's values are used in the smoothing, collab is weighted).  The reference forms two
+    F.cosine_similarity per (pair, common neighbour) (:566-569); both depend on one stored entry only, so they are computed
+    once per entry here: eps_cos_node_features (normalised x', the per-vector clamp of F.cosine_similarity) and
+    eps_edge_cosines (one dot per entry; each undirected entry once on a symmetric pattern).  Shares adj's rowptr / col.
+    Cached on adj, keyed on the feature tensor itself and its version: train and test graphs (adj_t / full_adj_t) each
+    hold their own."""
+    g = _as_graph(adj)
+    if x is None or x.dim() != 2 or x.shape[0] != g.n_rows:
+        raise EpsError(f"cosine_graph: node features must be [{g.n_rows}, F], got "
+                       f"{None if x is None else tuple(x.shape)}")
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"cosine_graph needs a square adjacency, got {g.sparse_sizes()}")
+
+    def build() -> CSRGraph:
+        from . import scan
+        xin = x.detach().to(device=g.device, dtype=torch.float32)
+        if xin.stride(-1) != 1 or xin.stride(0) % 4 or xin.data_ptr() % 16:
+            # rows gathered whole as float4 (ppa's 58 features are 232-byte rows): copy into 128-byte aligned rows first
+            f = xin.shape[1]
+            buf = torch.zeros((xin.shape[0], (f + ops.COS_ROW_FLOATS - 1) // ops.COS_ROW_FLOATS * ops.COS_ROW_FLOATS),
+                              dtype=torch.float32, device=g.device)
+            buf[:, :f] = xin
+            xin = buf[:, :f]
+        xhat = ops.cos_node_features(g.rowptr, g.col, g.val, xin)
+        revpos = None
+        if g.nnz() and g.nnz() < 1 << 31:
+            rev = scan.reverse_positions(g)                     # (cached per graph; the filter scan shares the table)
+            revpos = rev if scan.is_symmetric(g) else None
+        c = ops.edge_cosines(g.rowptr, g.col, xhat, revpos)
+        return CSRGraph(g.rowptr, g.col, c, g.n_rows, g.n_cols)
+
+    return g.weight_cached("cosine_graph", x, build)
+
+
+def cosine_common_neighbors(adj: CSRGraph, x: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+    """sigmoid(sum_{w in N(u) & N(v)} cos(x'_u, x'_w) * cos(x'_v, x'_w)) per pair (models.py:556-575): the edge-valued
+    common-neighbour sum of ``cosine_graph`` (eps_pair_scores), then torch.sigmoid; pairs without a common neighbour
+    score 0.5.  float32 [E] on the adjacency's device."""
+    g = _as_graph(adj)
+    u, v = _as_pairs(edges, g.device, g.n_rows)
+    cg = cosine_graph(g, x)
+    _, cn, _ = pair_scores_streamed(cg, u, v, None, want_cn=True)
+    return torch.sigmoid(cn)
+
+
+def sigmoid_raw_cut(bar: float) -> float:
+    """A raw threshold t for a bar on sigmoid scores: every float32 raw sum r whose torch.sigmoid(r) exceeds ``bar`` has
+    r > t (conservative: candidates at or a little below the bar may pass too, none above it is cut).  The fused kernels
+    compare raw sums; the cosine filters' scores are sigmoid(raw).  float32 sigmoid never exceeds 1.0, so a bar that has
+    saturated at 1.0 admits nothing (+inf).  Otherwise the bar is lowered by 4 x 2^-24 (four ulps of the float32 scores
+    near 1; more than the rounding of any sigmoid implementation) before the exact float64 logit, and the result is
+    rounded down to float32."""
+    b = float(bar)
+    if not b < 1.0:
+        return float("inf")
+    lo = b - 4.0 * 2.0 ** -24
+    if lo <= 0.0:
+        return float("-inf")
+    t = np.float32(np.log(lo) - np.log1p(-lo))
+    if float(t) > np.log(lo) - np.log1p(-lo):
+        t = np.nextafter(t, np.float32(-np.inf))
+    return float(t)
 
 
 # ----------------------------------------------------------------------------------------------------------- Katz

@@ -317,22 +317,67 @@ class LinkGNN(torch.nn.Module):
         return self.linkpred.decode(h, edges).unsqueeze(1)
 
 
+class MLP(torch.nn.Module):
+    """models.py:136-163 (the layers and state-dict keys ``lins.*``).  Only 'mlpcos' constructs it, and -- like the
+    reference, whose call is commented out (models.py:564) -- never applies it: it exists so that a reference checkpoint
+    (``mlp.lins.*``, ``emb.weight``) loads."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout):
+        super().__init__()
+        self.lins = torch.nn.ModuleList()
+        self.lins.append(torch.nn.Linear(in_channels, hidden_channels))
+        for _ in range(num_layers - 2):
+            self.lins.append(torch.nn.Linear(hidden_channels, hidden_channels))
+        self.lins.append(torch.nn.Linear(hidden_channels, out_channels))
+        self.dropout = dropout
+
+    def reset_parameters(self):
+        for lin in self.lins:
+            lin.reset_parameters()
+
+
+_COSINE = ('mlpcos', 'simplecos')
+
+
 class CommonNeighborsPredictor(torch.nn.Module):
     """models.py:508-575.  'simple' (CN) and 'adamic' run on eps_pair_scores; 'adamic_ogb',
     'resource_allocation', 'katz' return None exactly like the reference (those heuristics are evaluated by
-    AA()/resource_allocation(), not by the module).  The cosine variants ('mlpcos', 'simplecos') are not
-    part of the accelerated path."""
+    AA()/resource_allocation(), not by the module).  The cosine variants ('mlpcos', 'simplecos') score the edge-valued
+    common-neighbour sum of the cosine graph (heuristics.cosine_common_neighbors: csrc/cosine_cn.hip + eps_pair_scores);
+    inference only -- their forward does not build an autograd graph."""
 
     def __init__(self, emb, in_channels, hidden_channels, out_channels, num_layers, dropout, model_type='weighted'):
         super().__init__()
         assert model_type in ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz']
         self.type = model_type
-        self.mlp = torch.nn.Identity()
+        if self.type == 'mlpcos':
+            self.mlp = MLP(in_channels, hidden_channels, out_channels, num_layers, dropout)
+        else:
+            self.mlp = torch.nn.Identity()
         self.emb = emb
+        self._x_key = self._x_src = self._x = None
 
     def reset_parameters(self):
+        if self.type == 'mlpcos':
+            self.mlp.reset_parameters()
         if self.emb is not None:
             self.emb.reset_parameters()
+
+    @torch.no_grad()
+    def cosine_input(self, x: Optional[torch.Tensor]) -> torch.Tensor:
+        """The node features the cosine variants smooth (models.py:529-532): emb.weight when x is None, else
+        [emb.weight || x] with an embedding, else x.  The concatenation is kept per (embedding version, x), so the cosine
+        graph cached on the adjacency (keyed on this tensor) serves every scoring batch."""
+        if x is None and self.emb is None:
+            raise ValueError(f"CommonNeighborsPredictor('{self.type}') needs node features or a learnable embedding")
+        if self.emb is None:
+            return x
+        w = self.emb.weight
+        key = (w.data_ptr(), w._version, None if x is None else x._version)
+        if key != self._x_key or self._x_src is not x:     # (x itself is held: an address can be recycled)
+            self._x = w.detach() if x is None else torch.cat([w.detach(), x], dim=1)
+            self._x_key, self._x_src = key, x
+        return self._x
 
     @torch.no_grad()
     def forward(self, x, edges, adj):
@@ -352,7 +397,8 @@ class CommonNeighborsPredictor(torch.nn.Module):
             _, _, ws = ops.pair_scores(g.rowptr, g.col, None, adj._cache[key], g.n_rows, e[0].contiguous(),
                                        e[1].contiguous(), want_count=False, want_cn=False)
             return torch.sigmoid(ws)
-        raise NotImplementedError(f"CommonNeighborsPredictor('{self.type}') is outside the accelerated path")
+        # 'simplecos' / 'mlpcos' (models.py:556-575; self.mlp stays unused, :564)
+        return heuristics.cosine_common_neighbors(adj, self.cosine_input(x), edges)
 
 
 # ----------------------------------------------------------------------------------- factory
@@ -365,6 +411,14 @@ _HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', 
 def build_model(args, data, device):
     """models.py:578-670 for the models on the accelerated path (gcn, sage, heuristics)."""
     assert args.model in _MODELS
+    if args.model in _COSINE:
+        # the reference would fail inside its forward (emb.weight of None, models.py:529-532): say why here
+        if args.use_feature and data.x is None:
+            raise ValueError(f"--model {args.model} --use_feature: the dataset carries no node features "
+                             "(ddi has none; collab and ppa do)")
+        if not args.use_feature and not args.use_learnable_embedding:
+            raise ValueError(f"--model {args.model} needs node features: pass --use_feature True (on a dataset that has "
+                             "them) or --use_learnable_embedding True")
     emb = None
     if args.use_learnable_embedding:
         emb = torch.nn.Embedding(data.num_nodes, args.hidden_channels).to(device)

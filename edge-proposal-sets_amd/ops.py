@@ -331,7 +331,8 @@ def expand_unit(rowptr, col, node_w, n_nodes: int, v_lo: int, v_hi: int, max_deg
 
 
 def expand_candidates(rowptr, col, val, node_w, n_nodes: int, v_lo: int, v_hi: int, want_cn=True, want_score=True,
-                      want_v=True, col_order=None, max_paths=None, colptr_ub=None, total_ub=None, cut=None, tile_ranks=0):
+                      want_v=True, col_order=None, max_paths=None, colptr_ub=None, total_ub=None, cut=None, tile_ranks=0,
+                      signed=False):
     """Fused 2-hop expansion of columns [v_lo, v_hi) of a SYMMETRIC adjacency (filter.py:96-109 + scoring).
     -> (colptr int64[n_cols+1], cand_u int32[E], cand_v int32[E] | None, cn int32[E] | None, score float32[E] | None);
     candidates are column-major, u ascending inside a column (the reference's order).  ``col_order`` (int32
@@ -348,7 +349,10 @@ def expand_candidates(rowptr, col, val, node_w, n_nodes: int, v_lo: int, v_hi: i
 
     ``cut=(threshold, capacity)``: the kernel also reports the candidates whose score exceeds ``threshold`` (the
     streaming top-K's current K-th score) -- the result carries ``.survivors`` = (positions int64 ascending, scores) or
-    None when more than ``capacity`` qualified.  With a cut, ``want_score=False`` skips the score array altogether."""
+    None when more than ``capacity`` qualified.  With a cut, ``want_score=False`` skips the score array altogether.
+
+    ``signed``: the terms may be negative (edge cosines, eps_expand_fill_signed): the kernel does not flag negative sums;
+    the caller must have checked the range (candidates.fused_scores_fit)."""
     dev = _need_gpu(rowptr, col, val, node_w, col_order, colptr_ub)
     _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
     _chk(node_w, torch.float32, "node_w"); _chk(col_order, torch.int32, "col_order"); _chk(colptr_ub, torch.int64, "colptr_ub")
@@ -390,11 +394,10 @@ def expand_candidates(rowptr, col, val, node_w, n_nodes: int, v_lo: int, v_hi: i
                 raise _lib.EpsError(f"expand_candidates: a column with {max_paths} two-hop paths needs {ws_bytes >> 30} GiB "
                                     "of bucket scratch; score such graphs with the pair kernels")
             ws = _expand_scratch(dev, ws_bytes)
-            _lib.check(lib.eps_expand_fill_tiled(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, v_lo, v_hi,
-                                                 _ptr(col_order), _ptr(colptr),
-                                                 _ptr(counts) if colptr_ub is not None else None, _ptr(cand_u), _ptr(cand_v),
-                                                 _ptr(cn), _ptr(score), _ptr(cut_rec), _ptr(ws), ws_bytes, int(tile_ranks),
-                                                 _stream(dev)), "eps_expand_fill")
+            fill = lib.eps_expand_fill_signed if signed else lib.eps_expand_fill_tiled
+            _lib.check(fill(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, v_lo, v_hi, _ptr(col_order), _ptr(colptr),
+                            _ptr(counts) if colptr_ub is not None else None, _ptr(cand_u), _ptr(cand_v), _ptr(cn), _ptr(score),
+                            _ptr(cut_rec), _ptr(ws), ws_bytes, int(tile_ranks), _stream(dev)), "eps_expand_fill")
             if cut_rec is not None:                      # one read-back for the status word and the survivor count
                 both = torch.stack([ws[0], cut_rec[1]]).tolist()
                 status, n_cut = both[0] & 0xFFFFFFFF, both[1] & 0xFFFFFFFF
@@ -1013,6 +1016,54 @@ def spmm_csr(rowptr, col, val, x: torch.Tensor, bias=None, relu=False, mean=Fals
         _lib.check(_lib.load().eps_spmm_csr(_ptr(rowptr), _ptr(col), _ptr(val), n_rows, _ptr(x), x.stride(0), f,
                                             _ptr(bias), int(relu), int(mean), _ptr(out), out.stride(0),
                                             _stream(dev)), "eps_spmm_csr")
+    return out
+
+
+COS_ROW_FLOATS = 32      # xhat rows padded to a multiple of 128 bytes (whole cache lines per gathered row)
+
+
+def cos_node_features(rowptr, col, val, x: torch.Tensor) -> torch.Tensor:
+    """xhat = normalise(x + (A @ x) / (rowsum(A) + 1e-6)), each row divided by max(||row||_2, 1e-8) (eps_cos_node_features).
+    ``x``: float32 [N, F] (any F >= 1; a row stride of its own is fine).  -> float32 [N, F] view of an [N, ldh] buffer whose
+    rows are 128-byte aligned and whose pad columns are zero (what ``edge_cosines`` reads)."""
+    dev = _need_gpu(rowptr, col, val, x, row_strided=(x,))
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val"); _chk(x, torch.float32, "x")
+    n = rowptr.numel() - 1
+    if x.dim() != 2 or x.shape[0] != n:
+        raise _lib.EpsError(f"cos_node_features: x must be [{n}, F], got {tuple(x.shape)}")
+    f = int(x.shape[1])
+    if f < 1:
+        raise _lib.EpsError("cos_node_features: x needs at least one feature column")
+    if val is not None and val.numel() != col.numel():
+        raise _lib.EpsError("cos_node_features: val and col differ in length")
+    ldh = (f + COS_ROW_FLOATS - 1) // COS_ROW_FLOATS * COS_ROW_FLOATS
+    buf = torch.empty((n, ldh), dtype=torch.float32, device=dev)
+    ldx = x.stride(0) if n > 1 else max(f, x.stride(0))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().eps_cos_node_features(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(x), ldx, f, _ptr(buf), ldh,
+                                                     _stream(dev)), "eps_cos_node_features")
+    return buf[:, :f]
+
+
+def edge_cosines(rowptr, col, xhat: torch.Tensor, revpos: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """c[e] = xhat[row(e)] . xhat[col(e)] for every stored entry -> float32[nnz] (eps_edge_cosines).  ``xhat``: the output of
+    ``cos_node_features``.  ``revpos`` (scan.reverse_positions of a SYMMETRIC pattern) computes each undirected entry once."""
+    dev = _need_gpu(rowptr, col, xhat, revpos, row_strided=(xhat,))
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(xhat, torch.float32, "xhat")
+    _chk(revpos, torch.int32, "revpos")
+    n = rowptr.numel() - 1
+    if xhat.dim() != 2 or xhat.shape[0] != n:
+        raise _lib.EpsError(f"edge_cosines: xhat must be [{n}, F], got {tuple(xhat.shape)}")
+    if revpos is not None and revpos.numel() != col.numel():
+        raise _lib.EpsError("edge_cosines: revpos and col differ in length")
+    f = int(xhat.shape[1])
+    ldh = xhat.stride(0) if n > 1 else max(f, xhat.stride(0))
+    if f < 1 or ldh % 4 or xhat.data_ptr() % 16:
+        raise _lib.EpsError("edge_cosines: xhat needs 16-byte aligned rows of at least one column (cos_node_features output)")
+    out = torch.empty(col.numel(), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().eps_edge_cosines(_ptr(rowptr), _ptr(col), n, _ptr(xhat), ldh, f, _ptr(revpos), _ptr(out),
+                                                _stream(dev)), "eps_edge_cosines")
     return out
 
 

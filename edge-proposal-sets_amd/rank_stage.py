@@ -195,6 +195,11 @@ def _print_epoch(results, run_i: int, epoch: int, loss: float) -> None:
 def run(args):
     args = default_model_configs(args)
     print(args)
+    if args.model == 'mlpcos' and not args.load_model:
+        # (before any data is generated: the run would otherwise fail at its first backward)
+        raise NotImplementedError("rank.py --model mlpcos trains its embedding through the cosine scores; that backward "
+                                  "is not implemented (mlpcos is supported for scoring: filter.py, or rank.py with "
+                                  "--load_model <state_dict.pt>)")
     if not torch.cuda.is_available():
         raise RuntimeError("rank stage needs a HIP device: the scoring path has no CPU fallback")
     device = torch.device(f'cuda:{args.device}')

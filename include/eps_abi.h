@@ -157,6 +157,16 @@ int eps_expand_fill_tiled(const int64_t *rowptr, const int32_t *col, const float
                           eps_score_cut *cut, void *workspace, int64_t workspace_bytes,
                           int32_t tile_ranks, void *stream);
 int64_t eps_expand_workspace_bytes(int64_t max_col_paths);
+/* eps_expand_fill_tiled for SIGNED terms (cosine-weighted common neighbours: val = edge cosines in [-1, 1]): the same
+ * exact 2^-40 fixed-point sums, without the in-kernel backstop that takes a negative sum for one that wrapped (status bit 2
+ * is never set).  The caller guarantees the range: every |sum| < 2^22 (candidates.fused_score_bound, which sums |terms|,
+ * is <= the largest degree for cosines).  A cut compares the raw sums with its threshold. */
+int eps_expand_fill_signed(const int64_t *rowptr, const int32_t *col, const float *val,
+                           const float *node_w, int64_t n_nodes, int64_t v_lo, int64_t v_hi,
+                           const int32_t *col_order, const int64_t *colptr, int64_t *cand_count,
+                           int32_t *cand_u, int32_t *cand_v, int32_t *cn, float *score,
+                           eps_score_cut *cut, void *workspace, int64_t workspace_bytes,
+                           int32_t tile_ranks, void *stream);
 
 /* ---- K7+K1+K8: threshold scan of the whole candidate set (filter.py:96-142 + :160-161 under --keep_top) ------------
  * Computes the score of EVERY 2-hop non-edge of the given columns like eps_expand_fill does (same 2^-40 fixed-point
@@ -646,6 +656,24 @@ int eps_katz_pair_scores(const int64_t *rowptr, const int32_t *col, const float 
                          const int32_t *col_t, const float *val_t, const int64_t *paths_out, const int64_t *paths_in,
                          int64_t n_nodes, const int32_t *u, const int32_t *v, int64_t n_pairs, double c1, double c2,
                          double c3, void *workspace, float *out, void *stream);
+
+/* ---- Cosine-weighted common neighbours: the prologue (csrc/cosine_cn.hip) -------------------------------------------
+ * Replaces the per-path cosines of models.py:556-575 ('simplecos' / 'mlpcos'): both factors of a path u - w - v depend
+ * on one stored entry, so the score is the edge-valued common-neighbour sum over the graph whose values are
+ *   eps_cos_node_features: xhat_i = x'_i / max(||x'_i||_2, 1e-8),  x' = x + (A @ x) / (rowsum(A) + 1e-6)
+ *                          (A's values, or ones for val == NULL).  A square [n_rows x n_rows]; x float32 [n_rows x f]
+ *                          with row stride ldx >= f (any f >= 1); xhat float32 [n_rows x ldh], ldh >= f -- a multiple of
+ *                          32 floats (128-byte rows) is what the gathers want.  Columns [f, ldh) of xhat are written 0;
+ *                          a row whose x' is zero gets a zero xhat row.
+ *   eps_edge_cosines:      c[e] = xhat_row(e) . xhat_col(e) for every stored entry e (cosines ignore A's values).  xhat
+ *                          as written above (ldh % 4 == 0, 16-byte aligned).  revpos (eps_reverse_positions of a
+ *                          SYMMETRIC pattern) computes each undirected entry once and writes it to both positions; NULL
+ *                          computes every entry (any pattern).
+ * One wave per row, neighbour rows gathered whole; float32 throughout like the reference. */
+int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                          const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, void *stream);
+int eps_edge_cosines(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const float *xhat, int64_t ldh,
+                     int32_t f, const int32_t *revpos, float *c, void *stream);
 
 #ifdef __cplusplus
 }
