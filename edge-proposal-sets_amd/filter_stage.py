@@ -106,8 +106,9 @@ GNN_PRUNE_SLACK = 1 << 20  # gnn_half_topk re-cuts its kept pairs to the running
 def gnn_half_topk(args, model, data, keep: int, rank: int, world: int):
     """The ``keep`` best proposals of a GNN filter, decoding each unordered candidate pair ONCE.
 
-    The reference scores both orientations of a pair (filter.py:96-121), but LinkPredictor decodes h_u * h_v
-    (models.py:478-485): the product commutes bit for bit, so score(u, v) == score(v, u).  On a symmetric pattern column v
+    The reference scores both orientations of a pair (filter.py:96-121), but LinkPredictor and DEA_GNN_JK decode h_u * h_v
+    (models.py:478-485, :118-120): the product commutes bit for bit, so score(u, v) == score(v, u) (DEA_GNN_JK's scores are
+    logits, as the reference writes them).  On a symmetric pattern column v
     therefore lists only its candidates u < v (eps_expand_unit_* with revpos: half the list), the decoder runs on those
     (half the MFMA work -- the decode is all of this filter's time: 39.5 -> 20 s on the ppa stand-in), the pairs whose score
     reaches the running ceil(keep/2)-th best are kept, and the final selection mirrors them and orders the rows by the
@@ -400,8 +401,8 @@ def run(args) -> str:
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             rows = torch.stack([(rows_k & 0xFFFFFFFF).to(torch.float32), (rows_k >> 32).to(torch.float32), rows_v], 1)
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    from .models import LinkGNN
-    if (GNN_HALF and 0 <= keep <= scan.MAX_K and isinstance(model, LinkGNN) and data.adj_t.device.type == "cuda"
+    from .models import DEA_GNN_JK, LinkGNN
+    if (GNN_HALF and 0 <= keep <= scan.MAX_K and isinstance(model, (LinkGNN, DEA_GNN_JK)) and data.adj_t.device.type == "cuda"
             and data.adj_t.n_rows == data.adj_t.n_cols and data.adj_t.nnz() < 1 << 30 and scan.is_symmetric(data.adj_t)
             and (keep > 0 or int(scan.half_paths(data.adj_t).sum().item()) < 1 << 29)):     # (the whole file: lists that fit)
         with torch.no_grad():

@@ -254,6 +254,15 @@ class CSRGraph:
             self._cache["gcn"] = CSRGraph(g.rowptr, g.col, nv, g.n_rows, g.n_cols)
         return self._cache["gcn"]
 
+    def tag_normalized(self) -> "CSRGraph":
+        """gcn_norm of torch_geometric 1.7.0 TAGConv [third-party, restated]: the same scaling as ``gcn_normalized`` WITHOUT
+        self loops, val' = (val * deg^-1/2[row]) * deg^-1/2[col] with deg = rowsum(A) and inf -> 0.  Cached per adjacency."""
+        if "tag" not in self._cache:
+            from . import ops
+            self._cache["tag"] = CSRGraph(self.rowptr, self.col, ops.gcn_norm(self.rowptr, self.col, self.val), self.n_rows,
+                                          self.n_cols)
+        return self._cache["tag"]
+
     def __repr__(self) -> str:
         return (f"CSRGraph(n_rows={self.n_rows}, n_cols={self.n_cols}, nnz={self.nnz()}, "
                 f"values={'float32' if self.val is not None else 'implicit 1'}, device={self.device})")

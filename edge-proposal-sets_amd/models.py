@@ -1,5 +1,5 @@
-"""GCN / SAGE / LinkPredictor / LinkGNN / CommonNeighborsPredictor with the reference's class
-names, constructor signatures, ``forward`` signatures and state-dict keys (models.py:163-187,
+"""GCN / SAGE / LinkPredictor / LinkGNN / DEA_GNN_JK / CommonNeighborsPredictor with the reference's class
+names, constructor signatures, ``forward`` signatures and state-dict keys (models.py:36-133, :163-187,
 :417-440, :461-485, :487-506, :508-575, :578-670, :673-790) -- the forward passes run on the
 hand-written HIP kernels (csrc/) instead of torch_geometric / torch_sparse / cuBLAS.
 
@@ -256,7 +256,35 @@ class LinkPredictor(torch.nn.Module):
         return self.decode(h2, torch.stack([idx, idx + b])).unsqueeze(1)
 
 
-class LinkGNN(torch.nn.Module):
+class _CachedEmbeddings:
+    """The node embeddings ``h`` of a GNN link model in eval mode, computed ONCE per (parameter and buffer versions, x,
+    adjacency) and reused for every scoring batch -- the reference recomputes them for each batch.  Graphs from
+    REORDER_MIN_NODES nodes on run the layers on the hubs-first relabelling (graph.degree_ordered: the SpMM's gathers hit
+    the cache more often); ``h`` comes back in the caller's node order.  A model supplies ``_node_input(x)`` and
+    ``_node_forward(xin, adj)``."""
+    _h_key = None
+    _h = None
+
+    @torch.no_grad()
+    def embeddings(self, x: Optional[torch.Tensor], adj: CSRGraph) -> torch.Tensor:
+        key = (adj.uid, None if x is None else (x.data_ptr(), x._version),
+               tuple((p.data_ptr(), p._version) for p in self.parameters()),
+               tuple((b.data_ptr(), b._version) for b in self.buffers()))
+        if key != self._h_key:
+            xin = self._node_input(x)
+            relabel = adj.n_rows >= REORDER_MIN_NODES and adj.n_rows == adj.n_cols
+            if relabel:
+                adj_run, perm, inv = adj.degree_ordered()
+                xin = xin[perm].contiguous()
+            else:
+                adj_run = adj
+            h = self._node_forward(xin, adj_run)
+            self._h = h[inv].contiguous() if relabel else h
+            self._h_key = key
+        return self._h
+
+
+class LinkGNN(_CachedEmbeddings, torch.nn.Module):
     """models.py:487-506."""
 
     def __init__(self, emb, gnn, linkpred):
@@ -274,36 +302,20 @@ class LinkGNN(torch.nn.Module):
             self.emb.reset_parameters()
         self._h_key = None
 
-    @torch.no_grad()
-    def embeddings(self, x: Optional[torch.Tensor], adj: CSRGraph) -> torch.Tensor:
-        """h = gnn([emb.weight || x], adj), embedding FIRST (models.py:501-505); cached per
-        (parameter versions, x, adjacency) -- the reference recomputes it for every scoring batch."""
-        key = (adj.uid, None if x is None else (x.data_ptr(), x._version),
-               tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if key != self._h_key:
-            if x is None:
-                xin = self.emb.weight.detach()
-            elif self.emb is not None:
-                xin = torch.cat([self.emb.weight.detach(), x], dim=1)
-            else:
-                xin = x
-            from . import dist as epd
-            rank, world = epd.world_info()
-            # large graphs run the layers on the hubs-first relabelling (graph.degree_ordered: the SpMM's gathers hit the
-            # cache more often); the embeddings come back in the caller's node order
-            relabel = adj.n_rows >= REORDER_MIN_NODES and adj.n_rows == adj.n_cols
-            if relabel:
-                adj_run, perm, inv = adj.degree_ordered()
-                xin = xin[perm].contiguous()
-            else:
-                adj_run = adj
-            if world > 1 and hasattr(self.gnn, "forward_sharded"):
-                h = self.gnn.forward_sharded(xin, adj_run, rank, world, epd.all_gather_rows)
-            else:
-                h = self.gnn(xin, adj_run)
-            self._h = h[inv].contiguous() if relabel else h
-            self._h_key = key
-        return self._h
+    def _node_input(self, x):
+        """[emb.weight || x], embedding FIRST (models.py:501-505)."""
+        if x is None:
+            return self.emb.weight.detach()
+        if self.emb is not None:
+            return torch.cat([self.emb.weight.detach(), x], dim=1)
+        return x
+
+    def _node_forward(self, xin, adj):
+        from . import dist as epd
+        rank, world = epd.world_info()
+        if world > 1 and hasattr(self.gnn, "forward_sharded"):
+            return self.gnn.forward_sharded(xin, adj, rank, world, epd.all_gather_rows)
+        return self.gnn(xin, adj)
 
     def forward(self, x, edges, adj):
         if torch.is_grad_enabled() and self.training:   # models.py:500-506 on autograd (no caching while training)
@@ -315,6 +327,188 @@ class LinkGNN(torch.nn.Module):
             return self.linkpred(h[edges[0]], h[edges[1]])
         h = self.embeddings(x, adj)
         return self.linkpred.decode(h, edges).unsqueeze(1)
+
+
+# ----------------------------------------------------------------------------------- DEA_GNN_JK
+def fold_batchnorm(weight: torch.Tensor, bias: torch.Tensor, bn: torch.nn.BatchNorm1d):
+    """(W', b') such that x W'^T + b' == bn(x W^T + b) with bn in eval mode (running statistics):
+    s = gamma / sqrt(var + eps), W' = s W, b' = s b + beta - s mu.  Formed in float64, returned in W's dtype."""
+    f = torch.float64
+    s = bn.weight.detach().to(f) / torch.sqrt(bn.running_var.to(f) + bn.eps)
+    w = s[:, None] * weight.detach().to(f)
+    b = s * bias.detach().to(f) + bn.bias.detach().to(f) - s * bn.running_mean.to(f)
+    return w.to(weight.dtype).contiguous(), b.to(weight.dtype).contiguous()
+
+
+class TAGConv(torch.nn.Module):
+    """torch_geometric 1.7.0 TAGConv(in, out, K) with normalize=True [third-party, restated]: with
+    A^ = D^-1/2 A D^-1/2 (no self loops, inf -> 0; graph.tag_normalized), out = lin([x || A^ x || ... || A^K x]),
+    ``lin`` = Linear(in * (K + 1), out) with bias.  Checkpoints in the PyG >= 2.0 layout (``lins.{k}.weight`` [out,in],
+    optional ``lins.{k}.bias`` and ``bias``) load too: the weights are concatenated along ``in`` in k order and every
+    bias is summed into ``lin.bias``."""
+
+    def __init__(self, in_channels: int, out_channels: int, K: int = 3):
+        super().__init__()
+        self.in_channels, self.out_channels, self.K = in_channels, out_channels, K
+        self.lin = torch.nn.Linear(in_channels * (K + 1), out_channels)
+
+    def reset_parameters(self):
+        self.lin.reset_parameters()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if prefix + "lin.weight" not in state_dict and prefix + "lins.0.weight" in state_dict:
+            ws = [state_dict.pop(f"{prefix}lins.{k}.weight") for k in range(self.K + 1)]
+            b = torch.zeros(ws[0].shape[0], dtype=ws[0].dtype, device=ws[0].device)
+            for k in [f"{prefix}lins.{k}.bias" for k in range(self.K + 1)] + [prefix + "bias"]:
+                if k in state_dict:
+                    b = b + state_dict.pop(k)
+            state_dict[prefix + "lin.weight"] = torch.cat(ws, 1)
+            state_dict[prefix + "lin.bias"] = b
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, x: torch.Tensor, adj_t: CSRGraph) -> torch.Tensor:
+        """Training (autograd): the hops through the HIP SpMM Function (A^ is symmetric, so its backward holds)."""
+        an = adj_t.tag_normalized()
+        xs = [x]
+        for _ in range(self.K):
+            xs.append(_SpMM.apply(xs[-1], an, False))
+        return self.lin(torch.cat(xs, 1))
+
+    @torch.no_grad()
+    def hops(self, x: torch.Tensor, an: CSRGraph) -> torch.Tensor:
+        """[x || A^ x || ... || A^K x] in ONE [N, (K + 1) * k4] buffer (k4 = in rounded up to 4 floats, zero pad columns:
+        every block starts 16-byte aligned); each hop is an SpMM from the previous block into the next."""
+        n, k = x.shape
+        k4 = (k + 3) // 4 * 4
+        buf = (torch.empty if k4 == k else torch.zeros)((n, (self.K + 1) * k4), dtype=torch.float32, device=x.device)
+        buf[:, :k] = x
+        for j in range(1, self.K + 1):
+            ops.spmm_csr(an.rowptr, an.col, an.val, buf[:, (j - 1) * k4:(j - 1) * k4 + k], out=buf[:, j * k4:j * k4 + k])
+        return buf
+
+    def hop_weight(self, w: torch.Tensor) -> torch.Tensor:
+        """``w`` [out, (K + 1) * in] laid out for ``hops``' buffer (zero columns at the pad of each block)."""
+        k, k4 = self.in_channels, (self.in_channels + 3) // 4 * 4
+        if k4 == k:
+            return w
+        wp = torch.zeros((w.shape[0], self.K + 1, k4), dtype=w.dtype, device=w.device)
+        wp[:, :, :k] = w.view(w.shape[0], self.K + 1, k)
+        return wp.view(w.shape[0], -1)
+
+    def __repr__(self):
+        return f"TAGConv({self.in_channels}, {self.out_channels}, K={self.K})"
+
+
+_JK_MODES = ('max', 'sum', 'mean')
+
+
+class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
+    """models.py:36-133: a learnable embedding (FIRST in the input, [emb.weight || x]), ``gnn_num_layers`` x [TAGConv(K),
+    BatchNorm, ReLU, dropout], jumping knowledge over the layer outputs, then the decoder h[u] * h[v] -> (mlp_num_layers - 1)
+    x [Linear, BatchNorm, ReLU, dropout] -> Linear(hidden, out).squeeze(1).  The output is a LOGIT; ``loss`` is
+    BCEWithLogitsLoss.
+
+    Training mode runs on torch autograd with the hops through the HIP SpMM.  Eval mode runs on the HIP kernels: per layer
+    the hop buffer (TAGConv.hops) and one GEMM with the BatchNorm folded into its weights and ReLU in its epilogue; the
+    embeddings are cached like LinkGNN's; the decode is eps_mlp_decode (logits) with the decoder's BatchNorms folded in."""
+
+    def __init__(self, num_nodes, embed_dim, gnn_in_dim, gnn_hidden_dim, gnn_out_dim, gnn_num_layers, mlp_in_dim,
+                 mlp_hidden_dim, mlp_out_dim=1, mlp_num_layers=2, dropout=0.5, gnn_batchnorm=False, mlp_batchnorm=False, K=2,
+                 jk_mode='max'):
+        super().__init__()
+        if jk_mode not in _JK_MODES:
+            # the reference accepts 'lstm' / 'cat' too and then fails in its decoder or in JumpingKnowledge: say so here
+            raise ValueError(f"DEA_GNN_JK: jk_mode '{jk_mode}' is not supported (one of {', '.join(_JK_MODES)})")
+        self.emb = torch.nn.Embedding(num_nodes, embedding_dim=embed_dim)
+        self.convs = torch.nn.ModuleList([TAGConv(gnn_in_dim, gnn_hidden_dim, K)] +
+                                         [TAGConv(gnn_hidden_dim, gnn_hidden_dim, K) for _ in range(gnn_num_layers - 2)] +
+                                         [TAGConv(gnn_hidden_dim, gnn_out_dim, K)])
+        self.lins = torch.nn.ModuleList([torch.nn.Linear(mlp_in_dim, mlp_hidden_dim)] +
+                                        [torch.nn.Linear(mlp_hidden_dim, mlp_hidden_dim) for _ in range(mlp_num_layers - 2)] +
+                                        [torch.nn.Linear(mlp_hidden_dim, mlp_out_dim)])
+        self.gnn_batchnorm, self.mlp_batchnorm = gnn_batchnorm, mlp_batchnorm
+        if gnn_batchnorm:
+            self.gnn_bns = torch.nn.ModuleList([torch.nn.BatchNorm1d(gnn_hidden_dim) for _ in range(gnn_num_layers)])
+        if mlp_batchnorm:
+            self.mlp_bns = torch.nn.ModuleList([torch.nn.BatchNorm1d(mlp_hidden_dim) for _ in range(mlp_num_layers - 1)])
+        self.jk_mode = jk_mode
+        self.dropout = dropout
+        self.loss_fn = torch.nn.BCEWithLogitsLoss()
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.emb.weight)
+        for conv in self.convs:
+            conv.reset_parameters()
+        for lin in self.lins:
+            lin.reset_parameters()
+        for bn in (list(self.gnn_bns) if self.gnn_batchnorm else []) + (list(self.mlp_bns) if self.mlp_batchnorm else []):
+            bn.reset_parameters()
+        self._h_key = None
+
+    def _jk(self, outs):
+        if self.jk_mode == 'max':
+            return torch.stack(outs).max(0).values
+        s = torch.stack(outs).sum(0)
+        return s / len(outs) if self.jk_mode == 'mean' else s
+
+    def _node_input(self, x):
+        w = self.emb.weight.detach()
+        return w if x is None else torch.cat([w, x], 1)
+
+    def _node_forward(self, xin, adj):
+        """Eval: per layer the hop buffer, then ONE GEMM with the BatchNorm folded in and ReLU in the epilogue."""
+        an = adj.tag_normalized()
+        x, h, n_out = xin, None, len(self.convs)
+        for i, conv in enumerate(self.convs):
+            w, b = conv.lin.weight.detach(), conv.lin.bias.detach()
+            if self.gnn_batchnorm:
+                w, b = fold_batchnorm(w, b, self.gnn_bns[i])
+            x = ops.gemm(conv.hops(x, an), conv.hop_weight(w), bias=b.contiguous(), relu=True)
+            if h is None:
+                h = x
+            elif self.jk_mode == 'max':
+                h = torch.maximum(h, x, out=h)        # (x of the layer before is in this layer's hop buffer already)
+            else:
+                h = h + x
+        return h / n_out if self.jk_mode == 'mean' else h
+
+    @torch.no_grad()
+    def decode(self, h: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+        """Logits of the decoder over edges [2,B] (eps_mlp_decode with the BatchNorms folded in) -> float32 [B]."""
+        heuristics.check_node_ids(edges, h.shape[0], "decode edges")   # the kernel gathers h[u], h[v] unchecked
+        e = edges.to(device=h.device, dtype=torch.int32)
+        ws, bs = [], []
+        for i, lin in enumerate(self.lins):
+            w, b = lin.weight.detach(), lin.bias.detach()
+            if self.mlp_batchnorm and i < len(self.lins) - 1:
+                w, b = fold_batchnorm(w, b, self.mlp_bns[i])
+            ws.append(w.contiguous())
+            bs.append(b.contiguous())
+        return ops.mlp_decode(h.contiguous(), e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid=False)
+
+    def forward(self, x_feature, edge_label_index, adj_t):
+        if not self.training:
+            return self.decode(self.embeddings(x_feature, adj_t), edge_label_index)
+        out = self.emb.weight if x_feature is None else torch.cat([self.emb.weight, x_feature], dim=1)
+        outs = []
+        for i, conv in enumerate(self.convs):
+            out = conv(out, adj_t)
+            if self.gnn_batchnorm:
+                out = self.gnn_bns[i](out)
+            out = F.dropout(F.relu(out), p=self.dropout, training=True)
+            outs.append(out)
+        out = self._jk(outs)
+        out = out[edge_label_index[0]] * out[edge_label_index[1]]
+        for i, lin in enumerate(self.lins[:-1]):
+            out = lin(out)
+            if self.mlp_batchnorm:
+                out = self.mlp_bns[i](out)
+            out = F.dropout(F.relu(out), p=self.dropout, training=True)
+        return self.lins[-1](out).squeeze(1)
+
+    def loss(self, y_pred, y_true):
+        return self.loss_fn(y_pred, y_true)
 
 
 class MLP(torch.nn.Module):
@@ -409,7 +603,7 @@ _HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', 
 
 
 def build_model(args, data, device):
-    """models.py:578-670 for the models on the accelerated path (gcn, sage, heuristics)."""
+    """models.py:578-670 for the models on the accelerated path (gcn, sage, dea, dea_512, heuristics)."""
     assert args.model in _MODELS
     if args.model in _COSINE:
         # the reference would fail inside its forward (emb.weight of None, models.py:529-532): say why here
@@ -419,6 +613,8 @@ def build_model(args, data, device):
         if not args.use_feature and not args.use_learnable_embedding:
             raise ValueError(f"--model {args.model} needs node features: pass --use_feature True (on a dataset that has "
                              "them) or --use_learnable_embedding True")
+    if args.model in ('dea', 'dea_512'):
+        return _build_dea(args, data, device)
     emb = None
     if args.use_learnable_embedding:
         emb = torch.nn.Embedding(data.num_nodes, args.hidden_channels).to(device)
@@ -441,8 +637,34 @@ def build_model(args, data, device):
     if args.model in _HEURISTICS:
         return CommonNeighborsPredictor(emb, input_dim, args.hidden_channels, args.hidden_channels, args.num_layers,
                                         args.dropout, model_type=args.model).to(device)
-    raise NotImplementedError(f"model '{args.model}' (sage2 / dea / ensemble) is outside the accelerated path "
+    raise NotImplementedError(f"model '{args.model}' (sage2 / ensemble_gcn_sage) is outside the accelerated path "
                               "(SURVEY 2.1: alternative / experimental models, not in the north star)")
+
+
+DEA_MAX_HIDDEN = 512             # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 512
+
+
+class UnsupportedModelConfig(ValueError, NotImplementedError):
+    """A model configuration refused at build time (the reference would fail later, or the kernels do not take it).  A
+    ValueError; also a NotImplementedError, which is what build_model raised for every 'dea' configuration before the
+    model was supported."""
+
+
+def _build_dea(args, data, device):
+    """models.py:629-636: 3 TAGConv(K=2) layers and a 2-layer decoder of width --hidden_channels, BatchNorm in both, JK max
+    (--num_layers does not change the depth).  The reference fails later on the combinations refused here."""
+    hc = args.hidden_channels
+    if hc is None:
+        raise UnsupportedModelConfig(f"--model {args.model} needs --hidden_channels (the reference has no {getattr(args, 'dataset', '')} default for it)")
+    if hc % 4 != 0 or hc > DEA_MAX_HIDDEN:
+        raise UnsupportedModelConfig(f"--hidden_channels {hc}: the fused decode kernel takes a multiple of 4 up to {DEA_MAX_HIDDEN}")
+    if not args.use_learnable_embedding:
+        # its forward always puts emb.weight first; without the flag the first layer's input width would not count it
+        raise UnsupportedModelConfig(f"--model {args.model} needs --use_learnable_embedding True (its input is [embedding || x])")
+    input_dim = hc + (data.x.shape[1] if args.use_feature else 0)
+    return DEA_GNN_JK(num_nodes=data.num_nodes, embed_dim=hc, gnn_in_dim=input_dim, gnn_hidden_dim=hc, gnn_out_dim=hc,
+                      gnn_num_layers=3, mlp_in_dim=hc, mlp_hidden_dim=hc, mlp_out_dim=1, mlp_num_layers=2,
+                      dropout=args.dropout, gnn_batchnorm=True, mlp_batchnorm=True, K=2, jk_mode='max').to(device)
 
 
 # per-dataset defaults, one row per (dataset group, model group): restates the table of models.py:673-790

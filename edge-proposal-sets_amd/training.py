@@ -1,4 +1,4 @@
-"""Training loop of the rank stage (train_and_eval.py:31-96), for the GCN / SAGE + LinkPredictor models.
+"""Training loop of the rank stage (train_and_eval.py:31-96), for the GCN / SAGE + LinkPredictor and DEA_GNN_JK models.
 
 Outside the scored hot path but needed to produce the checkpoints filter.py consumes and to
 run rank.py with a parametrised model: torch autograd drives it, the GNN aggregate is the HIP SpMM (custom autograd
@@ -30,8 +30,9 @@ def negative_sampling(edge_index: torch.Tensor, num_nodes: int, num_neg_samples:
 
 
 def train(model, data, dataset_name, split_edge, optimizer, batch_size, use_params, model_str, device):
-    """train_and_eval.py:31-96: one epoch over the training edges; -log(pos) - log(1-neg) on a batch of positive
-    edges (both directions) and as many negatives; gradient clipping at 1.0; Adam step."""
+    """train_and_eval.py:31-96: one epoch over the training edges; -log(pos) - log(1-neg) (dea / dea_512: the model's
+    BCEWithLogitsLoss) on a batch of positive edges (both directions) and as many negatives; gradient clipping at 1.0;
+    Adam step."""
     model.train()
     pos_train_edge = split_edge['train']['edge'].to(device)
     row, col, _ = data.adj_t.coo()
@@ -43,7 +44,7 @@ def train(model, data, dataset_name, split_edge, optimizer, batch_size, use_para
         if use_params:
             optimizer.zero_grad()
         pos_edge = to_undirected(pos_train_edge[perm].t())
-        if model_str in ['gcn', 'sage']:
+        if model_str in ['gcn', 'sage', 'dea', 'dea_512']:
             if dataset_name in ["collab"]:
                 neg_edge = torch.randint(0, data.num_nodes, pos_edge.size(), dtype=torch.long, device=pos_edge.device)
             else:
@@ -54,7 +55,11 @@ def train(model, data, dataset_name, split_edge, optimizer, batch_size, use_para
         out = model(data.x, torch.cat([pos_edge, neg_edge], 1), data.adj_t).squeeze()
         pos_out = out[:pos_edge.size(1)]
         neg_out = out[pos_edge.size(1):]
-        loss = -torch.log(pos_out + 1e-8).mean() - torch.log(1 - neg_out + 1e-8).mean()
+        if model_str in ['dea', 'dea_512']:      # logits: BCEWithLogitsLoss against 1 / 0 labels (train_and_eval.py:66-71)
+            label = torch.cat([torch.ones(pos_edge.shape[1]), torch.zeros(neg_edge.shape[1])]).to(device)
+            loss = model.loss(out, label.type_as(out))
+        else:
+            loss = -torch.log(pos_out + 1e-8).mean() - torch.log(1 - neg_out + 1e-8).mean()
         if use_params:
             loss.backward()
             torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)

@@ -1,0 +1,308 @@
+"""GPU: DEA_GNN_JK (models.py:36-133) on the HIP kernels -- eps_mlp_decode past H = 256, the eval forward against a float64
+restatement of the model, a training step against a dense float64 autograd restatement, and the filter / rank command lines
+with --model dea / dea_512."""
+import argparse
+import os
+
+import numpy as np
+import pytest
+import scipy.sparse as ssp
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+BN_EPS = 1e-5
+
+
+# ---------------------------------------------------------------------------------------------------------- restatement
+def decode_truth(h, u, v, ws, bs, sigmoid):
+    """Hadamard -> (L-1) x [Linear, ReLU] -> Linear(H, 1) (-> sigmoid), float64."""
+    z = h[u] * h[v]
+    for w, b in zip(ws[:-1], bs[:-1]):
+        z = np.maximum(z @ w.T + b, 0.0)
+    z = (z @ ws[-1].T + bs[-1])[:, 0]
+    return 1.0 / (1.0 + np.exp(-z)) if sigmoid else z
+
+
+def tag_norm(A):
+    """D^-1/2 A D^-1/2 with D the row sums of A's values (no self loops), inf -> 0."""
+    A = ssp.csr_matrix(A, dtype=np.float64)
+    deg = np.asarray(A.sum(1)).ravel()
+    dis = np.zeros_like(deg)
+    dis[deg > 0] = deg[deg > 0] ** -0.5
+    return ssp.diags(dis) @ A @ ssp.diags(dis)
+
+
+def _bn(z, sd, pre):
+    return (z - sd[pre + ".running_mean"]) / np.sqrt(sd[pre + ".running_var"] + BN_EPS) * sd[pre + ".weight"] + sd[pre + ".bias"]
+
+
+def dea_embeddings_truth(sd, A, x):
+    """Eval-mode DEA_GNN_JK node embeddings: [emb || x] -> 3 x [TAGConv(K=2), BatchNorm, ReLU] -> JK max."""
+    An = tag_norm(A)
+    cur = sd["emb.weight"] if x is None else np.concatenate([sd["emb.weight"], x], 1)
+    outs = []
+    for i in range(3):
+        hs = np.concatenate([cur, An @ cur, An @ (An @ cur)], 1)
+        cur = np.maximum(_bn(hs @ sd[f"convs.{i}.lin.weight"].T + sd[f"convs.{i}.lin.bias"], sd, f"gnn_bns.{i}"), 0.0)
+        outs.append(cur)
+    return np.max(np.stack(outs), 0)
+
+
+def dea_logits_truth(sd, h, u, v):
+    z = h[u] * h[v]
+    z = np.maximum(_bn(z @ sd["lins.0.weight"].T + sd["lins.0.bias"], sd, "mlp_bns.0"), 0.0)
+    return (z @ sd["lins.1.weight"].T + sd["lins.1.bias"])[:, 0]
+
+
+def _sd64(model):
+    return {k: v.detach().cpu().double().numpy() for k, v in model.state_dict().items()}
+
+
+def _tol(ref):
+    return 2e-5 * max(1.0, float(np.abs(ref).max()))
+
+
+def _dea(n, H, in_extra, seed, dev):
+    from eps_amd import models
+    torch.manual_seed(seed)
+    m = models.DEA_GNN_JK(n, H, H + in_extra, H, H, 3, H, H, 1, 2, 0.5, True, True, 2, "max").to(dev)
+    with torch.no_grad():                      # non-trivial BatchNorm statistics, so that the fold is exercised
+        for bn in list(m.gnn_bns) + list(m.mlp_bns):
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.uniform_(-0.1, 0.1)
+            bn.running_mean.uniform_(-0.05, 0.05)
+            bn.running_var.uniform_(0.5, 2.0)
+    return m.eval()
+
+
+# ---------------------------------------------------------------------------------------------------------- decode kernel
+@pytest.mark.parametrize("H", [260, 384, 508, 512])
+@pytest.mark.parametrize("L", [1, 2, 3])
+def test_mlp_decode_wide_parity(eps, dev, H, L):
+    rng = np.random.default_rng(H * 10 + L)
+    n, n_pairs = 300, 1000 + 37                 # not a multiple of the 32-edge tile
+    h = rng.standard_normal((n, H)).astype(np.float32)
+    u = rng.integers(0, n, n_pairs).astype(np.int32)
+    v = rng.integers(0, n, n_pairs).astype(np.int32)
+    u[:50] = 7                                  # repeated endpoints ...
+    v[50:80] = u[50:80]                         # ... and u == v
+    ws = [(rng.standard_normal((H, H)) / np.sqrt(H)).astype(np.float32) for _ in range(L - 1)]
+    ws.append((rng.standard_normal((1, H)) / np.sqrt(H)).astype(np.float32))
+    bs = [(0.1 * rng.standard_normal(H)).astype(np.float32) for _ in range(L - 1)] + [np.float32([0.05])]
+    d = lambda a: torch.from_numpy(a).to(dev)
+    for sig in (False, True):
+        got = eps.ops.mlp_decode(d(h), d(u), d(v), [d(w) for w in ws], [d(b) for b in bs], apply_sigmoid=sig).cpu().numpy()
+        ref = decode_truth(h.astype(np.float64), u, v, [w.astype(np.float64) for w in ws],
+                           [b.astype(np.float64) for b in bs], sig)
+        assert float(np.abs(got - ref).max()) <= _tol(ref), (H, L, sig)
+
+
+def test_mlp_decode_rejects_past_512(eps, dev):
+    h = torch.zeros(4, 516, device=dev)
+    e = torch.zeros(3, dtype=torch.int32, device=dev)
+    with pytest.raises(eps._lib.EpsError, match="hdim"):
+        eps.ops.mlp_decode(h, e, e, [torch.zeros(1, 516, device=dev)], [torch.zeros(1, device=dev)])
+
+
+# ---------------------------------------------------------------------------------------------------------- eval forward
+def _graph(kind, dev):
+    from eps_amd.graph import CSRGraph
+    g = torch.Generator().manual_seed(3)
+    if kind == "big":                           # >= REORDER_MIN_NODES: the hubs-first relabelled path
+        n, m, live = 120_000, 500_000, 120_000
+    else:
+        n, m, live = 3000, 20_000, 2500         # nodes >= live are isolated
+    ei = torch.randint(0, live, (2, m), generator=g)
+    ei = ei[:, ei[0] != ei[1]]
+    val = torch.rand(ei.shape[1], generator=g) + 0.5 if kind == "weighted" else None
+    adj = CSRGraph.from_edge_index(ei, val, (n, n)).to_symmetric()
+    if kind != "weighted":
+        adj = adj.fill_value(1.0)
+    return adj.to(dev), n
+
+
+@pytest.mark.parametrize("kind,H,feat", [("unit", 256, 0), ("unit", 512, 0), ("weighted", 256, 20), ("weighted", 512, 0),
+                                         ("unit", 512, 36), ("big", 256, 0)])
+def test_eval_forward_matches_restatement(eps, dev, kind, H, feat):
+    from eps_amd import models
+    adj, n = _graph(kind, dev)
+    assert (n >= models.REORDER_MIN_NODES) == (kind == "big")
+    m = _dea(n, H, feat, 11, dev)
+    x = torch.randn(n, feat, device=dev) if feat else None
+    A = adj.to_scipy()
+    sd = _sd64(m)
+    xn = None if x is None else x.cpu().double().numpy()
+    h_ref = dea_embeddings_truth(sd, A, xn)
+    h = m.embeddings(x, adj)
+    assert float(np.abs(h.cpu().numpy() - h_ref).max()) <= _tol(h_ref)
+    g = torch.Generator().manual_seed(4)
+    e = torch.randint(0, n, (2, 5000), generator=g)
+    e[1, :40] = e[0, :40]
+    ref = dea_logits_truth(sd, h_ref, e[0].numpy(), e[1].numpy())
+    got = m(x, e.to(dev), adj)
+    assert got.shape == (5000,)
+    assert float(np.abs(got.cpu().numpy() - ref).max()) <= _tol(ref)
+
+
+def test_embeddings_cache_reused_and_invalidated(eps, dev):
+    adj, n = _graph("unit", dev)
+    m = _dea(n, 256, 0, 12, dev)
+    h1 = m.embeddings(None, adj)
+    assert m.embeddings(None, adj) is h1
+    with torch.no_grad():
+        m.convs[1].lin.weight.mul_(1.5)
+    h2 = m.embeddings(None, adj)
+    assert h2 is not h1
+    ref = dea_embeddings_truth(_sd64(m), adj.to_scipy(), None)
+    assert float(np.abs(h2.cpu().numpy() - ref).max()) <= _tol(ref)
+    with torch.no_grad():                       # a buffer (running statistics) counts too
+        m.gnn_bns[2].running_mean.add_(0.1)
+    assert m.embeddings(None, adj) is not h2
+
+
+# ---------------------------------------------------------------------------------------------------------- training
+def test_training_step_matches_dense_autograd(eps, dev):
+    from eps_amd import synth
+    torch.manual_seed(0)
+    g = synth.rmat_graph(8, 6, 4, "cpu")
+    n, H, fin = g.n_rows, 16, 12
+    adj = g.to(dev)
+    from eps_amd import models
+    m = models.DEA_GNN_JK(n, H, H + fin, H, H, 3, H, H, 1, 2, 0.0, True, True, 2, "max").to(dev).train()
+    x = torch.randn(n, fin, device=dev)
+    edges = torch.randint(0, n, (2, 300), device=dev)
+    label = torch.cat([torch.ones(150), torch.zeros(150)]).to(dev)
+    p64 = {k: v.detach().double().clone().requires_grad_(v.dtype.is_floating_point and "running" not in k)
+           for k, v in m.state_dict().items()}
+    out = m(x, edges, adj)
+    loss = m.loss(out, label)
+    loss.backward()
+
+    # dense float64 restatement on torch autograd (BatchNorm in training mode: batch statistics + running-stat update)
+    A = torch.from_numpy(g.to_scipy().toarray()).double().to(dev)
+    deg = A.sum(1)
+    dis = torch.where(deg > 0, deg.pow(-0.5), torch.zeros_like(deg))
+    An = dis[:, None] * A * dis[None, :]
+    cur = torch.cat([p64["emb.weight"], x.double()], 1)
+    outs = []
+    for i in range(3):
+        hs = torch.cat([cur, An @ cur, An @ (An @ cur)], 1)
+        z = hs @ p64[f"convs.{i}.lin.weight"].t() + p64[f"convs.{i}.lin.bias"]
+        pre = f"gnn_bns.{i}"
+        z = F.batch_norm(z, p64[pre + ".running_mean"], p64[pre + ".running_var"], p64[pre + ".weight"], p64[pre + ".bias"],
+                         training=True, momentum=0.1, eps=BN_EPS)
+        cur = torch.relu(z)
+        outs.append(cur)
+    h = torch.stack(outs).max(0).values
+    z = h[edges[0]] * h[edges[1]]
+    z = z @ p64["lins.0.weight"].t() + p64["lins.0.bias"]
+    z = torch.relu(F.batch_norm(z, p64["mlp_bns.0.running_mean"], p64["mlp_bns.0.running_var"], p64["mlp_bns.0.weight"],
+                                p64["mlp_bns.0.bias"], training=True, momentum=0.1, eps=BN_EPS))
+    ref = (z @ p64["lins.1.weight"].t() + p64["lins.1.bias"]).squeeze(1)
+    assert float((ref.detach() - out.detach().double()).abs().max()) <= 1e-4 * max(1.0, float(ref.detach().abs().max()))
+    F.binary_cross_entropy_with_logits(ref, label.double()).backward()
+    for k, p in m.named_parameters():
+        # (the biases in front of a training-mode BatchNorm have a true gradient of 0: float32 noise is all they get)
+        scale = max(1e-4, float(p64[k].grad.abs().max()))
+        assert float((p.grad.double() - p64[k].grad).abs().max()) <= 2e-4 * scale, k
+    for k, b in m.named_buffers():
+        if "running" in k:
+            assert float((b.double() - p64[k]).abs().max()) <= 1e-5 * max(1.0, float(p64[k].abs().max())), k
+
+
+def test_training_epochs_decrease_loss(eps, dev, monkeypatch):
+    monkeypatch.setenv("EPS_SYNTH_SCALE", "0.05")
+    from eps_amd import datasets, models, training
+    _, _, split_edge, data = datasets.get_data(argparse.Namespace(dataset="ddi", synthetic=True, use_feature=False))
+    data = data.to(dev)
+    torch.manual_seed(2)
+    args = argparse.Namespace(dataset="ddi", model="dea", hidden_channels=32, use_learnable_embedding=True,
+                              use_feature=False, dropout=0.5, num_layers=3)
+    m = models.build_model(args, data, dev)
+    opt = torch.optim.Adam(m.parameters(), lr=0.005)
+    losses = [training.train(m, data, "ddi", split_edge, opt, 4096, True, "dea", dev) for _ in range(6)]
+    assert min(losses[-2:]) < losses[0] - 0.02, losses     # BCE with logits starts near ln 2
+
+
+# ---------------------------------------------------------------------------------------------------------- command lines
+def _ddi_stand_in(monkeypatch, scale):
+    monkeypatch.setenv("EPS_SYNTH_SCALE", scale)
+    from eps_amd import datasets
+    return datasets.get_data(argparse.Namespace(dataset="ddi", synthetic=True, use_feature=False))
+
+
+def _save_reference_state(model_name, n, H, seed):
+    """A state dict of the reference's DEA_GNN_JK (non-trivial BatchNorm statistics) under models/."""
+    m = _dea(n, H, 0, seed, "cpu")
+    os.makedirs("models", exist_ok=True)
+    name = f"ddi_{model_name}||0|0.pt"
+    torch.save(m.state_dict(), os.path.join("models", name))
+    return name, _sd64(m)
+
+
+@pytest.mark.parametrize("model_name,H", [("dea", 256), ("dea_512", 512)])
+def test_filter_cli_keeps_restatement_top_k(eps, oracle, dev, tmp_path, monkeypatch, model_name, H):
+    monkeypatch.chdir(tmp_path)
+    ei, ew, split_edge, data = _ddi_stand_in(monkeypatch, "0.05")
+    n = data.num_nodes
+    name, sd = _save_reference_state(model_name, n, H, 21)
+    from eps_amd import filter_stage
+    K = 2000
+    fname = filter_stage.main(["--dataset", "ddi", "--model", model_name, "--checkpoint", name, "--synthetic",
+                               "--keep_top", str(K)])
+    got = torch.load(fname).numpy()
+    assert got.shape == (K, 3) and bool((got[:-1, 2] >= got[1:, 2]).all())
+    A = oracle.add_edges_scipy("ddi", ei.numpy(), ew.numpy(), np.zeros((2, 0), np.int64), n)
+    P = ssp.csr_matrix(A, dtype=np.float64)
+    P.data[:] = 1.0
+    two = (P @ P).tocoo()
+    cand = (two.row != two.col) & (np.asarray(P[two.row, two.col]).ravel() == 0)
+    cu, cv = two.row[cand], two.col[cand]
+    ref = dea_logits_truth(sd, dea_embeddings_truth(sd, A, None), cu, cv)
+    tol = _tol(ref)
+    kth = np.sort(ref)[-K]
+    ref_of = dict(zip(zip(cu.tolist(), cv.tolist()), ref.tolist()))
+    kept = set(zip(got[:, 0].astype(np.int64).tolist(), got[:, 1].astype(np.int64).tolist()))
+    assert len(kept) == K and kept <= set(ref_of)                          # K distinct candidates
+    for p in kept:                                                         # kept pairs reach the bar ...
+        assert ref_of[p] >= kth - tol, p
+    must = {p for p, s in ref_of.items() if s > kth + tol}                 # ... and every clear winner is kept
+    assert must <= kept
+    for (u, v, s) in got[:50]:
+        assert abs(s - ref_of[(int(u), int(v))]) <= tol                     # the file holds logits
+
+
+def test_rank_cli_trains_and_load_model_hits(eps, oracle, dev, tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    ei, ew, split_edge, data = _ddi_stand_in(monkeypatch, "0.05")
+    n = data.num_nodes
+    from eps_amd import evaluate, rank_stage
+    torch.manual_seed(3)
+    curves = rank_stage.main(["--dataset", "ddi", "--model", "dea", "--synthetic", "--runs", "1", "--epochs", "2",
+                              "--hidden_channels", "32", "--batch_size", "8192", "--save_models", "--eval_steps", "1"])
+    assert len(curves) == 1 and os.listdir("curves")
+    ckpts = [f for f in os.listdir("models") if f.startswith("ddi_dea")]
+    assert len(ckpts) == 1
+    # --load_model: a reference state dict is evaluated without training; Hits@20 equals the restatement's
+    name, sd = _save_reference_state("dea", n, 256, 31)
+    curves = rank_stage.main(["--dataset", "ddi", "--model", "dea", "--synthetic", "--runs", "1",
+                              "--load_model", os.path.join("models", name)])
+    K = evaluate.hits["ddi"][1]
+    A = oracle.add_edges_scipy("ddi", ei.numpy(), ew.numpy(), np.zeros((2, 0), np.int64), n)
+
+    def band(G, split):
+        h = dea_embeddings_truth(sd, G, None)
+        p = dea_logits_truth(sd, h, *split_edge[split]["edge"].t().numpy())
+        q = dea_logits_truth(sd, h, *split_edge[split]["edge_neg"].t().numpy())
+        tol = _tol(np.concatenate([p, q]))
+        if len(q) < K:
+            return 1.0, 1.0
+        return float(np.mean(p - tol > np.sort(q + tol)[-K])), float(np.mean(p + tol > np.sort(q - tol)[-K]))
+
+    lo, hi = band(A, "valid")
+    assert 100 * lo - 1e-4 <= float(curves[0][1]) <= 100 * hi + 1e-4, ("valid", lo, hi, curves[0])
+    lo, hi = band(A, "test")                   # (ddi scores its test edges on the same graph: rank.py adds the valid edges for
+                                               # collab / email / reddit only)
+    assert 100 * lo - 1e-4 <= float(curves[0][2]) <= 100 * hi + 1e-4, ("test", lo, hi, curves[0])
