@@ -116,6 +116,10 @@ SIGNATURES = {
                                     _c.c_double, _vp, _vp, _vp]),
     "eps_cos_node_features": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "eps_edge_cosines": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "eps_cos_node_features_nrm": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "eps_pair_cn_backward_workspace_bytes": (_i64, [_i64]),
+    "eps_pair_cn_backward": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "eps_cos_features_backward": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

@@ -15,104 +15,7 @@
 // float4) keep four neighbour rows per wave load instead of leaving 48 lanes idle.  Up to CC_REG_CHUNKS chunks live in
 // registers; wider rows (F in the thousands) stream the rest (node features: column panels, normalised at the end;
 // edge cosines: the row's chunks beyond the registers are re-read, from the cache).
-#include "eps_common.h"
-
-#define CC_THREADS 256
-#define CC_REG_CHUNKS 8          // chunks of G x VEC floats a lane keeps in registers (float4: 2048 features per wave)
-#define CC_FLIGHT_VEC4 8         // float4 loads in flight per lane per batch (divided over the chunks of a row)
-
-template <int VEC>
-struct CcVec;
-template <>
-struct CcVec<4> {
-    using type = float4;
-};
-template <>
-struct CcVec<1> {
-    using type = float;
-};
-
-__device__ __forceinline__ float4 cc_zero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float cc_zero(float) { return 0.f; }
-__device__ __forceinline__ void cc_fma(float4 &a, float s, const float4 &x)
-{
-    a.x = fmaf(s, x.x, a.x);
-    a.y = fmaf(s, x.y, a.y);
-    a.z = fmaf(s, x.z, a.z);
-    a.w = fmaf(s, x.w, a.w);
-}
-__device__ __forceinline__ void cc_fma(float &a, float s, float x) { a = fmaf(s, x, a); }
-__device__ __forceinline__ float cc_dot(const float4 &a, const float4 &b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float cc_dot(float a, float b) { return a * b; }
-
-// elements [c, c + VEC) of row p, zero past column f (c < f)
-__device__ __forceinline__ float4 cc_load(const float *__restrict__ p, int c, int f, float4)
-{
-    if (c + 4 <= f) return *reinterpret_cast<const float4 *>(p + c);
-    float4 r = make_float4(p[c], 0.f, 0.f, 0.f);
-    if (c + 1 < f) r.y = p[c + 1];
-    if (c + 2 < f) r.z = p[c + 2];
-    return r;
-}
-__device__ __forceinline__ float cc_load(const float *__restrict__ p, int c, int, float) { return p[c]; }
-
-__device__ __forceinline__ void cc_store(float *__restrict__ p, int c, int f, const float4 &v)
-{
-    if (c + 4 <= f) {
-        *reinterpret_cast<float4 *>(p + c) = v;
-        return;
-    }
-    p[c] = v.x;
-    if (c + 1 < f) p[c + 1] = v.y;
-    if (c + 2 < f) p[c + 2] = v.z;
-}
-__device__ __forceinline__ void cc_store(float *__restrict__ p, int c, int, float v) { p[c] = v; }
-
-// sum over the lanes whose ids differ only in the bits [lo, hi) of the lane id (lo, hi powers of two)
-__device__ __forceinline__ float cc_xor_sum(float x, int lo, int hi)
-{
-    for (int o = lo; o < hi; o <<= 1) x += __shfl_xor(x, o);
-    return x;
-}
-__device__ __forceinline__ float4 cc_xor_sum(float4 x, int lo, int hi)
-{
-    for (int o = lo; o < hi; o <<= 1) {
-        x.x += __shfl_xor(x.x, o);
-        x.y += __shfl_xor(x.y, o);
-        x.z += __shfl_xor(x.z, o);
-        x.w += __shfl_xor(x.w, o);
-    }
-    return x;
-}
-__device__ __forceinline__ float4 cc_axpy_div(const float4 &x, const float4 &a, float d)
-{
-    return make_float4(x.x + a.x / d, x.y + a.y / d, x.z + a.z / d, x.w + a.w / d);
-}
-__device__ __forceinline__ float cc_axpy_div(float x, float a, float d) { return x + a / d; }
-__device__ __forceinline__ float4 cc_div(const float4 &x, float d) { return make_float4(x.x / d, x.y / d, x.z / d, x.w / d); }
-__device__ __forceinline__ float cc_div(float x, float d) { return x / d; }
-
-// log2 of the lanes per slot: the smallest power of two whose lanes x vec floats span f (at most 64 lanes)
-static int cc_lanes_log2(int64_t f, int vec)
-{
-    const int64_t units = (f + vec - 1) / vec;
-    int lg = 0;
-    while (lg < 6 && (1ll << lg) < units) ++lg;
-    return lg;
-}
-
-static int cc_reg_chunks(int64_t chunks)     // register chunk template: 1, 2, 4 or 8
-{
-    return chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 4 ? 4 : 8;
-}
-
-static unsigned cc_blocks(int64_t n_rows)
-{
-    const int64_t waves_per_block = CC_THREADS / 64;
-    int64_t b = (n_rows + waves_per_block - 1) / waves_per_block;
-    const int64_t cap = (int64_t)eps_num_cus() * 16;
-    return (unsigned)(b < cap ? b : cap);
-}
+#include "cosine_common.h"
 
 // ---- xhat = normalise(x + (A @ x) / (rowsum(A) + 1e-6)) ---------------------------------------------------------------
 // One wave per row r.  Slot s gathers entries s, s + S, ... of row r (FLIGHT rows in flight per slot), the slots' partial
@@ -122,7 +25,8 @@ static unsigned cc_blocks(int64_t n_rows)
 template <int VEC, int NCR, bool HAS_VAL>
 __global__ __launch_bounds__(CC_THREADS) void cos_node_features_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int64_t n_rows,
-    const float *__restrict__ x, int64_t ldx, int32_t f, int32_t lg, float *__restrict__ xhat, int64_t ldh)
+    const float *__restrict__ x, int64_t ldx, int32_t f, int32_t lg, float *__restrict__ xhat, int64_t ldh,
+    float *__restrict__ nrm_out)
 {
     using V = typename CcVec<VEC>::type;
     constexpr int FLIGHT = (CC_FLIGHT_VEC4 * 4 / VEC / NCR) > 0 ? (CC_FLIGHT_VEC4 * 4 / VEC / NCR) : 1;
@@ -196,6 +100,7 @@ __global__ __launch_bounds__(CC_THREADS) void cos_node_features_kernel(
         }
         ss = cc_xor_sum(ss, 1, G);
         const float nrm = fmaxf(sqrtf(ss), 1e-8f);
+        if (nrm_out && lane == 0) nrm_out[r] = nrm;             // (kept for the backward: eps_cos_node_features_nrm)
         if (slot == 0) {
             if (!multi) {
 #pragma unroll
@@ -299,15 +204,15 @@ __global__ __launch_bounds__(CC_THREADS) void edge_cosines_kernel(const int64_t 
     }
 }
 
-extern "C" int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
-                                     const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, void *stream)
+static int cos_node_features(const char *who, const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                             const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, float *nrm, bool want_nrm,
+                             void *stream)
 {
-    EPS_REQUIRE(n_rows >= 0 && f >= 1 && ldx >= f && ldh >= f,
-                "eps_cos_node_features: bad shape (n_rows=%lld f=%d ldx=%lld ldh=%lld)", (long long)n_rows, f,
-                (long long)ldx, (long long)ldh);
+    EPS_REQUIRE(n_rows >= 0 && f >= 1 && ldx >= f && ldh >= f, "%s: bad shape (n_rows=%lld f=%d ldx=%lld ldh=%lld)", who,
+                (long long)n_rows, f, (long long)ldx, (long long)ldh);
     if (n_rows == 0) return EPS_OK;
-    EPS_REQUIRE(rowptr && col && x && xhat, "eps_cos_node_features: null pointer");
-    EPS_REQUIRE(n_rows < (1ll << 31), "eps_cos_node_features: node ids are int32");
+    EPS_REQUIRE(rowptr && col && x && xhat && (nrm || !want_nrm), "%s: null pointer", who);
+    EPS_REQUIRE(n_rows < (1ll << 31), "%s: node ids are int32", who);
     const bool vec4 = ldx % 4 == 0 && ((uintptr_t)x % 16) == 0 && ldh % 4 == 0 && ((uintptr_t)xhat % 16) == 0;
     const int vec = vec4 ? 4 : 1;
     const int lg = cc_lanes_log2(f, vec);
@@ -317,7 +222,7 @@ extern "C" int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, 
     const unsigned blocks = cc_blocks(n_rows);
 #define CC_NODE(VEC, NCR, HV)                                                                                          \
     hipLaunchKernelGGL((cos_node_features_kernel<VEC, NCR, HV>), dim3(blocks), dim3(CC_THREADS), 0, s, rowptr, col, val, \
-                       n_rows, x, ldx, f, lg, xhat, ldh)
+                       n_rows, x, ldx, f, lg, xhat, ldh, nrm)
 #define CC_NODE_V(VEC, HV)                                                                                             \
     do {                                                                                                               \
         if (ncr == 1) CC_NODE(VEC, 1, HV);                                                                             \
@@ -334,8 +239,21 @@ extern "C" int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, 
     }
 #undef CC_NODE_V
 #undef CC_NODE
-    EPS_CHECK_LAUNCH("eps_cos_node_features");
+    EPS_CHECK_LAUNCH(who);
     return EPS_OK;
+}
+
+extern "C" int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                                     const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, void *stream)
+{
+    return cos_node_features("eps_cos_node_features", rowptr, col, val, n_rows, x, ldx, f, xhat, ldh, nullptr, false, stream);
+}
+
+extern "C" int eps_cos_node_features_nrm(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                                         const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, float *nrm,
+                                         void *stream)
+{
+    return cos_node_features("eps_cos_node_features_nrm", rowptr, col, val, n_rows, x, ldx, f, xhat, ldh, nrm, true, stream);
 }
 
 extern "C" int eps_edge_cosines(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const float *xhat, int64_t ldh,

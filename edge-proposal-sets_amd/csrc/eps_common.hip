@@ -112,6 +112,7 @@ extern "C" void eps_warm_topk_keys(void *stream);
 extern "C" void eps_warm_topk_select(void *stream);
 extern "C" void eps_warm_tail_sort(void *stream);
 extern "C" void eps_warm_cosine_cn(void *stream);
+extern "C" void eps_warm_cosine_cn_bwd(void *stream);
 
 extern "C" int eps_warm_up(void)
 {
@@ -135,6 +136,7 @@ extern "C" int eps_warm_up(void)
     eps_warm_topk_select(s);
     eps_warm_tail_sort(s);
     eps_warm_cosine_cn(s);
+    eps_warm_cosine_cn_bwd(s);
     const hipError_t e = hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
     if (e != hipSuccess) {

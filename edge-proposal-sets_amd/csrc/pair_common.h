@@ -87,3 +87,34 @@ __device__ __forceinline__ T sparse_lane_sum(uint64_t mask, T x)
     return tot;
 }
 
+// Lower bound over a sorted LDS array of 2^lg entries (padded with INT_MAX): fully unrolled, branch-free steps,
+// trip count selected by a wave-uniform switch.  Returns pos in [0, 2^lg - 1]; the caller tests L[pos] == t.
+__device__ __forceinline__ int lb_pow2(const int32_t *L, int lg, int t)
+{
+    int pos = 0;
+    switch (lg) {
+    case 10: pos += (L[pos + 511] < t) ? 512 : 0; [[fallthrough]];
+    case 9: pos += (L[pos + 255] < t) ? 256 : 0; [[fallthrough]];
+    case 8: pos += (L[pos + 127] < t) ? 128 : 0; [[fallthrough]];
+    case 7: pos += (L[pos + 63] < t) ? 64 : 0; [[fallthrough]];
+    case 6: pos += (L[pos + 31] < t) ? 32 : 0; [[fallthrough]];
+    case 5: pos += (L[pos + 15] < t) ? 16 : 0; [[fallthrough]];
+    case 4: pos += (L[pos + 7] < t) ? 8 : 0; [[fallthrough]];
+    case 3: pos += (L[pos + 3] < t) ? 4 : 0; [[fallthrough]];
+    case 2: pos += (L[pos + 1] < t) ? 2 : 0; [[fallthrough]];
+    case 1: pos += (L[pos] < t) ? 1 : 0; [[fallthrough]];
+    default: break;
+    }
+    return pos;
+}
+
+// INT_MAX in the elements of a staged 16-byte group that lie past the end of the row (n entries)
+__device__ __forceinline__ v4i pad_tail(v4i x, int idx, int n)
+{
+    const int big = 0x7fffffff;
+    x.x = idx + 0 < n ? x.x : big;
+    x.y = idx + 1 < n ? x.y : big;
+    x.z = idx + 2 < n ? x.z : big;
+    x.w = idx + 3 < n ? x.w : big;
+    return x;
+}

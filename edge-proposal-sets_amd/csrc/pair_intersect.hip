@@ -33,38 +33,7 @@
                              // r06, 2^24 pairs of the ppa-like graph, uniform / stored edges: 64: 3.55 / 10.64 ms, 128: 3.33 / 10.41, 256: 5.20 / 11.81
 #define PI_SMALL_LG (PI_SMALL == 256 ? 8 : PI_SMALL == 128 ? 7 : 6)
 
-// Lower bound over a sorted LDS array of 2^lg entries (padded with INT_MAX): fully unrolled, branch-free steps,
-// trip count selected by a wave-uniform switch.  Returns pos in [0, 2^lg - 1]; the caller tests L[pos] == t.
-__device__ __forceinline__ int lb_pow2(const int32_t *L, int lg, int t)
-{
-    int pos = 0;
-    switch (lg) {
-    case 10: pos += (L[pos + 511] < t) ? 512 : 0; [[fallthrough]];
-    case 9: pos += (L[pos + 255] < t) ? 256 : 0; [[fallthrough]];
-    case 8: pos += (L[pos + 127] < t) ? 128 : 0; [[fallthrough]];
-    case 7: pos += (L[pos + 63] < t) ? 64 : 0; [[fallthrough]];
-    case 6: pos += (L[pos + 31] < t) ? 32 : 0; [[fallthrough]];
-    case 5: pos += (L[pos + 15] < t) ? 16 : 0; [[fallthrough]];
-    case 4: pos += (L[pos + 7] < t) ? 8 : 0; [[fallthrough]];
-    case 3: pos += (L[pos + 3] < t) ? 4 : 0; [[fallthrough]];
-    case 2: pos += (L[pos + 1] < t) ? 2 : 0; [[fallthrough]];
-    case 1: pos += (L[pos] < t) ? 1 : 0; [[fallthrough]];
-    default: break;
-    }
-    return pos;
-}
-
 typedef int v4i_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ v4i pad_tail(v4i x, int idx, int n)
-{
-    const int big = 0x7fffffff;
-    x.x = idx + 0 < n ? x.x : big;
-    x.y = idx + 1 < n ? x.y : big;
-    x.z = idx + 2 < n ? x.z : big;
-    x.w = idx + 3 < n ? x.w : big;
-    return x;
-}
 
 // PART (r06): 0 = every pair, one at a time per wave (stored values, float64 weights); 1 = the SMALL pairs only, four at a time;
 // 2 = everything but the small pairs.  r05 had the small-pair path inside the one kernel: its 16 staging registers took the

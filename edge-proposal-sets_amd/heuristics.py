@@ -9,6 +9,7 @@ types:
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
 * ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
+* ``cosine_common_neighbors_raw(adj, x, edges)``     <- the same before the sigmoid, differentiable in x (training)
 
 Where the reference loops over 2000-pair batches on one CPU thread through SciPy, these upload
 the pair list once, run ``eps_pair_scores`` (csrc/pair_intersect.hip) over all of it and hand
@@ -193,6 +194,83 @@ def cosine_common_neighbors(adj: CSRGraph, x: torch.Tensor, edges: torch.Tensor)
     cg = cosine_graph(g, x)
     _, cn, _ = pair_scores_streamed(cg, u, v, None, want_cn=True)
     return torch.sigmoid(cn)
+
+
+def _aligned_rows(x: torch.Tensor) -> torch.Tensor:
+    """x as float32 rows the gathers can read whole as float4: a copy into 128-byte aligned rows where x is not already so."""
+    if x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and x.dtype == torch.float32:
+        return x
+    f = x.shape[1]
+    buf = torch.zeros((x.shape[0], (f + ops.COS_ROW_FLOATS - 1) // ops.COS_ROW_FLOATS * ops.COS_ROW_FLOATS),
+                      dtype=torch.float32, device=x.device)
+    buf[:, :f] = x
+    return buf[:, :f]
+
+
+class _CosineCN(torch.autograd.Function):
+    """raw[p] = sum_{w in N(u_p) & N(v_p)} cos(x'_u, x'_w) cos(x'_v, x'_w) with a gradient for the LEADING columns of the
+    features: x = [w || feat], w [N, H] the differentiable part (an embedding), feat constant columns or None.  Forward: the
+    kernels of ``cosine_graph`` + eps_pair_scores; backward: eps_pair_cn_backward (-> dL/dc per entry),
+    eps_cos_features_backward (-> dL/dx' and dL/dx' / deg), and the smoothing's transpose as one eps_spmm_csr over the H columns
+    (the adjacency is symmetric, values included: the assumption models._SpMM makes)."""
+
+    @staticmethod
+    def forward(ctx, w, feat, g, revpos, u, v):
+        x = w.detach() if feat is None else torch.cat([w.detach(), feat.detach().to(w.dtype)], dim=1)
+        xhat, nrm = ops.cos_node_features(g.rowptr, g.col, g.val, _aligned_rows(x), want_norm=True)
+        c = ops.edge_cosines(g.rowptr, g.col, xhat, revpos)
+        _, raw, _ = pair_scores_streamed(CSRGraph(g.rowptr, g.col, c, g.n_rows, g.n_cols), u, v, None, want_cn=True)
+        ctx.save_for_backward(xhat, nrm, c, u, v)
+        ctx.graph, ctx.revpos, ctx.hidden = g, revpos, w.shape[1]
+        return raw
+
+    @staticmethod
+    def backward(ctx, grad_raw):
+        xhat, nrm, c, u, v = ctx.saved_tensors
+        g, h = ctx.graph, ctx.hidden
+        gc = ops.pair_cn_backward(g.rowptr, g.col, c, u, v, grad_raw.to(torch.float32).contiguous())
+        gxp, gxs = ops.cos_features_backward(g.rowptr, g.col, g.val, xhat, nrm, ctx.revpos, gc, want_scaled=True)
+        gx = ops.spmm_csr(g.rowptr, g.col, g.val, gxs[:, :h])
+        return gx.add_(gxp[:, :h]), None, None, None, None, None
+
+
+def cosine_common_neighbors_raw(adj: CSRGraph, x: torch.Tensor, edges: torch.Tensor,
+                                feat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw (pre-sigmoid) cosine common-neighbour sums of ``cosine_common_neighbors`` over the features [x || feat],
+    DIFFERENTIABLE in ``x`` (float32 [N, H] on the device, e.g. emb.weight; ``feat`` takes no gradient): what training mlpcos /
+    simplecos-with-embedding needs (train_and_eval.py:31-96).  Same forward kernels as the scoring path; nothing is cached --
+    the embedding changes every step -- and the backward needs a symmetric adjacency."""
+    from . import scan
+    g = _as_graph(adj)
+    if x is None or x.dim() != 2 or x.shape[0] != g.n_rows or x.shape[1] < 1 or x.dtype != torch.float32:
+        raise EpsError(f"cosine_common_neighbors_raw: x must be float32 [{g.n_rows}, H], got "
+                       f"{None if x is None else (tuple(x.shape), x.dtype)}")
+    if not x.is_cuda:
+        raise EpsError("cosine_common_neighbors_raw: x must be on the HIP device (there is no CPU fallback)")
+    if feat is not None and (feat.dim() != 2 or feat.shape[0] != g.n_rows):
+        raise EpsError(f"cosine_common_neighbors_raw: feat must be [{g.n_rows}, F], got {tuple(feat.shape)}")
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"cosine_common_neighbors_raw needs a square adjacency, got {g.sparse_sizes()}")
+    if g.nnz() >= 1 << 31:
+        raise EpsError("cosine_common_neighbors_raw: the reverse-position table takes fewer than 2^31 stored entries")
+    if not scan.is_symmetric(g) or not values_are_symmetric(g):
+        raise EpsError("cosine_common_neighbors_raw: the backward needs a symmetric adjacency (pattern and values): it "
+                       "reads each cosine's gradient at both stored copies and multiplies by A in place of A^T")
+    u, v = _as_pairs(edges, g.device, g.n_rows)
+    revpos = scan.reverse_positions(g)
+    return _CosineCN.apply(x, None if feat is None else feat.to(g.device), g, revpos, u, v)
+
+
+def values_are_symmetric(g: CSRGraph) -> bool:
+    """Whether val[(r, w)] == val[(w, r)] on a graph with a symmetric pattern (cached; unit-valued graphs trivially)."""
+    if g.val is None or g.nnz() == 0:
+        return True
+    if "values_symmetric" not in g._cache:
+        from . import scan
+        row, col, _ = g.coo()
+        rev = g.rowptr[col.long()] + scan.reverse_positions(g).long()
+        g._cache["values_symmetric"] = bool(torch.equal(g.val[rev], g.val))
+    return g._cache["values_symmetric"]
 
 
 def sigmoid_raw_cut(bar: float) -> float:

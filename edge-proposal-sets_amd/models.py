@@ -537,8 +537,10 @@ class CommonNeighborsPredictor(torch.nn.Module):
     """models.py:508-575.  'simple' (CN) and 'adamic' run on eps_pair_scores; 'adamic_ogb',
     'resource_allocation', 'katz' return None exactly like the reference (those heuristics are evaluated by
     AA()/resource_allocation(), not by the module).  The cosine variants ('mlpcos', 'simplecos') score the edge-valued
-    common-neighbour sum of the cosine graph (heuristics.cosine_common_neighbors: csrc/cosine_cn.hip + eps_pair_scores);
-    inference only -- their forward does not build an autograd graph."""
+    common-neighbour sum of the cosine graph (heuristics.cosine_common_neighbors: csrc/cosine_cn.hip + eps_pair_scores).
+    Scoring (``model.eval()`` or ``torch.no_grad()``) builds no autograd graph.  In ``model.train()`` with grad enabled and a
+    learnable embedding the cosine variants are differentiable in emb.weight (heuristics.cosine_common_neighbors_raw:
+    csrc/cosine_cn_bwd.hip), which is how the reference trains mlpcos (train_and_eval.py:31-96)."""
 
     def __init__(self, emb, in_channels, hidden_channels, out_channels, num_layers, dropout, model_type='weighted'):
         super().__init__()
@@ -573,8 +575,16 @@ class CommonNeighborsPredictor(torch.nn.Module):
             self._x_key, self._x_src = key, x
         return self._x
 
-    @torch.no_grad()
     def forward(self, x, edges, adj):
+        if (self.type in _COSINE and self.training and torch.is_grad_enabled() and self.emb is not None
+                and self.emb.weight.requires_grad):
+            # training (train_and_eval.py:31-96): the gradient reaches emb.weight through the cosines (csrc/cosine_cn_bwd.hip);
+            # the feature columns take none, and self.mlp is never applied (models.py:564): its parameters keep grad None
+            return torch.sigmoid(heuristics.cosine_common_neighbors_raw(adj, self.emb.weight, edges, feat=x))
+        with torch.no_grad():
+            return self._score(x, edges, adj)
+
+    def _score(self, x, edges, adj):
         if self.type in ['adamic_ogb', "resource_allocation", 'katz']:
             return None                                                      # models.py:534-535
         if self.type == 'simple':

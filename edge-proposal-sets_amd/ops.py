@@ -1022,10 +1022,11 @@ def spmm_csr(rowptr, col, val, x: torch.Tensor, bias=None, relu=False, mean=Fals
 COS_ROW_FLOATS = 32      # xhat rows padded to a multiple of 128 bytes (whole cache lines per gathered row)
 
 
-def cos_node_features(rowptr, col, val, x: torch.Tensor) -> torch.Tensor:
+def cos_node_features(rowptr, col, val, x: torch.Tensor, want_norm: bool = False):
     """xhat = normalise(x + (A @ x) / (rowsum(A) + 1e-6)), each row divided by max(||row||_2, 1e-8) (eps_cos_node_features).
     ``x``: float32 [N, F] (any F >= 1; a row stride of its own is fine).  -> float32 [N, F] view of an [N, ldh] buffer whose
-    rows are 128-byte aligned and whose pad columns are zero (what ``edge_cosines`` reads)."""
+    rows are 128-byte aligned and whose pad columns are zero (what ``edge_cosines`` reads).  ``want_norm``: -> (xhat, nrm)
+    with nrm float32 [N] = max(||x'||_2, 1e-8), what the backward needs (eps_cos_node_features_nrm; the same xhat)."""
     dev = _need_gpu(rowptr, col, val, x, row_strided=(x,))
     _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val"); _chk(x, torch.float32, "x")
     n = rowptr.numel() - 1
@@ -1040,6 +1041,11 @@ def cos_node_features(rowptr, col, val, x: torch.Tensor) -> torch.Tensor:
     buf = torch.empty((n, ldh), dtype=torch.float32, device=dev)
     ldx = x.stride(0) if n > 1 else max(f, x.stride(0))
     with torch.cuda.device(dev):
+        if want_norm:
+            nrm = torch.empty(n, dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().eps_cos_node_features_nrm(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(x), ldx, f, _ptr(buf),
+                                                             ldh, _ptr(nrm), _stream(dev)), "eps_cos_node_features_nrm")
+            return buf[:, :f], nrm
         _lib.check(_lib.load().eps_cos_node_features(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(x), ldx, f, _ptr(buf), ldh,
                                                      _stream(dev)), "eps_cos_node_features")
     return buf[:, :f]
@@ -1065,6 +1071,61 @@ def edge_cosines(rowptr, col, xhat: torch.Tensor, revpos: Optional[torch.Tensor]
         _lib.check(_lib.load().eps_edge_cosines(_ptr(rowptr), _ptr(col), n, _ptr(xhat), ldh, f, _ptr(revpos), _ptr(out),
                                                 _stream(dev)), "eps_edge_cosines")
     return out
+
+
+def pair_cn_backward(rowptr, col, c: torch.Tensor, u, v, g: torch.Tensor) -> torch.Tensor:
+    """gc float32[nnz]: the gradient of L w.r.t. the edge cosines ``c`` given g[p] = dL/draw_p of the edge-valued
+    common-neighbour sums raw_p = sum_w c[(u_p, w)] c[(v_p, w)] (eps_pair_cn_backward).  Order-independent: the same inputs --
+    in any order of the pair list -- give the same bits."""
+    dev = _need_gpu(rowptr, col, c, u, v, g)
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(c, torch.float32, "c")
+    _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v"); _chk(g, torch.float32, "g")
+    if c.numel() != col.numel():
+        raise _lib.EpsError("pair_cn_backward: c and col differ in length")
+    if u.numel() != v.numel() or g.numel() != u.numel():
+        raise _lib.EpsError("pair_cn_backward: u, v and g differ in length")
+    n, nnz = rowptr.numel() - 1, col.numel()
+    gc = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if nnz == 0:
+        return gc
+    lib = _lib.load()
+    ws_bytes = int(lib.eps_pair_cn_backward_workspace_bytes(nnz))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.eps_pair_cn_backward(_ptr(rowptr), _ptr(col), _ptr(c), n, nnz, _ptr(u), _ptr(v), _ptr(g), u.numel(),
+                                            _ptr(gc), _ptr(ws), ws_bytes, _stream(dev)), "eps_pair_cn_backward")
+    return gc
+
+
+def cos_features_backward(rowptr, col, val, xhat: torch.Tensor, nrm: torch.Tensor, revpos: torch.Tensor, gc: torch.Tensor,
+                          want_scaled: bool = False):
+    """gxp float32 [N, F]: the gradient w.r.t. the smoothed features x' given ``gc`` = dL/dc per stored entry
+    (eps_cos_features_backward): through c[e] = xhat_row(e) . xhat_col(e) and xhat = x' / max(||x'||, 1e-8).  ``xhat``,
+    ``nrm``: ``cos_node_features(..., want_norm=True)``; ``revpos``: scan.reverse_positions of the SYMMETRIC pattern.
+    ``want_scaled``: -> (gxp, gxp / (rowsum(A) + 1e-6)), the second being what the smoothing's backward multiplies by A.
+    Both are views of buffers with 128-byte aligned rows and zero pad columns."""
+    dev = _need_gpu(rowptr, col, val, xhat, nrm, revpos, gc, row_strided=(xhat,))
+    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
+    _chk(xhat, torch.float32, "xhat"); _chk(nrm, torch.float32, "nrm"); _chk(revpos, torch.int32, "revpos"); _chk(gc, torch.float32, "gc")
+    n = rowptr.numel() - 1
+    if xhat.dim() != 2 or xhat.shape[0] != n or nrm.numel() != n:
+        raise _lib.EpsError(f"cos_features_backward: xhat must be [{n}, F] and nrm [{n}], got {tuple(xhat.shape)} and {tuple(nrm.shape)}")
+    if revpos is None or revpos.numel() != col.numel() or gc.numel() != col.numel():
+        raise _lib.EpsError("cos_features_backward: revpos, gc and col differ in length")
+    if val is not None and val.numel() != col.numel():
+        raise _lib.EpsError("cos_features_backward: val and col differ in length")
+    f = int(xhat.shape[1])
+    ldh = xhat.stride(0) if n > 1 else max(f, xhat.stride(0))
+    if f < 1 or ldh % 4 or xhat.data_ptr() % 16:
+        raise _lib.EpsError("cos_features_backward: xhat needs 16-byte aligned rows of at least one column (cos_node_features output)")
+    ldg = (f + COS_ROW_FLOATS - 1) // COS_ROW_FLOATS * COS_ROW_FLOATS
+    gxp = torch.empty((n, ldg), dtype=torch.float32, device=dev)
+    gxs = torch.empty((n, ldg), dtype=torch.float32, device=dev) if want_scaled else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().eps_cos_features_backward(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(xhat), ldh, f, _ptr(nrm),
+                                                         _ptr(revpos), _ptr(gc), _ptr(gxp), _ptr(gxs), ldg, _stream(dev)),
+                   "eps_cos_features_backward")
+    return (gxp[:, :f], gxs[:, :f]) if want_scaled else gxp[:, :f]
 
 
 def gcn_norm(rowptr, col, val) -> torch.Tensor:

@@ -54,6 +54,7 @@ def make_parser():
     # extensions
     parser.add_argument('--synthetic', action="store_true", default=False)
     parser.add_argument('--load_model', type=str, default="")
+    parser.add_argument('--train_cosine', action="store_true", default=False)   # train mlpcos's embedding (see run())
     return parser
 
 
@@ -195,11 +196,11 @@ def _print_epoch(results, run_i: int, epoch: int, loss: float) -> None:
 def run(args):
     args = default_model_configs(args)
     print(args)
-    if args.model == 'mlpcos' and not args.load_model:
-        # (before any data is generated: the run would otherwise fail at its first backward)
-        raise NotImplementedError("rank.py --model mlpcos trains its embedding through the cosine scores; that backward "
-                                  "is not implemented (mlpcos is supported for scoring: filter.py, or rank.py with "
-                                  "--load_model <state_dict.pt>)")
+    if args.model == 'mlpcos' and not args.load_model and not getattr(args, 'train_cosine', False):
+        # (before any data is generated.  Training mlpcos is opt-in: the bare command keeps the refusal it always had)
+        raise NotImplementedError("rank.py --model mlpcos trains its embedding through the cosine scores: pass --train_cosine "
+                                  "to train it here (Adam on emb.weight, like the reference), or --load_model "
+                                  "<state_dict.pt> to score a trained checkpoint")
     if not torch.cuda.is_available():
         raise RuntimeError("rank stage needs a HIP device: the scoring path has no CPU fallback")
     device = torch.device(f'cuda:{args.device}')

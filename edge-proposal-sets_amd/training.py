@@ -1,4 +1,5 @@
-"""Training loop of the rank stage (train_and_eval.py:31-96), for the GCN / SAGE + LinkPredictor and DEA_GNN_JK models.
+"""Training loop of the rank stage (train_and_eval.py:31-96), for the GCN / SAGE + LinkPredictor and DEA_GNN_JK models and the
+cosine common-neighbour models with an embedding (mlpcos: the gradient reaches emb.weight through csrc/cosine_cn_bwd.hip).
 
 Outside the scored hot path but needed to produce the checkpoints filter.py consumes and to
 run rank.py with a parametrised model: torch autograd drives it, the GNN aggregate is the HIP SpMM (custom autograd

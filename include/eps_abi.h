@@ -675,6 +675,35 @@ int eps_cos_node_features(const int64_t *rowptr, const int32_t *col, const float
 int eps_edge_cosines(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const float *xhat, int64_t ldh,
                      int32_t f, const int32_t *revpos, float *c, void *stream);
 
+/* ---- ... and its backward, for training the embedding through the raw score (csrc/cosine_cn_bwd.hip) ---------------------
+ * raw_p = sum_{w in N(u_p) & N(v_p)} c[(u_p, w)] * c[(v_p, w)]; with g_p = dL/draw_p the gradient reaches x in three steps:
+ *   eps_cos_node_features_nrm:  eps_cos_node_features that also writes nrm[r] = max(||x'_r||_2, 1e-8) (float32 [n_rows]),
+ *                               which the backward needs; xhat is the same, bit for bit.
+ *   eps_pair_cn_backward:       gc[e] (float32 [nnz], aligned with col) = sum over the pairs p and their common neighbours w
+ *                               of g_p * c[(v_p, w)] at e = (u_p, w) and g_p * c[(u_p, w)] at e = (v_p, w); a pair with
+ *                               u == v adds both terms to the same entry, entries no pair reaches get 0.  c: the edge cosines
+ *                               (|c| <= 2 is assumed).  The sums are 64-bit fixed-point integer atomics at a scale taken from
+ *                               max |g_p| on the device (each term keeps >= 59 - ceil(log2(2 n_pairs)) bits below that
+ *                               maximum), so gc is bit-identical from run to run and under any reordering of the pair
+ *                               list.  Pairs with an id outside [0, n_rows) add nothing.  workspace: device memory, 8-byte
+ *                               aligned, eps_pair_cn_backward_workspace_bytes(nnz) bytes; its contents need not survive.
+ *   eps_cos_features_backward:  gxp[r] = (a_r - xhat_r (xhat_r . a_r)) / nrm[r], a_r = sum_{e = (r, w)} (gc[e] + gc[rev(e)])
+ *                               xhat_w, rev(e) = rowptr[w] + revpos[e]; rows whose nrm is the clamp (<= 1e-8) get
+ *                               a_r / 1e-8.  Always finite for finite inputs.  Needs a SYMMETRIC pattern and its revpos
+ *                               (eps_reverse_positions).  gxs (or NULL) receives gxp[r] / (rowsum(A)_r + 1e-6) -- A's values, or
+ *                               ones for val == NULL -- so that the smoothing's backward is gx = gxp + A @ gxs (eps_spmm_csr;
+ *                               symmetric values).  xhat as eps_cos_node_features writes it; gxp / gxs float32 [n_rows x ldg],
+ *                               ldg >= f, ldg % 4 == 0, 16-byte aligned; their columns [f, ldg) are written 0. */
+int eps_cos_node_features_nrm(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                              const float *x, int64_t ldx, int32_t f, float *xhat, int64_t ldh, float *nrm, void *stream);
+int64_t eps_pair_cn_backward_workspace_bytes(int64_t nnz);
+int eps_pair_cn_backward(const int64_t *rowptr, const int32_t *col, const float *c, int64_t n_rows, int64_t nnz,
+                         const int32_t *u, const int32_t *v, const float *g, int64_t n_pairs, float *gc, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int eps_cos_features_backward(const int64_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                              const float *xhat, int64_t ldh, int32_t f, const float *nrm, const int32_t *revpos,
+                              const float *gc, float *gxp, float *gxs, int64_t ldg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
