@@ -29,10 +29,14 @@ from . import heuristics
 
 class _SpMM(torch.autograd.Function):
     """Differentiable CSR x dense aggregate for TRAINING (train_and_eval.py:31-96): forward and backward both run
-    eps_spmm_csr.  The adjacency must be structurally symmetric with symmetric values (every adjacency the reference
-    builds is: rank.py:33), so the transposed product of the backward pass is a product with the same matrix:
-      sum : Y = A X          ->  dX = A dY
-      mean: Y = D^-1 A X     ->  dX = A (D^-1 dY)        (unit values)"""
+    eps_spmm_csr.  The gradient of Y = A X is dX = A^T dY; the backward multiplies by A itself, which is that gradient only
+    when A equals its transpose:
+      sum : Y = A X          ->  dX = A dY               (pattern AND values symmetric)
+      mean: Y = D^-1 P X     ->  dX = P (D^-1 dY)        (P the pattern, symmetric; values are not read)
+    Every adjacency the reference builds is symmetric (rank.py:33), and the convs refuse any other one in training mode
+    (``_check_trainable``) BEFORE they get here: this Function itself checks nothing.  The normalised copies the convs pass
+    (graph.gcn_normalized / tag_normalized) hold (val * dis[r]) * dis[c], so their mirrored entries can differ in the last
+    bit; that is rounding of the same size as the product's own and is accepted."""
 
     @staticmethod
     def forward(ctx, x, graph, mean):
@@ -67,6 +71,26 @@ def _pad4(x: torch.Tensor) -> torch.Tensor:
     return _pad4_full(x)[0]
 
 
+def _check_rows(x: torch.Tensor, adj_t: CSRGraph, who: str) -> None:
+    """The SpMM gathers x[col] unchecked: x must have one row per column of the adjacency."""
+    if x.dim() != 2 or x.shape[0] != adj_t.n_cols:
+        raise ValueError(f"{who}: x must have one row per column of the adjacency ({adj_t.n_cols}), got {tuple(x.shape)}")
+
+
+def _check_trainable(adj_t: CSRGraph, who: str, values: bool) -> None:
+    """Training through _SpMM needs the adjacency THE CALLER PASSED to equal its transpose: its pattern, and for the convs
+    that read them (``values``) its stored values.  (Not the normalised copy: that one is symmetric only up to a rounding.)
+    Both verdicts are cached on the graph, so only the first step pays for them."""
+    from . import scan
+    from ._lib import EpsError
+    if adj_t.n_rows != adj_t.n_cols or not scan.is_symmetric(adj_t):
+        raise EpsError(f"{who}: training needs an adjacency with a symmetric pattern (the backward multiplies by A in "
+                       f"place of A^T); scoring under eval() / no_grad() takes any graph")
+    if values and not heuristics.values_are_symmetric(adj_t):
+        raise EpsError(f"{who}: training needs an adjacency with symmetric values (the backward multiplies by A in place "
+                       f"of A^T); scoring under eval() / no_grad() takes any graph")
+
+
 # ----------------------------------------------------------------------------------- convs
 class GCNConv(torch.nn.Module):
     """torch_geometric 1.7.0 GCNConv [third-party, restated]: out = D^-1/2 (A with diag := 1) D^-1/2 (x W) + b.
@@ -93,8 +117,12 @@ class GCNConv(torch.nn.Module):
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def forward(self, x: torch.Tensor, adj_t: CSRGraph, relu: bool = False) -> torch.Tensor:
+        _check_rows(x, adj_t, "GCNConv")
+        training = torch.is_grad_enabled() and self.training
+        if training:
+            _check_trainable(adj_t, "GCNConv", values=True)
         gn = adj_t.gcn_normalized()                      # cached per adjacency (eps_gcn_norm)
-        if torch.is_grad_enabled() and self.training:    # training: HIP SpMM inside autograd, dense part on torch
+        if training:                                     # training: HIP SpMM inside autograd, dense part on torch
             out = _SpMM.apply(x @ self.weight, gn, False) + self.bias
             return F.relu(out) if relu else out
         with torch.no_grad():
@@ -109,6 +137,7 @@ class GCNConv(torch.nn.Module):
     @torch.no_grad()
     def forward_rows(self, x: torch.Tensor, adj_t: CSRGraph, lo: int, hi: int, relu: bool = False) -> torch.Tensor:
         """Rows [lo, hi) of the layer output from the FULL input (multi-GPU row sharding, dist.py)."""
+        _check_rows(x, adj_t, "GCNConv")
         return self._forward_hip(x, adj_t.gcn_normalized(), relu, rows=(lo, hi))
 
     def __repr__(self):
@@ -131,7 +160,9 @@ class SAGEConv(torch.nn.Module):
         self.lin_r.reset_parameters()
 
     def forward(self, x: torch.Tensor, adj_t: CSRGraph, relu: bool = False) -> torch.Tensor:
+        _check_rows(x, adj_t, "SAGEConv")
         if torch.is_grad_enabled() and self.training:
+            _check_trainable(adj_t, "SAGEConv", values=False)     # the mean reads the pattern only
             out = self.lin_l(_SpMM.apply(x, adj_t, True)) + self.lin_r(x)
             return F.relu(out) if relu else out
         with torch.no_grad():
@@ -158,6 +189,7 @@ class SAGEConv(torch.nn.Module):
     @torch.no_grad()
     def forward_rows(self, x: torch.Tensor, adj_t: CSRGraph, lo: int, hi: int, relu: bool = False) -> torch.Tensor:
         """Rows [lo, hi) of the layer output from the FULL input (multi-GPU row sharding, dist.py)."""
+        _check_rows(x, adj_t, "SAGEConv")
         return self._forward_hip(x, adj_t, relu, rows=(lo, hi))
 
     def __repr__(self):
@@ -367,17 +399,26 @@ class TAGConv(torch.nn.Module):
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def forward(self, x: torch.Tensor, adj_t: CSRGraph) -> torch.Tensor:
-        """Training (autograd): the hops through the HIP SpMM Function (A^ is symmetric, so its backward holds)."""
+        """Training mode with grad enabled: the hops through the HIP SpMM Function (a symmetric adjacency is required: A^ is
+        then symmetric, so its backward holds).  Otherwise the same hops without autograd."""
+        _check_rows(x, adj_t, "TAGConv")
+        training = torch.is_grad_enabled() and self.training
+        if training:
+            _check_trainable(adj_t, "TAGConv", values=True)
         an = adj_t.tag_normalized()
         xs = [x]
         for _ in range(self.K):
-            xs.append(_SpMM.apply(xs[-1], an, False))
+            if training:
+                xs.append(_SpMM.apply(xs[-1], an, False))
+            else:       # eval() / no_grad(): any graph; no gradient reaches x through the hops (like GCNConv / SAGEConv)
+                xs.append(ops.spmm_csr(an.rowptr, an.col, an.val, xs[-1].detach().contiguous()))
         return self.lin(torch.cat(xs, 1))
 
     @torch.no_grad()
     def hops(self, x: torch.Tensor, an: CSRGraph) -> torch.Tensor:
         """[x || A^ x || ... || A^K x] in ONE [N, (K + 1) * k4] buffer (k4 = in rounded up to 4 floats, zero pad columns:
         every block starts 16-byte aligned); each hop is an SpMM from the previous block into the next."""
+        _check_rows(x, an, "TAGConv")
         n, k = x.shape
         k4 = (k + 3) // 4 * 4
         buf = (torch.empty if k4 == k else torch.zeros)((n, (self.K + 1) * k4), dtype=torch.float32, device=x.device)

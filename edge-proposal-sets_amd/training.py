@@ -17,7 +17,7 @@ def negative_sampling(edge_index: torch.Tensor, num_nodes: int, num_neg_samples:
     that are NOT edges of ``edge_index`` (rejection against the sorted edge keys)."""
     dev = edge_index.device
     keys = torch.unique(edge_index[0] * num_nodes + edge_index[1])
-    out = []
+    out = [torch.zeros(0, dtype=torch.int64, device=dev)]      # (a request for 0 pairs returns [2, 0])
     have = 0
     while have < num_neg_samples:
         n = int((num_neg_samples - have) * 1.2) + 16
