@@ -1,9 +1,10 @@
 """Thin torch-tensor wrappers over the C ABI (include/eps_abi.h).  Every function requires its
 tensors on a HIP device and launches on torch's current stream; nothing here computes on the
-CPU."""
+CPU.  Every launch goes through ``_call``; host-only queries (workspace sizes, table geometry) are plain calls."""
 from __future__ import annotations
 
 import ctypes
+import struct
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -12,8 +13,26 @@ from . import _lib
 
 W_AA, W_RA = 0, 1
 
+KERNEL_EVENTS = None      # a list while bench.py times kernels: (kernel name, start event, end event, work size) per launch
+EVENT_NAMES = None        # None: every library call is bracketed while KERNEL_EVENTS is a list; a collection of names: only those (the
+                          # scan launches always are) -- bench.py's timed region carries the dominant kernel's events alone
+_SCAN_EVENTS = ("scan_piece_kernel", "filter_scan_kernel")
 
-_EMPTY = {}
+_SCRATCH = {}
+
+
+def _scratch(name, dev, n_words: int, alloc, zero: bool = False) -> torch.Tensor:
+    """The grow-only int64 buffer ``name`` of a device, at least ``n_words`` long; when it has to grow it is replaced by one of
+    ``alloc`` words (an int, or a callable that gives it), the old buffer let go BEFORE the larger one is allocated.
+    Stream-ordered like any other tensor on the current stream, so one buffer must not serve launches on several streams at once."""
+    key = (name, dev.type, dev.index)
+    buf = _SCRATCH.get(key)
+    if buf is None or buf.numel() < n_words:
+        _SCRATCH.pop(key, None)
+        buf = None
+        make = torch.zeros if zero else torch.empty
+        buf = _SCRATCH[key] = make(alloc() if callable(alloc) else alloc, dtype=torch.int64, device=dev)
+    return buf
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -22,15 +41,28 @@ def _ptr(t: Optional[torch.Tensor]):
     if t is None:
         return None
     if t.numel() == 0 and t.is_cuda:
-        key = (t.device.type, t.device.index)
-        if key not in _EMPTY:
-            _EMPTY[key] = torch.zeros(8, dtype=torch.int64, device=t.device)
-        return ctypes.c_void_p(_EMPTY[key].data_ptr())
+        return ctypes.c_void_p(_scratch("empty", t.device, 8, 8, zero=True).data_ptr())
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _stream(dev: torch.device):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+def _call(name: str, dev: torch.device, *args, timed=None) -> None:
+    """The one way into the library for everything that launches: ``name`` is the exported symbol, resolved on the loaded library
+    and reported in the EpsError of a failed call; tensors among ``args`` go as their device pointers (``_ptr``), everything else
+    (ints, floats, None, ctypes values, raw device addresses) as it is; the current stream of ``dev`` is appended.
+    ``timed`` = (event name, work size): HIP events around the call on its stream while bench.py collects KERNEL_EVENTS."""
+    fn = getattr(_lib.load(), name)
+    args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ev = None
+        if timed is not None and KERNEL_EVENTS is not None and (
+                EVENT_NAMES is None or timed[0] in EVENT_NAMES or timed[0] in _SCAN_EVENTS):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record(stream)
+        _lib.check(fn(*args, ctypes.c_void_p(stream.cuda_stream)), name)
+        if ev is not None:
+            ev[1].record(stream)
+            KERNEL_EVENTS.append((timed[0], ev[0], ev[1], int(timed[1])))
 
 
 def _need_gpu(*tensors: Optional[torch.Tensor], row_strided=()) -> torch.device:
@@ -57,9 +89,19 @@ def _need_gpu(*tensors: Optional[torch.Tensor], row_strided=()) -> torch.device:
     return dev
 
 
-def _chk(t: Optional[torch.Tensor], dtype: torch.dtype, name: str):
-    if t is not None and t.dtype != dtype:
-        raise _lib.EpsError(f"{name}: expected {dtype}, got {t.dtype}")
+_I16, _I32, _I64, _F32, _F64 = torch.int16, torch.int32, torch.int64, torch.float32, torch.float64
+
+
+def _chk(dtype: torch.dtype, **named) -> None:
+    """``_chk(_I32, u=u, v=v)``: every named tensor has that dtype (None, and a device count given as a raw address, pass)."""
+    for name, t in named.items():
+        if isinstance(t, torch.Tensor) and t.dtype != dtype:
+            raise _lib.EpsError(f"{name}: expected {dtype}, got {t.dtype}")
+
+
+def _csr(rowptr, col, val=None, sfx: str = "") -> None:
+    """The dtypes of a CSR triple: rowptr int64, col int32, val float32 (or None)."""
+    _chk(_I64, **{"rowptr" + sfx: rowptr}); _chk(_I32, **{"col" + sfx: col}); _chk(_F32, **{"val" + sfx: val})
 
 
 def device_info() -> Tuple[int, str]:
@@ -73,25 +115,21 @@ def device_info() -> Tuple[int, str]:
 def col_sums(rowptr, col, val, n_cols: int, f64: bool = False) -> torch.Tensor:
     """Column sums, accumulated in float64 on the device; returned as float32 (rounded once) or, ``f64=True``, as is."""
     dev = _need_gpu(rowptr, col, val)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
+    _csr(rowptr, col, val)
     if col.numel() == 0:                        # a graph without entries (its col[] has no storage to point at)
-        return torch.zeros(n_cols, dtype=torch.float64 if f64 else torch.float32, device=dev)
-    wide = torch.empty(n_cols, dtype=torch.float64, device=dev)
-    out = None if f64 else torch.empty(n_cols, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_col_sums(_ptr(rowptr), _ptr(col), _ptr(val), rowptr.numel() - 1, n_cols,
-                                            _ptr(wide), _ptr(out), _stream(dev)), "eps_col_sums")
+        return torch.zeros(n_cols, dtype=_F64 if f64 else _F32, device=dev)
+    wide = torch.empty(n_cols, dtype=_F64, device=dev)
+    out = None if f64 else torch.empty(n_cols, dtype=_F32, device=dev)
+    _call("eps_col_sums", dev, rowptr, col, val, rowptr.numel() - 1, n_cols, wide, out)
     return wide if f64 else out
 
 
 def node_weights(colsum: torch.Tensor, mode: int, f64: bool = False) -> torch.Tensor:
     """1/log(colsum) (AA) or 1/colsum (RA), inf -> 0: float32 from float32 sums, or float64 from float64 sums."""
     dev = _need_gpu(colsum)
-    _chk(colsum, torch.float64 if f64 else torch.float32, "colsum")
-    out = torch.empty(colsum.numel(), dtype=torch.float64 if f64 else torch.float32, device=dev)
-    fn = _lib.load().eps_node_weights_f64 if f64 else _lib.load().eps_node_weights
-    with torch.cuda.device(dev):
-        _lib.check(fn(_ptr(colsum), colsum.numel(), mode, _ptr(out), _stream(dev)), "eps_node_weights")
+    _chk(_F64 if f64 else _F32, colsum=colsum)
+    out = torch.empty(colsum.numel(), dtype=_F64 if f64 else _F32, device=dev)
+    _call("eps_node_weights_f64" if f64 else "eps_node_weights", dev, colsum, colsum.numel(), mode, out)
     return out
 
 
@@ -115,44 +153,37 @@ def pair_scores(rowptr, col, val, node_w, n_nodes: int, u, v, want_count=True, w
     ``grouped``: True -> column-run kernel (pair list sorted by v), False -> generic kernel, None -> decide
     from the run statistics of ``v``.  Results are identical either way."""
     dev = _need_gpu(rowptr, col, val, node_w, u, v)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v")
+    _csr(rowptr, col, val); _chk(_I32, u=u, v=v)
     if u.numel() != v.numel():
         raise _lib.EpsError("u and v differ in length")
     if want_wsum is None:
         want_wsum = node_w is not None
     n = u.numel()
-    lib = _lib.load()
     if grouped is None:
         grouped = v_runs_are_long(v)
-    count = torch.empty(n, dtype=torch.int32, device=dev) if want_count else None
-    with torch.cuda.device(dev):
-        if node_w is not None and node_w.dtype == torch.float64:
-            ws = torch.empty(n, dtype=torch.float64, device=dev) if want_wsum else None
-            fn = lib.eps_pair_scores_grouped_f64 if grouped else lib.eps_pair_scores_f64
-            _lib.check(fn(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, _ptr(u), _ptr(v), n, _ptr(count),
-                          _ptr(ws), _stream(dev)), "eps_pair_scores_f64")
-            return count, None, ws
-        _chk(node_w, torch.float32, "node_w")
-        cn = torch.empty(n, dtype=torch.float32, device=dev) if want_cn else None
-        ws = torch.empty(n, dtype=torch.float32, device=dev) if want_wsum else None
-        fn = lib.eps_pair_scores_grouped if grouped else lib.eps_pair_scores
-        _lib.check(fn(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, _ptr(u), _ptr(v), n, _ptr(count),
-                      _ptr(cn), _ptr(ws), _stream(dev)), "eps_pair_scores")
+    count = torch.empty(n, dtype=_I32, device=dev) if want_count else None
+    if node_w is not None and node_w.dtype == _F64:
+        ws = torch.empty(n, dtype=_F64, device=dev) if want_wsum else None
+        _call("eps_pair_scores_grouped_f64" if grouped else "eps_pair_scores_f64", dev, rowptr, col, val, node_w, n_nodes, u, v,
+              n, count, ws)
+        return count, None, ws
+    _chk(_F32, node_w=node_w)
+    cn = torch.empty(n, dtype=_F32, device=dev) if want_cn else None
+    ws = torch.empty(n, dtype=_F32, device=dev) if want_wsum else None
+    _call("eps_pair_scores_grouped" if grouped else "eps_pair_scores", dev, rowptr, col, val, node_w, n_nodes, u, v, n, count, cn,
+          ws)
     return count, cn, ws
 
 
 def two_path_counts(rowptr, col) -> torch.Tensor:
     """paths[x] = sum over the entries w of row x of the length of row w: the two-paths out of every node (int64)."""
     dev = _need_gpu(rowptr, col)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    _csr(rowptr, col)
     n = rowptr.numel() - 1
     if n < 0:
         raise _lib.EpsError("rowptr must hold at least one entry")
-    out = torch.empty(n, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_two_path_counts(_ptr(rowptr), _ptr(col), n, _ptr(out), _stream(dev)),
-                   "eps_two_path_counts")
+    out = torch.empty(n, dtype=_I64, device=dev)
+    _call("eps_two_path_counts", dev, rowptr, col, n, out)
     return out
 
 
@@ -165,10 +196,8 @@ def katz_pair_scores(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_
     col_t, val_t)`` is A's transpose (A's own tensors when A is symmetric); ``paths_out`` / ``paths_in`` are
     ``two_path_counts`` of A and of A^T."""
     dev = _need_gpu(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_in, u, v)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(rowptr_t, torch.int64, "rowptr_t"); _chk(col_t, torch.int32, "col_t"); _chk(val_t, torch.float32, "val_t")
-    _chk(paths_out, torch.int64, "paths_out"); _chk(paths_in, torch.int64, "paths_in")
-    _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v")
+    _csr(rowptr, col, val); _csr(rowptr_t, col_t, val_t, "_t")
+    _chk(_I64, paths_out=paths_out, paths_in=paths_in); _chk(_I32, u=u, v=v)
     if u.numel() != v.numel():
         raise _lib.EpsError("u and v differ in length")
     if rowptr.numel() != n_nodes + 1 or rowptr_t.numel() != n_nodes + 1:
@@ -179,18 +208,14 @@ def katz_pair_scores(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_
     if len(c) != 3:
         raise _lib.EpsError(f"katz_pair_scores: expected three coefficients, got {len(c)}")
     n = u.numel()
-    out = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(n, dtype=_F32, device=dev)
     if n == 0:
         return out
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty((int(lib.eps_katz_workspace_bytes(min(n, KATZ_CHUNK))) + 7) // 8, dtype=torch.int64, device=dev)
-        for s in range(0, n, KATZ_CHUNK):
-            e = min(n, s + KATZ_CHUNK)
-            _lib.check(lib.eps_katz_pair_scores(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(rowptr_t), _ptr(col_t), _ptr(val_t),
-                                                _ptr(paths_out), _ptr(paths_in), n_nodes, _ptr(u[s:e]), _ptr(v[s:e]), e - s,
-                                                c[0], c[1], c[2], _ptr(ws), _ptr(out[s:e]), _stream(dev)),
-                       "eps_katz_pair_scores")
+    ws = torch.empty((int(_lib.load().eps_katz_workspace_bytes(min(n, KATZ_CHUNK))) + 7) // 8, dtype=_I64, device=dev)
+    for s in range(0, n, KATZ_CHUNK):
+        e = min(n, s + KATZ_CHUNK)
+        _call("eps_katz_pair_scores", dev, rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_in, n_nodes, u[s:e], v[s:e],
+              e - s, c[0], c[1], c[2], ws, out[s:e])
     return out
 
 
@@ -198,23 +223,25 @@ def expand_max_nodes() -> int:
     return int(_lib.load().eps_expand_max_nodes())
 
 
-_EXPAND_WS = {}
-
-
 def _expand_scratch(dev, n_bytes: int) -> torch.Tensor:
     """int64 scratch of the fill kernel (status word + per-workgroup path buckets): one grow-only buffer per device,
-    reused by every block of a filter run (a fresh multi-GB allocation per block costs more than the kernel saves).
-    Stream-ordered like any other tensor on the current stream, so expansions of one device must not run concurrently
-    on several streams."""
-    key = (dev.type, dev.index)
+    reused by every block of a filter run (a fresh multi-GB allocation per block costs more than the kernel saves)."""
     n_words = (n_bytes + 7) // 8
-    buf = _EXPAND_WS.get(key)
-    if buf is None or buf.numel() < n_words:
-        _EXPAND_WS.pop(key, None)
-        buf = None                                   # let the old buffer go before the larger one is allocated
-        buf = torch.empty(int(n_words * 1.25) + 1024, dtype=torch.int64, device=dev)
-        _EXPAND_WS[key] = buf
-    return buf
+    return _scratch("expand", dev, n_words, int(n_words * 1.25) + 1024)
+
+
+def _scan_scratch(dev, max_degree: int) -> torch.Tensor:
+    """Scratch of eps_filter_scan (1 GiB of bucket records on 256 CUs + max_degree weights per workgroup), at its exact size."""
+    need = (int(_lib.load().eps_filter_scan_workspace_bytes(int(max_degree))) + 7) // 8
+    return _scratch("scan", dev, need, need)
+
+
+def _aligned_ws(dev, n_bytes: int):
+    """(tensor, 256-byte aligned pointer, bytes from there) of the grow-only scratch of the sorts and selections."""
+    need = (int(n_bytes) + 7) // 8 + 32
+    ws = _scratch("select", dev, need, int(need * 1.25))
+    off = (-ws.data_ptr()) % 256
+    return ws, ctypes.c_void_p(ws.data_ptr() + off), ws.numel() * 8 - off
 
 
 def max_column_paths(rowptr: torch.Tensor, col: torch.Tensor, v_lo: int, v_hi: int) -> int:
@@ -265,68 +292,52 @@ def expand_unit(rowptr, col, node_w, n_nodes: int, v_lo: int, v_hi: int, max_deg
     (eps_expand_unit_list): no counting launch, no host read before the launch; column v fills the front of its segment, the rest
     of the segment is NOT written, ``.counts`` (int64[n_cols]) holds the real counts and there is no cand_v."""
     dev = _need_gpu(rowptr, col, node_w, col_order, splits, revpos, colptr_ub)
+    _csr(rowptr, col); _chk(_F32, node_w=node_w); _chk(_I32, col_order=col_order, splits=splits, revpos=revpos)
+    _chk(_I64, colptr_ub=colptr_ub)
+    n_cols = v_hi - v_lo
+    if colptr_ub is not None and (total_ub is None or want_v or colptr_ub.numel() != n_cols + 1):
+        raise ValueError("expand_unit: the one-pass list takes colptr_ub[n_cols + 1] + total_ub and writes no cand_v")
+    if col_order is not None and col_order.numel() != n_cols:
+        raise ValueError("col_order must have one entry per column of the range")
+    ws = _scan_scratch(dev, int(max_degree))
+    counts = torch.zeros(n_cols, dtype=_I64, device=dev)
+
+    def fixw():
+        if not want_score:
+            return None
+        return fixed_weights(node_w if node_w is not None else torch.ones(n_nodes, dtype=_F32, device=dev))
+
+    graph = (n_nodes, col.numel(), int(max_degree), v_lo, v_hi, col_order)
     if colptr_ub is not None:
-        _chk(colptr_ub, torch.int64, "colptr_ub")
-        if total_ub is None or want_v or colptr_ub.numel() != v_hi - v_lo + 1:
-            raise ValueError("expand_unit: the one-pass list takes colptr_ub[n_cols + 1] + total_ub and writes no cand_v")
-        _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(node_w, torch.float32, "node_w")
-        _chk(col_order, torch.int32, "col_order"); _chk(splits, torch.int32, "splits"); _chk(revpos, torch.int32, "revpos")
-        if col_order is not None and col_order.numel() != v_hi - v_lo:
-            raise ValueError("col_order must have one entry per column of the range")
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            ws = _scan_scratch(dev, int(max_degree))
-            counts = torch.zeros(v_hi - v_lo, dtype=torch.int64, device=dev)
-            cand_u = torch.empty(int(total_ub), dtype=torch.int32, device=dev)
-            score = torch.empty(int(total_ub), dtype=torch.float32, device=dev) if want_score else None
-            status = torch.zeros(1, dtype=torch.int32, device=dev)       # (the call clears it itself; an empty range makes no call)
-            fixw = None
-            if want_score:
-                fixw = fixed_weights(node_w if node_w is not None else torch.ones(n_nodes, dtype=torch.float32, device=dev))
-            if v_hi > v_lo:
-                _lib.check(lib.eps_expand_unit_list(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(fixw), _ptr(splits), n_nodes, col.numel(),
-                                                    int(max_degree), v_lo, v_hi, _ptr(col_order), _ptr(colptr_ub), _ptr(counts),
-                                                    _ptr(cand_u), _ptr(score), _ptr(status), _ptr(ws), ws.numel() * 8, _stream(dev)),
-                           "eps_expand_unit_list")
+        cand_u = torch.empty(int(total_ub), dtype=_I32, device=dev)
+        score = torch.empty(int(total_ub), dtype=_F32, device=dev) if want_score else None
+        status = torch.zeros(1, dtype=_I32, device=dev)       # (the call clears it itself; an empty range makes no call)
+        fw = fixw()
+        if n_cols > 0:
+            _call("eps_expand_unit_list", dev, rowptr, col, revpos, fw, splits, *graph, colptr_ub, counts, cand_u, score, status,
+                  ws, ws.numel() * 8)
         out = ExpandResult((colptr_ub, cand_u, None, None, score))
         out.counts = counts
         out.status = status           # (device word: bit 1 = a bound was too small, bit 2 = a sum left the fixed-point range)
         return out
-    _chk(revpos, torch.int32, "revpos")
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(node_w, torch.float32, "node_w")
-    _chk(col_order, torch.int32, "col_order"); _chk(splits, torch.int32, "splits")
-    lib = _lib.load()
-    n_cols = v_hi - v_lo
-    if col_order is not None and col_order.numel() != n_cols:
-        raise ValueError("col_order must have one entry per column of the range")
-    with torch.cuda.device(dev):
-        ws = _scan_scratch(dev, int(max_degree))
-        counts = torch.zeros(n_cols, dtype=torch.int64, device=dev)
-        colptr = torch.zeros(n_cols + 1, dtype=torch.int64, device=dev)
-        if n_cols:
-            _lib.check(lib.eps_expand_unit_count(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(splits), n_nodes, col.numel(), int(max_degree),
-                                                 v_lo, v_hi, _ptr(col_order), _ptr(counts), _ptr(ws), ws.numel() * 8,
-                                                 _stream(dev)), "eps_expand_unit_count")
-        torch.cumsum(counts, 0, out=colptr[1:])
-        total = int(colptr[-1].item())
-        pairs = torch.empty((2 if want_v else 1, total), dtype=torch.int32, device=dev)
-        score = torch.empty(total, dtype=torch.float32, device=dev) if want_score else None
-        if total:
-            fixw = None
-            if want_score:
-                fixw = fixed_weights(node_w if node_w is not None else torch.ones(n_nodes, dtype=torch.float32, device=dev))
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.eps_expand_unit_fill(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(fixw), _ptr(splits), n_nodes, col.numel(),
-                                                int(max_degree), v_lo, v_hi, _ptr(col_order), _ptr(colptr), None,
-                                                _ptr(pairs[0]), _ptr(pairs[1]) if want_v else None, _ptr(score), _ptr(status),
-                                                _ptr(ws), ws.numel() * 8, _stream(dev)), "eps_expand_unit_fill")
-            st = int(status.item())
-            if st:
-                raise _lib.EpsError("expand_unit: " + ("a column outgrew its segment; " if st & 2 else "")
-                                    + ("a score left the fixed-point range (|sum| >= 2**23): use the pair kernels" if st & 4 else ""))
+    colptr = torch.zeros(n_cols + 1, dtype=_I64, device=dev)
+    if n_cols:
+        _call("eps_expand_unit_count", dev, rowptr, col, revpos, splits, *graph, counts, ws, ws.numel() * 8)
+    torch.cumsum(counts, 0, out=colptr[1:])
+    total = int(colptr[-1].item())
+    pairs = torch.empty((2 if want_v else 1, total), dtype=_I32, device=dev)
+    score = torch.empty(total, dtype=_F32, device=dev) if want_score else None
+    if total:
+        fw = fixw()
+        status = torch.zeros(1, dtype=_I32, device=dev)
+        _call("eps_expand_unit_fill", dev, rowptr, col, revpos, fw, splits, *graph, colptr, None, pairs[0],
+              pairs[1] if want_v else None, score, status, ws, ws.numel() * 8)
+        st = int(status.item())
+        if st:
+            raise _lib.EpsError("expand_unit: " + ("a column outgrew its segment; " if st & 2 else "")
+                                + ("a score left the fixed-point range (|sum| >= 2**23): use the pair kernels" if st & 4 else ""))
     out = ExpandResult((colptr, pairs[0], pairs[1] if want_v else None, None, score))
     out.pairs = pairs if want_v else None
-    out.counts = None
     return out
 
 
@@ -354,59 +365,54 @@ def expand_candidates(rowptr, col, val, node_w, n_nodes: int, v_lo: int, v_hi: i
     ``signed``: the terms may be negative (edge cosines, eps_expand_fill_signed): the kernel does not flag negative sums;
     the caller must have checked the range (candidates.fused_scores_fit)."""
     dev = _need_gpu(rowptr, col, val, node_w, col_order, colptr_ub)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(node_w, torch.float32, "node_w"); _chk(col_order, torch.int32, "col_order"); _chk(colptr_ub, torch.int64, "colptr_ub")
+    _csr(rowptr, col, val); _chk(_F32, node_w=node_w); _chk(_I32, col_order=col_order); _chk(_I64, colptr_ub=colptr_ub)
     lib = _lib.load()
     n_cols = v_hi - v_lo
     if col_order is not None and col_order.numel() != n_cols:
         raise ValueError("col_order must have one entry per column of the range")
     if colptr_ub is not None and (colptr_ub.numel() != n_cols + 1 or total_ub is None):
         raise ValueError("colptr_ub needs n_cols + 1 entries and total_ub")
-    with torch.cuda.device(dev):
-        counts = torch.empty(n_cols, dtype=torch.int64, device=dev)
-        if colptr_ub is None:
-            colptr = torch.zeros(n_cols + 1, dtype=torch.int64, device=dev)
-            _lib.check(lib.eps_expand_count(_ptr(rowptr), _ptr(col), n_nodes, v_lo, v_hi, _ptr(col_order), _ptr(counts),
-                                            _stream(dev)), "eps_expand_count")
-            torch.cumsum(counts, 0, out=colptr[1:])
-            total = int(colptr[-1].item())
+    counts = torch.empty(n_cols, dtype=_I64, device=dev)
+    if colptr_ub is None:
+        colptr = torch.zeros(n_cols + 1, dtype=_I64, device=dev)
+        _call("eps_expand_count", dev, rowptr, col, n_nodes, v_lo, v_hi, col_order, counts)
+        torch.cumsum(counts, 0, out=colptr[1:])
+        total = int(colptr[-1].item())
+    else:
+        colptr, total = colptr_ub, int(total_ub)
+    pairs = torch.empty((2 if want_v else 1, total), dtype=_I32, device=dev)
+    cand_u = pairs[0]
+    cand_v = pairs[1] if want_v else None
+    cn = torch.empty(total, dtype=_I32, device=dev) if want_cn else None
+    score = torch.empty(total, dtype=_F32, device=dev) if want_score else None
+    cut_rec = cut_pos = cut_val = None
+    if cut is not None and total:
+        thr, cap = float(cut[0]), int(cut[1])
+        cut_pos = torch.empty(cap, dtype=_I64, device=dev)
+        cut_val = torch.empty(cap, dtype=_F32, device=dev)
+        head = struct.unpack("<q", struct.pack("<fI", thr, cap))[0]          # eps_score_cut: threshold, capacity
+        cut_rec = torch.tensor([head, 0, cut_pos.data_ptr(), cut_val.data_ptr()], dtype=_I64, device=dev)
+    scored = want_cn or want_score or cut_rec is not None
+    if total:
+        if max_paths is None:
+            max_paths = max_column_paths(rowptr, col, v_lo, v_hi) if scored else 0
+        ws_bytes = int(lib.eps_expand_workspace_bytes(int(max_paths) if scored else 0))
+        if ws_bytes > _EXPAND_WS_LIMIT:
+            raise _lib.EpsError(f"expand_candidates: a column with {max_paths} two-hop paths needs {ws_bytes >> 30} GiB "
+                                "of bucket scratch; score such graphs with the pair kernels")
+        ws = _expand_scratch(dev, ws_bytes)
+        _call("eps_expand_fill_signed" if signed else "eps_expand_fill_tiled", dev, rowptr, col, val, node_w, n_nodes, v_lo, v_hi,
+              col_order, colptr, counts if colptr_ub is not None else None, cand_u, cand_v, cn, score, cut_rec, ws, ws_bytes,
+              int(tile_ranks))
+        if cut_rec is not None:                      # one read-back for the status word and the survivor count
+            both = torch.stack([ws[0], cut_rec[1]]).tolist()
+            status, n_cut = both[0] & 0xFFFFFFFF, both[1] & 0xFFFFFFFF
         else:
-            colptr, total = colptr_ub, int(total_ub)
-        pairs = torch.empty((2 if want_v else 1, total), dtype=torch.int32, device=dev)
-        cand_u = pairs[0]
-        cand_v = pairs[1] if want_v else None
-        cn = torch.empty(total, dtype=torch.int32, device=dev) if want_cn else None
-        score = torch.empty(total, dtype=torch.float32, device=dev) if want_score else None
-        cut_rec = cut_pos = cut_val = None
-        if cut is not None and total:
-            thr, cap = float(cut[0]), int(cut[1])
-            cut_pos = torch.empty(cap, dtype=torch.int64, device=dev)
-            cut_val = torch.empty(cap, dtype=torch.float32, device=dev)
-            import struct
-            head = struct.unpack("<q", struct.pack("<fI", thr, cap))[0]          # eps_score_cut: threshold, capacity
-            cut_rec = torch.tensor([head, 0, cut_pos.data_ptr(), cut_val.data_ptr()], dtype=torch.int64, device=dev)
-        scored = want_cn or want_score or cut_rec is not None
-        if total:
-            if max_paths is None:
-                max_paths = max_column_paths(rowptr, col, v_lo, v_hi) if scored else 0
-            ws_bytes = int(lib.eps_expand_workspace_bytes(int(max_paths) if scored else 0))
-            if ws_bytes > _EXPAND_WS_LIMIT:
-                raise _lib.EpsError(f"expand_candidates: a column with {max_paths} two-hop paths needs {ws_bytes >> 30} GiB "
-                                    "of bucket scratch; score such graphs with the pair kernels")
-            ws = _expand_scratch(dev, ws_bytes)
-            fill = lib.eps_expand_fill_signed if signed else lib.eps_expand_fill_tiled
-            _lib.check(fill(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, v_lo, v_hi, _ptr(col_order), _ptr(colptr),
-                            _ptr(counts) if colptr_ub is not None else None, _ptr(cand_u), _ptr(cand_v), _ptr(cn), _ptr(score),
-                            _ptr(cut_rec), _ptr(ws), ws_bytes, int(tile_ranks), _stream(dev)), "eps_expand_fill")
-            if cut_rec is not None:                      # one read-back for the status word and the survivor count
-                both = torch.stack([ws[0], cut_rec[1]]).tolist()
-                status, n_cut = both[0] & 0xFFFFFFFF, both[1] & 0xFFFFFFFF
-            else:
-                status, n_cut = int(ws[0].item()) & 0xFFFFFFFF, 0
-            if status:
-                raise _lib.EpsError("expand_candidates: " + ("a column had more two-hop paths than max_paths allows; " if status & 1 else "")
-                                    + ("a column had more candidates than its colptr_ub segment; " if status & 2 else "")
-                                    + ("a score left the fixed-point range (|sum| >= 2**23): use the pair kernels" if status & 4 else ""))
+            status, n_cut = int(ws[0].item()) & 0xFFFFFFFF, 0
+        if status:
+            raise _lib.EpsError("expand_candidates: " + ("a column had more two-hop paths than max_paths allows; " if status & 1 else "")
+                                + ("a column had more candidates than its colptr_ub segment; " if status & 2 else "")
+                                + ("a score left the fixed-point range (|sum| >= 2**23): use the pair kernels" if status & 4 else ""))
     out = ExpandResult((colptr, cand_u, cand_v, cn, score))
     out.pairs = pairs if want_v else None
     out.counts = counts if colptr_ub is not None else None
@@ -414,7 +420,7 @@ def expand_candidates(rowptr, col, val, node_w, n_nodes: int, v_lo: int, v_hi: i
         order = torch.argsort(cut_pos[:n_cut])                     # arrival order -> candidate order
         out.survivors = (cut_pos[:n_cut][order], cut_val[:n_cut][order])
     elif cut is not None and not total:
-        out.survivors = (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev))
+        out.survivors = (torch.zeros(0, dtype=_I64, device=dev), torch.zeros(0, dtype=_F32, device=dev))
     return out
 
 
@@ -427,14 +433,12 @@ def reverse_positions(rowptr: torch.Tensor, col: torch.Tensor, with_stats: bool 
     """int32[nnz]: for entry e of row v with w = col[e], the number of entries of row w below v (per-graph table).
     ``with_stats``: -> (revpos, half_paths int64[N] = its row sums, asymmetric int32[1] device flag) from the same pass."""
     dev = _need_gpu(rowptr, col)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    _csr(rowptr, col)
     n = rowptr.numel() - 1
-    out = torch.empty(col.numel(), dtype=torch.int32, device=dev)
-    hp = torch.zeros(n, dtype=torch.int64, device=dev) if with_stats else None
-    flag = torch.zeros(1, dtype=torch.int32, device=dev) if with_stats else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_reverse_positions(_ptr(rowptr), _ptr(col), n, _ptr(out), _ptr(hp), _ptr(flag), _stream(dev)),
-                   "eps_reverse_positions")
+    out = torch.empty(col.numel(), dtype=_I32, device=dev)
+    hp = torch.zeros(n, dtype=_I64, device=dev) if with_stats else None
+    flag = torch.zeros(1, dtype=_I32, device=dev) if with_stats else None
+    _call("eps_reverse_positions", dev, rowptr, col, n, out, hp, flag)
     return (out, hp, flag) if with_stats else out
 
 
@@ -447,26 +451,20 @@ def reverse_positions_symmetric(rowptr: torch.Tensor, col: torch.Tensor):
     per unordered stored pair (eps_reverse_positions_symmetric); the flag comes back 1 on any other pattern and revpos is then
     not usable."""
     dev = _need_gpu(rowptr, col)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
-    n = rowptr.numel() - 1
-    out = torch.empty(col.numel(), dtype=torch.int32, device=dev)
-    hp = torch.empty(n, dtype=torch.int64, device=dev)
+    _csr(rowptr, col)
+    n, nnz = rowptr.numel() - 1, col.numel()
+    out = torch.empty(nnz, dtype=_I32, device=dev)
+    hp = torch.empty(n, dtype=_I64, device=dev)
     # one small buffer for everything the caller reads back: [asymmetric flag (low word), max degree, max half paths, their sum]
     # (zeros: the library clears the flag as the 32-bit word it is -- the high half of info[0] is nobody's)
-    info = torch.zeros(4, dtype=torch.int64, device=dev)
-    if col.numel() >= REVPOS_SORT_MIN:
+    info = torch.zeros(4, dtype=_I64, device=dev)
+    if nnz >= REVPOS_SORT_MIN:
         # (r06: no search at all -- the mirror entries come out of a stable sort of the entry indices by column id)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _keep, wsp, wsb = _aligned_ws(dev, lib.eps_reverse_positions_sorted_workspace_bytes(n, col.numel()))
-            _lib.check(lib.eps_reverse_positions_sorted(_ptr(rowptr), _ptr(col), n, col.numel(), max(1, int(n - 1).bit_length()), _ptr(out),
-                                                        _ptr(hp), info.data_ptr(), info.data_ptr() + 8, wsp, wsb, _stream(dev)),
-                       "eps_reverse_positions_sorted")
-        return out, hp, info
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_reverse_positions_symmetric(_ptr(rowptr), _ptr(col), n, col.numel(), _ptr(out), _ptr(hp),
-                                                               info.data_ptr(), info.data_ptr() + 8, _stream(dev)),
-                   "eps_reverse_positions_symmetric")
+        _keep, wsp, wsb = _aligned_ws(dev, _lib.load().eps_reverse_positions_sorted_workspace_bytes(n, nnz))
+        _call("eps_reverse_positions_sorted", dev, rowptr, col, n, nnz, max(1, int(n - 1).bit_length()), out, hp, info.data_ptr(),
+              info.data_ptr() + 8, wsp, wsb)
+    else:
+        _call("eps_reverse_positions_symmetric", dev, rowptr, col, n, nnz, out, hp, info.data_ptr(), info.data_ptr() + 8)
     return out, hp, info
 
 
@@ -476,20 +474,17 @@ def node_order(rowptr: Optional[torch.Tensor] = None, keys: Optional[torch.Tenso
     new_rowptr int64[n + 1]): what ``relabel_graph`` needs for the copy under that order."""
     src = rowptr if rowptr is not None else keys
     dev = _need_gpu(src)
-    _chk(src, torch.int64, "rowptr / keys")
+    _chk(_I64, **{"rowptr / keys": src})
     n = src.numel() - 1 if rowptr is not None else src.numel()
-    lib = _lib.load()
     order = perm = inv = new_rp = None
     if relabel:
-        perm = torch.empty(n, dtype=torch.int64, device=dev)
-        inv = torch.empty(n, dtype=torch.int32, device=dev)
-        new_rp = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        perm = torch.empty(n, dtype=_I64, device=dev)
+        inv = torch.empty(n, dtype=_I32, device=dev)
+        new_rp = torch.empty(n + 1, dtype=_I64, device=dev)
     else:
-        order = torch.empty(n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _, wsp, wsb = _aligned_ws(dev, lib.eps_node_order_workspace_bytes(n))
-        _lib.check(lib.eps_node_order(_ptr(rowptr), _ptr(keys) if rowptr is None else None, n, _ptr(order), _ptr(perm), _ptr(inv),
-                                      _ptr(new_rp), wsp, wsb, _stream(dev)), "eps_node_order")
+        order = torch.empty(n, dtype=_I32, device=dev)
+    _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_node_order_workspace_bytes(n))
+    _call("eps_node_order", dev, rowptr, keys if rowptr is None else None, n, order, perm, inv, new_rp, wsp, wsb)
     return (perm, inv, new_rp) if relabel else order
 
 
@@ -497,30 +492,24 @@ def relabel_graph(rowptr, col, val, perm: torch.Tensor, inv32: torch.Tensor, new
     """(col, val) of the copy of a coalesced CSR graph under a node permutation: row i = row perm[i] with ids through inv32,
     sorted inside the row (eps_relabel_graph: gather + segmented radix sort)."""
     dev = _need_gpu(rowptr, col, val, perm, inv32, new_rowptr)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(perm, torch.int64, "perm"); _chk(inv32, torch.int32, "inv"); _chk(new_rowptr, torch.int64, "new_rowptr")
+    _csr(rowptr, col, val); _chk(_I64, perm=perm, new_rowptr=new_rowptr); _chk(_I32, inv=inv32)
     n, nnz = rowptr.numel() - 1, col.numel()
-    out_c = torch.empty(nnz, dtype=torch.int32, device=dev)
-    out_v = None if val is None else torch.empty(nnz, dtype=torch.float32, device=dev)
+    out_c = torch.empty(nnz, dtype=_I32, device=dev)
+    out_v = None if val is None else torch.empty(nnz, dtype=_F32, device=dev)
     if nnz:
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_relabel_graph_workspace_bytes(n, nnz, int(val is not None)))
-            _lib.check(lib.eps_relabel_graph(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(perm), _ptr(inv32), _ptr(new_rowptr), n, nnz,
-                                             max(1, int(n - 1).bit_length()), _ptr(out_c), _ptr(out_v), wsp, wsb, _stream(dev)),
-                       "eps_relabel_graph")
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_relabel_graph_workspace_bytes(n, nnz, int(val is not None)))
+        _call("eps_relabel_graph", dev, rowptr, col, val, perm, inv32, new_rowptr, n, nnz, max(1, int(n - 1).bit_length()), out_c,
+              out_v, wsp, wsb)
     return out_c, out_v
 
 
 def score_bound(rowptr, col, val, node_w, n_rows: int, n_cols: int) -> torch.Tensor:
     """1-element float64 DEVICE tensor: max over the rows of sum |A[v,w]| |node_w[w]| max_u |A[u,w]| (eps_score_bound)."""
     dev = _need_gpu(rowptr, col, val, node_w)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val"); _chk(node_w, torch.float32, "node_w")
-    out = torch.empty(1, dtype=torch.float64, device=dev)
-    ws = torch.empty(n_cols, dtype=torch.int32, device=dev) if val is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_score_bound(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), int(n_rows), int(n_cols), col.numel(),
-                                               _ptr(out), _ptr(ws), _stream(dev)), "eps_score_bound")
+    _csr(rowptr, col, val); _chk(_F32, node_w=node_w)
+    out = torch.empty(1, dtype=_F64, device=dev)
+    ws = torch.empty(n_cols, dtype=_I32, device=dev) if val is not None else None
+    _call("eps_score_bound", dev, rowptr, col, val, node_w, int(n_rows), int(n_cols), col.numel(), out, ws)
     return out
 
 
@@ -536,58 +525,20 @@ def row_window_splits(rowptr: torch.Tensor, col: torch.Tensor, win_ids: int, n_w
     if n_win <= 1:
         return None
     dev = _need_gpu(rowptr, col)
+    _csr(rowptr, col)
     n = rowptr.numel() - 1
-    out = torch.empty((n_win - 1) * n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_row_window_splits(_ptr(rowptr), _ptr(col), n, int(win_ids), int(n_win), _ptr(out),
-                                                     _stream(dev)), "eps_row_window_splits")
+    out = torch.empty((n_win - 1) * n, dtype=_I32, device=dev)
+    _call("eps_row_window_splits", dev, rowptr, col, n, int(win_ids), int(n_win), out)
     return out
 
 
 def fixed_weights(node_w: torch.Tensor) -> torch.Tensor:
     """int64[N]: round(node_w * 2**40), the per-node weights in the scan kernel's fixed point."""
     dev = _need_gpu(node_w)
-    _chk(node_w, torch.float32, "node_w")
-    out = torch.empty(node_w.numel(), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_fixed_weights(_ptr(node_w), node_w.numel(), _ptr(out), _stream(dev)), "eps_fixed_weights")
+    _chk(_F32, node_w=node_w)
+    out = torch.empty(node_w.numel(), dtype=_I64, device=dev)
+    _call("eps_fixed_weights", dev, node_w, node_w.numel(), out)
     return out
-
-
-_SCAN_WS = {}
-KERNEL_EVENTS = None      # a list while bench.py times kernels: (kernel name, start event, end event, work size) per launch
-EVENT_NAMES = None        # None: every library call is bracketed while KERNEL_EVENTS is a list; a collection of names: only those (the
-                          # scan launches always are) -- bench.py's timed region carries the dominant kernel's events alone
-
-
-class _timed:
-    """``with _timed(dev, name, size):`` -- HIP events around a library call on its stream while bench.py collects KERNEL_EVENTS."""
-
-    def __init__(self, dev, name, size):
-        self.dev, self.name, self.size, self.ev = dev, name, int(size), None
-
-    def __enter__(self):
-        if KERNEL_EVENTS is not None and (EVENT_NAMES is None or self.name in EVENT_NAMES):
-            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            self.ev[0].record(torch.cuda.current_stream(self.dev))
-        return self
-
-    def __exit__(self, *exc):
-        if self.ev is not None and exc[0] is None:
-            self.ev[1].record(torch.cuda.current_stream(self.dev))
-            KERNEL_EVENTS.append((self.name, self.ev[0], self.ev[1], self.size))
-        return False
-
-
-def _scan_scratch(dev, max_degree: int) -> torch.Tensor:
-    """Scratch of eps_filter_scan (1 GiB of bucket records on 256 CUs + max_degree weights per workgroup): one grow-only
-    buffer per device, stream-ordered."""
-    key = (dev.type, dev.index)
-    need = (int(_lib.load().eps_filter_scan_workspace_bytes(int(max_degree))) + 7) // 8
-    if key not in _SCAN_WS or _SCAN_WS[key].numel() < need:
-        _SCAN_WS.pop(key, None)
-        _SCAN_WS[key] = torch.empty(need, dtype=torch.int64, device=dev)
-    return _SCAN_WS[key]
 
 
 SURVIVOR_SLOTS_MAX = (1 << 32) - (1 << 20)   # slots are 32-bit positions handed out in chunks: keep a chunk's worth of head-room
@@ -600,11 +551,11 @@ def _pinned_words(words) -> torch.Tensor:
     """A pinned int64 host tensor holding ``words`` (<= 8), from a ring of 256 slots -- the source of an asynchronous host-to-device
     copy must stay untouched until the stream has run it; 256 copies ahead of the device do not happen in this library."""
     if _PINNED["buf"] is None:
-        _PINNED["buf"] = torch.empty((256, 8), dtype=torch.int64).pin_memory()
+        _PINNED["buf"] = torch.empty((256, 8), dtype=_I64).pin_memory()
     _PINNED["i"] = (_PINNED["i"] + 1) % 256
     slot = _PINNED["buf"][_PINNED["i"]]
     n = len(words)
-    slot[:n] = torch.tensor(words, dtype=torch.int64)
+    slot[:n] = torch.tensor(words, dtype=_I64)
     return slot[:n]
 
 
@@ -620,32 +571,31 @@ class Survivors:
         ``prefill=False`` (eps_scan_screen only): no fill at all -- that kernel marks the unused slots of its reservations
         (key -1, val -inf) itself, and the list's readers stop at the slot counter (``count_ptr``): a step saves two passes
         over a list that is sized for the worst case."""
-        import struct
         self.capacity = int(capacity)
         if not 0 < self.capacity <= SURVIVOR_SLOTS_MAX:
             raise _lib.EpsError(f"Survivors: capacity {capacity} outside (0, {SURVIVOR_SLOTS_MAX}]")
         self.scores_only = bool(scores_only) and not both
         self.prefilled = bool(prefill)
         if not prefill:
-            self.key = torch.empty(self.capacity, dtype=torch.int64, device=device)
-            self.val = torch.empty(self.capacity, dtype=torch.float32, device=device)
+            self.key = torch.empty(self.capacity, dtype=_I64, device=device)
+            self.val = torch.empty(self.capacity, dtype=_F32, device=device)
         elif both:
-            self.key = torch.full((self.capacity,), -1, dtype=torch.int64, device=device)
-            self.val = torch.full((self.capacity,), float("-inf"), dtype=torch.float32, device=device)
+            self.key = torch.full((self.capacity,), -1, dtype=_I64, device=device)
+            self.val = torch.full((self.capacity,), float("-inf"), dtype=_F32, device=device)
         elif scores_only:
-            self.key = torch.empty(self.capacity, dtype=torch.int64, device=device)
-            self.val = torch.full((self.capacity,), float("-inf"), dtype=torch.float32, device=device)
+            self.key = torch.empty(self.capacity, dtype=_I64, device=device)
+            self.val = torch.full((self.capacity,), float("-inf"), dtype=_F32, device=device)
         else:
-            self.key = torch.full((self.capacity,), -1, dtype=torch.int64, device=device)
-            self.val = torch.empty(self.capacity, dtype=torch.float32, device=device)
+            self.key = torch.full((self.capacity,), -1, dtype=_I64, device=device)
+            self.val = torch.empty(self.capacity, dtype=_F32, device=device)
         thr_host = float(threshold) if not isinstance(threshold, torch.Tensor) else 0.0
         head = struct.unpack("<q", struct.pack("<fI", thr_host, self.capacity))[0]
         # (the 40-byte record goes up through a pinned staging slot, asynchronously on the stream: torch.tensor(..., device=) is a
         #  blocking copy, and a filter step builds three of these between its launches)
-        self.rec = torch.empty(5, dtype=torch.int64, device=device)
+        self.rec = torch.empty(5, dtype=_I64, device=device)
         self.rec.copy_(_pinned_words([head, 0, self.key.data_ptr(), self.val.data_ptr(), 0]), non_blocking=True)
         if isinstance(threshold, torch.Tensor):
-            self.rec.view(torch.float32)[0:1].copy_(threshold.reshape(1).to(torch.float32))
+            self.rec.view(_F32)[0:1].copy_(threshold.reshape(1).to(_F32))
 
     @property
     def count_ptr(self) -> int:
@@ -668,14 +618,11 @@ class Survivors:
         assert not self.scores_only
         n = min(int(slots), self.capacity)
         dev = self.key.device
-        out_k = torch.empty(n, dtype=torch.int64, device=dev)
-        out_v = torch.empty(n, dtype=torch.float32, device=dev)
-        n_out = torch.zeros(1, dtype=torch.int64, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_select_topk_cut_workspace_bytes())
-            _lib.check(lib.eps_compact_survivors(_ptr(self.key), _ptr(self.val), n, _ptr(out_k), _ptr(out_v), _ptr(n_out), wsp, wsb,
-                                                 _stream(dev)), "eps_compact_survivors")
+        out_k = torch.empty(n, dtype=_I64, device=dev)
+        out_v = torch.empty(n, dtype=_F32, device=dev)
+        n_out = torch.zeros(1, dtype=_I64, device=dev)
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_select_topk_cut_workspace_bytes())
+        _call("eps_compact_survivors", dev, self.key, self.val, n, out_k, out_v, n_out, wsp, wsb)
         m = int(n_out.item())
         return out_k[:m], out_v[:m]
 
@@ -686,22 +633,12 @@ def filter_scan(rowptr, col, revpos, fixw, n_nodes: int, columns: torch.Tensor, 
     ``max_degree``: the longest row of the graph (sizes a scratch table); ``splits``: ``row_window_splits`` of the graph
     when ``filter_scan_windows`` reports more than one id window."""
     dev = _need_gpu(rowptr, col, revpos, fixw, columns, splits)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(revpos, torch.int32, "revpos")
-    _chk(fixw, torch.int64, "fixw"); _chk(columns, torch.int32, "columns"); _chk(splits, torch.int32, "splits")
+    _csr(rowptr, col); _chk(_I32, revpos=revpos, columns=columns, splits=splits); _chk(_I64, fixw=fixw)
     if revpos.numel() != col.numel() or fixw.numel() != n_nodes:
         raise _lib.EpsError("filter_scan: revpos / fixw do not match the graph")
     ws = _scan_scratch(dev, max_degree)
-    with torch.cuda.device(dev):
-        ev = None
-        if KERNEL_EVENTS is not None:              # bench.py: HIP events around the launch, on the stream it runs on
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record(torch.cuda.current_stream(dev))
-        _lib.check(_lib.load().eps_filter_scan(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(fixw), _ptr(splits), n_nodes,
-                                               col.numel(), int(max_degree), _ptr(columns), columns.numel(), _ptr(out.rec), _ptr(ws),
-                                               ws.numel() * 8, _stream(dev)), "eps_filter_scan")
-        if ev is not None:
-            ev[1].record(torch.cuda.current_stream(dev))
-            KERNEL_EVENTS.append(("filter_scan_kernel", ev[0], ev[1], int(columns.numel())))
+    _call("eps_filter_scan", dev, rowptr, col, revpos, fixw, splits, n_nodes, col.numel(), int(max_degree), columns,
+          columns.numel(), out.rec, ws, ws.numel() * 8, timed=("filter_scan_kernel", columns.numel()))
 
 
 # ------------------------------------------------------------------ one-pass threshold scan (csrc/scan_pieces.hip)
@@ -712,14 +649,13 @@ def scan_windows() -> int:
 def scan_cuts(rowptr: torch.Tensor, col: torch.Tensor, bounds: torch.Tensor) -> torch.Tensor:
     """uint16 table [N, M] (stored as int16 bits): entries of every row below each id-window boundary (per-graph table)."""
     dev = _need_gpu(rowptr, col, bounds)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(bounds, torch.int32, "bounds")
+    _csr(rowptr, col); _chk(_I32, bounds=bounds)
     m = scan_windows()
     if bounds.numel() != m + 1:
         raise _lib.EpsError(f"scan_cuts: bounds must hold {m + 1} boundaries")
     n = rowptr.numel() - 1
-    out = torch.empty((n, m), dtype=torch.int16, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_cuts(_ptr(rowptr), _ptr(col), n, _ptr(bounds), _ptr(out), _stream(dev)), "eps_scan_cuts")
+    out = torch.empty((n, m), dtype=_I16, device=dev)
+    _call("eps_scan_cuts", dev, rowptr, col, n, bounds, out)
     return out
 
 
@@ -729,26 +665,21 @@ def scan_window_paths(rowptr, col, revpos, cuts, heads: Optional[torch.Tensor] =
     ``columns`` (int32 ids; without heads): only these rows are computed, the rest of the table stays uninitialised
     (eps_scan_window_paths_columns: the bar sample of a graph whose whole-graph table has not been needed yet)."""
     dev = _need_gpu(rowptr, col, revpos, cuts, heads, columns)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(revpos, torch.int32, "revpos"); _chk(cuts, torch.int16, "cuts")
+    _csr(rowptr, col); _chk(_I32, revpos=revpos, columns=columns); _chk(_I16, cuts=cuts)
     n = rowptr.numel() - 1
     _chk_heads(heads, n)
-    out = torch.empty((n, scan_windows()), dtype=torch.int32, device=dev)
-    if columns is not None:
-        _chk(columns, torch.int32, "columns")
-        if heads is not None:
-            raise _lib.EpsError("scan_window_paths: a column subset comes without a head table")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().eps_scan_window_paths_columns(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(cuts), n, _ptr(columns),
-                                                                 columns.numel(), _ptr(out), _stream(dev)), "eps_scan_window_paths_columns")
+    out = torch.empty((n, scan_windows()), dtype=_I32, device=dev)
+    if columns is None:
+        _call("eps_scan_window_paths", dev, rowptr, col, revpos, cuts, n, heads, out)
         return out
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_window_paths(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(cuts), n, _ptr(heads), _ptr(out),
-                                                     _stream(dev)), "eps_scan_window_paths")
+    if heads is not None:
+        raise _lib.EpsError("scan_window_paths: a column subset comes without a head table")
+    _call("eps_scan_window_paths_columns", dev, rowptr, col, revpos, cuts, n, columns, columns.numel(), out)
     return out
 
 
 def _chk_heads(heads: Optional[torch.Tensor], n_nodes: int) -> None:
-    _chk(heads, torch.int32, "heads")
+    _chk(_I32, heads=heads)
     if heads is not None and tuple(heads.shape) != (n_nodes, 2):
         raise _lib.EpsError("heads: expected the int32 [N, 2] table of scan_heads")
 
@@ -761,15 +692,14 @@ def scan_row_records(cuts: torch.Tensor, rowptr: torch.Tensor, fx32: torch.Tenso
     """int32-bits [N, 32]: per node ONE 128-byte line -- its 32 cuts, its first entry, its screening weight (eps_scan_row_records):
     what eps_scan_screen gathers per walked row, out of one table instead of three.  Per (graph, weight table)."""
     dev = _need_gpu(cuts, rowptr, fx32)
-    _chk(cuts, torch.int16, "cuts"); _chk(rowptr, torch.int64, "rowptr"); _chk(fx32, torch.int32, "fx32")
+    _chk(_I16, cuts=cuts); _chk(_I64, rowptr=rowptr); _chk(_I32, fx32=fx32)
     n = fx32.numel()
     if cuts.shape[0] != n or rowptr.numel() != n + 1:
         raise _lib.EpsError("scan_row_records: cuts / rowptr / fx32 do not match")
-    buf = torch.empty(n * 32 + 32, dtype=torch.int32, device=dev)           # (128-byte aligned start inside the allocation)
+    buf = torch.empty(n * 32 + 32, dtype=_I32, device=dev)           # (128-byte aligned start inside the allocation)
     off = (-buf.data_ptr() % 128) // 4
     out = buf[off:off + n * 32].view(n, 32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_row_records(_ptr(cuts), _ptr(rowptr), _ptr(fx32), n, _ptr(out), _stream(dev)), "eps_scan_row_records")
+    _call("eps_scan_row_records", dev, cuts, rowptr, fx32, n, out)
     return out
 
 
@@ -779,15 +709,12 @@ def scan_column_pack(rowptr, col, revpos, rowrec: torch.Tensor, plan) -> torch.T
     first nine pieces in the neighbour's row.  Built from ``plan`` = (pptr, records) and the row records ``rowrec``."""
     pptr, recs = plan
     dev = _need_gpu(rowptr, col, revpos, rowrec, pptr, recs)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(revpos, torch.int32, "revpos")
-    _chk(rowrec, torch.int32, "rowrec"); _chk(pptr, torch.int32, "pptr"); _chk(recs, torch.int32, "plan")
+    _csr(rowptr, col); _chk(_I32, revpos=revpos, rowrec=rowrec, pptr=pptr, plan=recs)
     n_nodes = rowptr.numel() - 1
     if pptr.numel() != n_nodes + 1 or revpos.numel() != col.numel() or rowrec.numel() != n_nodes * 32:
         raise _lib.EpsError("scan_column_pack: the tables do not match the graph")
-    pack = torch.empty((max(col.numel(), 1), 8), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_column_pack(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(rowrec), _ptr(pptr), _ptr(recs), n_nodes,
-                                                    _ptr(pack), _stream(dev)), "eps_scan_column_pack")
+    pack = torch.empty((max(col.numel(), 1), 8), dtype=_I32, device=dev)
+    _call("eps_scan_column_pack", dev, rowptr, col, revpos, rowrec, pptr, recs, n_nodes, pack)
     return pack
 
 
@@ -795,14 +722,12 @@ def scan_heads(rowptr, col, fx32: torch.Tensor, n_hub: int, budget: int, max_row
     """int32-bits [N, 2] (x_v, T_v): per column the longest prefix of its row with ids < ``n_hub`` whose screening weights sum
     to T_v <= ``budget`` (table units) -- the rows eps_scan_screen does not walk under a bar (eps_scan_heads)."""
     dev = _need_gpu(rowptr, col, fx32)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(fx32, torch.int32, "fx32")
+    _csr(rowptr, col); _chk(_I32, fx32=fx32)
     n = rowptr.numel() - 1
     if fx32.numel() != n or not 0 <= int(budget) < 1 << 31:
         raise _lib.EpsError("scan_heads: fx32 does not match the graph, or budget outside [0, 2^31)")
-    out = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_heads(_ptr(rowptr), _ptr(col), _ptr(fx32), n, int(n_hub), int(budget), int(max_rows), _ptr(out),
-                                              _stream(dev)), "eps_scan_heads")
+    out = torch.empty((n, 2), dtype=_I32, device=dev)
+    _call("eps_scan_heads", dev, rowptr, col, fx32, n, int(n_hub), int(budget), int(max_rows), out)
     return out
 
 
@@ -814,11 +739,10 @@ def scan_hub_rows(rowptr, col, n_hub: int) -> torch.Tensor:
     """int32-bits [n_hub, words]: bit x of row w = "x is a neighbour of hub w" -- the adjacency rows of the first ``n_hub`` ids as
     bitmaps over the id space (eps_scan_hub_rows; per-graph table)."""
     dev = _need_gpu(rowptr, col)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    _csr(rowptr, col)
     n = rowptr.numel() - 1
-    out = torch.empty((max(int(n_hub), 1), scan_hub_row_words(n)), dtype=torch.int32, device=dev)[:int(n_hub)]
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_hub_rows(_ptr(rowptr), _ptr(col), n, int(n_hub), _ptr(out), _stream(dev)), "eps_scan_hub_rows")
+    out = torch.empty((max(int(n_hub), 1), scan_hub_row_words(n)), dtype=_I32, device=dev)[:int(n_hub)]
+    _call("eps_scan_hub_rows", dev, rowptr, col, n, int(n_hub), out)
     return out
 
 
@@ -826,47 +750,39 @@ def scan_refine(walked: "Survivors", heads, hubrows, fx32, rowptr, col, n_nodes:
     """Complete the walked sums of a launch with skipped heads (eps_scan_refine): every valid slot of ``walked`` gets its pair's
     exact head term added; sums at or above ``out``'s bar are appended to ``out`` (compact, scores in 2^-shift units x 2^-shift)."""
     dev = _need_gpu(heads, hubrows, fx32, rowptr, col)
-    _chk_heads(heads, n_nodes); _chk(hubrows, torch.int32, "hubrows"); _chk(fx32, torch.int32, "fx32")
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    _chk_heads(heads, n_nodes); _chk(_I32, hubrows=hubrows, fx32=fx32); _csr(rowptr, col)
     if hubrows.dim() != 2 or hubrows.shape[1] != scan_hub_row_words(n_nodes) or fx32.numel() != n_nodes:
         raise _lib.EpsError("scan_refine: hubrows / fx32 do not match the graph")
-    with torch.cuda.device(dev), _timed(dev, "scan_refine", walked.capacity):
-        _lib.check(_lib.load().eps_scan_refine(_ptr(walked.rec), _ptr(heads), _ptr(hubrows), hubrows.shape[0], _ptr(fx32), _ptr(rowptr),
-                                               _ptr(col), n_nodes, int(shift), _ptr(out.rec), _stream(dev)), "eps_scan_refine")
+    _call("eps_scan_refine", dev, walked.rec, heads, hubrows, hubrows.shape[0], fx32, rowptr, col, n_nodes, int(shift), out.rec,
+          timed=("scan_refine", walked.capacity))
 
 
 def scan_screen_weights(fixw: torch.Tensor, shift: int):
     """(fx32 int32-bits[N], bad int32[1]): the scan's fixed-point weights rounded UP to 2^-shift (at least 1)."""
     dev = _need_gpu(fixw)
-    _chk(fixw, torch.int64, "fixw")
-    out = torch.empty(fixw.numel(), dtype=torch.int32, device=dev)
-    bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_screen_weights(_ptr(fixw), fixw.numel(), int(shift), _ptr(out), _ptr(bad), _stream(dev)),
-                   "eps_scan_screen_weights")
+    _chk(_I64, fixw=fixw)
+    out = torch.empty(fixw.numel(), dtype=_I32, device=dev)
+    bad = torch.empty(1, dtype=_I32, device=dev)
+    _call("eps_scan_screen_weights", dev, fixw, fixw.numel(), int(shift), out, bad)
     return out, bad
 
 
 def rescore_runs(rowptr, col, fixw: torch.Tensor, n_nodes: int, keys_by_u: torch.Tensor) -> torch.Tensor:
     """float32 exact scores of the pairs ``keys_by_u`` = (u << 32) | v, sorted ascending (eps_rescore_runs; unit values)."""
     dev = _need_gpu(rowptr, col, fixw, keys_by_u)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(fixw, torch.int64, "fixw"); _chk(keys_by_u, torch.int64, "keys")
-    out = torch.empty(keys_by_u.numel(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed(dev, "rescore_runs", keys_by_u.numel()):
-        _lib.check(_lib.load().eps_rescore_runs(_ptr(rowptr), _ptr(col), _ptr(fixw), n_nodes, _ptr(keys_by_u), keys_by_u.numel(),
-                                                _ptr(out), _stream(dev)), "eps_rescore_runs")
+    _csr(rowptr, col); _chk(_I64, fixw=fixw, keys=keys_by_u)
+    out = torch.empty(keys_by_u.numel(), dtype=_F32, device=dev)
+    _call("eps_rescore_runs", dev, rowptr, col, fixw, n_nodes, keys_by_u, keys_by_u.numel(), out,
+          timed=("rescore_runs", keys_by_u.numel()))
     return out
 
 
 def rescore_weighted(rowptr, col, val, node_w: torch.Tensor, n_nodes: int, keys: torch.Tensor) -> torch.Tensor:
     """float32 exact scores of the pairs ``keys`` = (a << 32) | b on an adjacency with stored values (eps_rescore_weighted)."""
     dev = _need_gpu(rowptr, col, val, node_w, keys)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(node_w, torch.float32, "node_w"); _chk(keys, torch.int64, "keys")
-    out = torch.empty(keys.numel(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_rescore_weighted(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(node_w), n_nodes, _ptr(keys), keys.numel(),
-                                                    _ptr(out), _stream(dev)), "eps_rescore_weighted")
+    _csr(rowptr, col, val); _chk(_F32, node_w=node_w); _chk(_I64, keys=keys)
+    out = torch.empty(keys.numel(), dtype=_F32, device=dev)
+    _call("eps_rescore_weighted", dev, rowptr, col, val, node_w, n_nodes, keys, keys.numel(), out)
     return out
 
 
@@ -874,10 +790,9 @@ def scan_plan_rewalk(plan, variant: int):
     """(paths walked again in hash-partitioned passes, all paths) of a plan table (eps_scan_plan_rewalk) -- two Python ints."""
     pptr, recs = plan
     dev = _need_gpu(pptr, recs)
-    out = torch.empty(2, dtype=torch.int64, device=dev)
-    n_rec = int(pptr[-1].item())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_plan_rewalk(_ptr(recs), n_rec, int(variant), _ptr(out), _stream(dev)), "eps_scan_plan_rewalk")
+    _chk(_I32, pptr=pptr, plan=recs)
+    out = torch.empty(2, dtype=_I64, device=dev)
+    _call("eps_scan_plan_rewalk", dev, recs, int(pptr[-1].item()), int(variant), out)
     re, total = out.tolist()
     return re, total
 
@@ -885,10 +800,9 @@ def scan_plan_rewalk(plan, variant: int):
 def scan_bounds(rowptr, n_nodes: int) -> torch.Tensor:
     """int32 [M + 1]: the id windows of equal stored-entry mass eps_scan_cuts / eps_scan_screen work on (eps_scan_bounds)."""
     dev = _need_gpu(rowptr)
-    _chk(rowptr, torch.int64, "rowptr")
-    out = torch.empty(scan_windows() + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_bounds(_ptr(rowptr), n_nodes, _ptr(out), _stream(dev)), "eps_scan_bounds")
+    _chk(_I64, rowptr=rowptr)
+    out = torch.empty(scan_windows() + 1, dtype=_I32, device=dev)
+    _call("eps_scan_bounds", dev, rowptr, n_nodes, out)
     return out
 
 
@@ -897,13 +811,11 @@ def scan_row_sums(rowptr, col, fx32: torch.Tensor, bounds: torch.Tensor, n_nodes
     2^31 - 1), its suffix maxima at the window boundaries, and the smallest screening weight of a node with two neighbours or
     more (-1 = none) -- eps_scan_row_sums."""
     dev = _need_gpu(rowptr, col, fx32, bounds)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(fx32, torch.int32, "fx32"); _chk(bounds, torch.int32, "bounds")
+    _csr(rowptr, col); _chk(_I32, fx32=fx32, bounds=bounds)
     m = scan_windows()
-    buf = torch.empty(n_nodes + 2 * m + 2, dtype=torch.int32, device=dev)       # ssum | smax | min_fx | workspace
+    buf = torch.empty(n_nodes + 2 * m + 2, dtype=_I32, device=dev)       # ssum | smax | min_fx | workspace
     ssum, smax, min_fx, ws = buf[:n_nodes], buf[n_nodes:n_nodes + m + 1], buf[n_nodes + m + 1:n_nodes + m + 2], buf[n_nodes + m + 2:]
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_scan_row_sums(_ptr(rowptr), _ptr(col), _ptr(fx32), _ptr(bounds), n_nodes, _ptr(ssum), _ptr(smax),
-                                                 _ptr(min_fx), _ptr(ws), _stream(dev)), "eps_scan_row_sums")
+    _call("eps_scan_row_sums", dev, rowptr, col, fx32, bounds, n_nodes, ssum, smax, min_fx, ws)
     return ssum, smax, min_fx
 
 
@@ -924,21 +836,17 @@ def scan_plan(rowptr, cuts, wpaths, ssum, smax, bounds, n_nodes: int, shift: int
     ``heads``: the head table ``wpaths`` was built with (a column's sum bound then leaves its skipped head out)."""
     dev = _need_gpu(rowptr, cuts, wpaths, ssum, smax, bounds, heads)
     _chk_heads(heads, n_nodes)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(cuts, torch.int16, "cuts"); _chk(wpaths, torch.int32, "wpaths")
-    _chk(ssum, torch.int32, "ssum"); _chk(smax, torch.int32, "smax"); _chk(bounds, torch.int32, "bounds")
-    lib = _lib.load()
-    counts = torch.empty(n_nodes, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.eps_scan_plan(_ptr(rowptr), _ptr(cuts), _ptr(wpaths), _ptr(ssum), _ptr(smax), _ptr(heads), _ptr(bounds), n_nodes,
-                                     int(shift), int(variant), _ptr(counts), None, None, None, _stream(dev)), "eps_scan_plan")
-        pptr = torch.zeros(n_nodes + 1, dtype=torch.int32, device=dev)
-        if n_nodes:
-            torch.cumsum(counts, 0, dtype=torch.int32, out=pptr[1:])
-        n_rec = int(pptr[-1].item()) if n_nodes else 0
-        recs = torch.empty((max(n_rec, 1), 4), dtype=torch.int32, device=dev)
-        d_used = torch.zeros(1, dtype=torch.int32, device=dev) if with_d else None
-        _lib.check(lib.eps_scan_plan(_ptr(rowptr), _ptr(cuts), _ptr(wpaths), _ptr(ssum), _ptr(smax), _ptr(heads), _ptr(bounds), n_nodes,
-                                     int(shift), int(variant), None, _ptr(pptr), _ptr(recs), _ptr(d_used), _stream(dev)), "eps_scan_plan")
+    _chk(_I64, rowptr=rowptr); _chk(_I16, cuts=cuts); _chk(_I32, wpaths=wpaths, ssum=ssum, smax=smax, bounds=bounds)
+    tables = (rowptr, cuts, wpaths, ssum, smax, heads, bounds, n_nodes, int(shift), int(variant))
+    counts = torch.empty(n_nodes, dtype=_I32, device=dev)
+    _call("eps_scan_plan", dev, *tables, counts, None, None, None)
+    pptr = torch.zeros(n_nodes + 1, dtype=_I32, device=dev)
+    if n_nodes:
+        torch.cumsum(counts, 0, dtype=_I32, out=pptr[1:])
+    n_rec = int(pptr[-1].item()) if n_nodes else 0
+    recs = torch.empty((max(n_rec, 1), 4), dtype=_I32, device=dev)
+    d_used = torch.zeros(1, dtype=_I32, device=dev) if with_d else None
+    _call("eps_scan_plan", dev, *tables, None, pptr, recs, d_used)
     return (pptr, recs, d_used) if with_d else (pptr, recs)
 
 
@@ -963,59 +871,44 @@ def scan_screen(rowptr, col, revpos, fx32, cuts, bounds, n_nodes: int, columns: 
     ``colrec`` (int32 [len(columns), 8]; ``scan.column_records``): the columns' headers in hand-out order.
     ``pack`` (``scan_column_pack``; main launch only): the per-column pack built from this plan table and these row records."""
     pptr, recs = plan if plan is not None else (None, None)
-    dev = _need_gpu(rowptr, col, revpos, fx32, cuts, bounds, columns, status, val, node_w, wpaths, ssum, smax, pptr, recs, heads)
+    dev = _need_gpu(rowptr, col, revpos, fx32, cuts, bounds, columns, status, val, node_w, wpaths, ssum, smax, pptr, recs, heads,
+                    rowrec, colrec, pack)
     _chk_heads(heads, n_nodes)
     if heads is not None and (pptr is None or val is not None):
         raise _lib.EpsError("scan_screen: a head table comes with the plan table built for it (unit-valued graphs)")
-    _chk(pptr, torch.int32, "pptr"); _chk(recs, torch.int32, "plan")
+    _chk(_I32, pptr=pptr, plan=recs)
     if pptr is not None and (val is not None or wpaths is None or pptr.numel() != n_nodes + 1):
         raise _lib.EpsError("scan_screen: the plan table does not match the graph (unit-valued graphs with wpaths only)")
-    _chk(wpaths, torch.int32, "wpaths"); _chk(ssum, torch.int32, "ssum"); _chk(smax, torch.int32, "smax")
+    _chk(_I32, wpaths=wpaths, ssum=ssum, smax=smax)
     if (ssum is None) != (smax is None) or (ssum is not None and (ssum.numel() != n_nodes or smax.numel() != scan_windows() + 1)):
         raise _lib.EpsError("scan_screen: ssum / smax do not match the graph")
     if wpaths is not None and tuple(wpaths.shape) != (n_nodes, scan_windows()):
         raise _lib.EpsError("scan_screen: wpaths does not match the graph")
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(revpos, torch.int32, "revpos")
-    _chk(fx32, torch.int32, "fx32"); _chk(cuts, torch.int16, "cuts"); _chk(bounds, torch.int32, "bounds")
-    _chk(columns, torch.int32, "columns"); _chk(status, torch.int32, "status"); _chk(val, torch.float32, "val")
-    _chk(node_w, torch.float32, "node_w")
+    _csr(rowptr, col, val); _chk(_F32, node_w=node_w); _chk(_I16, cuts=cuts)
+    _chk(_I32, revpos=revpos, fx32=fx32, bounds=bounds, columns=columns, status=status, rowrec=rowrec, colrec=colrec, pack=pack)
     if revpos.numel() != col.numel() or cuts.shape[0] != n_nodes or (val is None and fx32.numel() != n_nodes):
         raise _lib.EpsError("scan_screen: revpos / fx32 / cuts do not match the graph")
     if val is not None and (val.numel() != col.numel() or node_w is None or node_w.numel() != n_nodes):
         raise _lib.EpsError("scan_screen: val / node_w do not match the graph")
     variant = SCAN_VARIANT if variant is None else int(variant)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ev = None
-        if KERNEL_EVENTS is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record(torch.cuda.current_stream(dev))
-        if val is None:
-            _lib.check(lib.eps_scan_screen(_ptr(rowptr), _ptr(col), _ptr(revpos), _ptr(fx32), _ptr(cuts), _ptr(wpaths), _ptr(ssum),
-                                           _ptr(smax), _ptr(pptr), _ptr(recs), _ptr(heads), _ptr(rowrec), _ptr(pack), _ptr(bounds), n_nodes,
-                                           col.numel(), _ptr(columns), _ptr(colrec), columns.numel(), -1 if batch_from is None else int(batch_from),
-                                           int(shift), variant, _ptr(out.rec), _ptr(status), _stream(dev)), "eps_scan_screen")
-        else:
-            _lib.check(lib.eps_scan_screen_weighted(_ptr(rowptr), _ptr(col), _ptr(val), _ptr(revpos), _ptr(node_w), _ptr(cuts),
-                                                    _ptr(wpaths), _ptr(bounds), n_nodes, col.numel(), _ptr(columns), columns.numel(), int(shift),
-                                                    variant, _ptr(out.rec), _ptr(status), _stream(dev)), "eps_scan_screen_weighted")
-        if ev is not None:
-            ev[1].record(torch.cuda.current_stream(dev))
-            KERNEL_EVENTS.append(("scan_piece_kernel", ev[0], ev[1], int(columns.numel())))
+    timed = ("scan_piece_kernel", columns.numel())
+    if val is None:
+        _call("eps_scan_screen", dev, rowptr, col, revpos, fx32, cuts, wpaths, ssum, smax, pptr, recs, heads, rowrec, pack,
+              bounds, n_nodes, col.numel(), columns, colrec, columns.numel(), -1 if batch_from is None else int(batch_from),
+              int(shift), variant, out.rec, status, timed=timed)
+    else:
+        _call("eps_scan_screen_weighted", dev, rowptr, col, val, revpos, node_w, cuts, wpaths, bounds, n_nodes, col.numel(),
+              columns, columns.numel(), int(shift), variant, out.rec, status, timed=timed)
 
 
 def spmm_csr(rowptr, col, val, x: torch.Tensor, bias=None, relu=False, mean=False, out=None) -> torch.Tensor:
     dev = _need_gpu(rowptr, col, val, x, bias, out, row_strided=(x, out))
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(x, torch.float32, "x"); _chk(bias, torch.float32, "bias")
+    _csr(rowptr, col, val); _chk(_F32, x=x, bias=bias, out=out)
     n_rows = rowptr.numel() - 1
     f = x.shape[1]
     if out is None:
-        out = torch.empty((n_rows, f), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_spmm_csr(_ptr(rowptr), _ptr(col), _ptr(val), n_rows, _ptr(x), x.stride(0), f,
-                                            _ptr(bias), int(relu), int(mean), _ptr(out), out.stride(0),
-                                            _stream(dev)), "eps_spmm_csr")
+        out = torch.empty((n_rows, f), dtype=_F32, device=dev)
+    _call("eps_spmm_csr", dev, rowptr, col, val, n_rows, x, x.stride(0), f, bias, int(relu), int(mean), out, out.stride(0))
     return out
 
 
@@ -1028,7 +921,7 @@ def cos_node_features(rowptr, col, val, x: torch.Tensor, want_norm: bool = False
     rows are 128-byte aligned and whose pad columns are zero (what ``edge_cosines`` reads).  ``want_norm``: -> (xhat, nrm)
     with nrm float32 [N] = max(||x'||_2, 1e-8), what the backward needs (eps_cos_node_features_nrm; the same xhat)."""
     dev = _need_gpu(rowptr, col, val, x, row_strided=(x,))
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val"); _chk(x, torch.float32, "x")
+    _csr(rowptr, col, val); _chk(_F32, x=x)
     n = rowptr.numel() - 1
     if x.dim() != 2 or x.shape[0] != n:
         raise _lib.EpsError(f"cos_node_features: x must be [{n}, F], got {tuple(x.shape)}")
@@ -1038,16 +931,13 @@ def cos_node_features(rowptr, col, val, x: torch.Tensor, want_norm: bool = False
     if val is not None and val.numel() != col.numel():
         raise _lib.EpsError("cos_node_features: val and col differ in length")
     ldh = (f + COS_ROW_FLOATS - 1) // COS_ROW_FLOATS * COS_ROW_FLOATS
-    buf = torch.empty((n, ldh), dtype=torch.float32, device=dev)
+    buf = torch.empty((n, ldh), dtype=_F32, device=dev)
     ldx = x.stride(0) if n > 1 else max(f, x.stride(0))
-    with torch.cuda.device(dev):
-        if want_norm:
-            nrm = torch.empty(n, dtype=torch.float32, device=dev)
-            _lib.check(_lib.load().eps_cos_node_features_nrm(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(x), ldx, f, _ptr(buf),
-                                                             ldh, _ptr(nrm), _stream(dev)), "eps_cos_node_features_nrm")
-            return buf[:, :f], nrm
-        _lib.check(_lib.load().eps_cos_node_features(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(x), ldx, f, _ptr(buf), ldh,
-                                                     _stream(dev)), "eps_cos_node_features")
+    if want_norm:
+        nrm = torch.empty(n, dtype=_F32, device=dev)
+        _call("eps_cos_node_features_nrm", dev, rowptr, col, val, n, x, ldx, f, buf, ldh, nrm)
+        return buf[:, :f], nrm
+    _call("eps_cos_node_features", dev, rowptr, col, val, n, x, ldx, f, buf, ldh)
     return buf[:, :f]
 
 
@@ -1055,8 +945,7 @@ def edge_cosines(rowptr, col, xhat: torch.Tensor, revpos: Optional[torch.Tensor]
     """c[e] = xhat[row(e)] . xhat[col(e)] for every stored entry -> float32[nnz] (eps_edge_cosines).  ``xhat``: the output of
     ``cos_node_features``.  ``revpos`` (scan.reverse_positions of a SYMMETRIC pattern) computes each undirected entry once."""
     dev = _need_gpu(rowptr, col, xhat, revpos, row_strided=(xhat,))
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(xhat, torch.float32, "xhat")
-    _chk(revpos, torch.int32, "revpos")
+    _csr(rowptr, col); _chk(_F32, xhat=xhat); _chk(_I32, revpos=revpos)
     n = rowptr.numel() - 1
     if xhat.dim() != 2 or xhat.shape[0] != n:
         raise _lib.EpsError(f"edge_cosines: xhat must be [{n}, F], got {tuple(xhat.shape)}")
@@ -1066,10 +955,8 @@ def edge_cosines(rowptr, col, xhat: torch.Tensor, revpos: Optional[torch.Tensor]
     ldh = xhat.stride(0) if n > 1 else max(f, xhat.stride(0))
     if f < 1 or ldh % 4 or xhat.data_ptr() % 16:
         raise _lib.EpsError("edge_cosines: xhat needs 16-byte aligned rows of at least one column (cos_node_features output)")
-    out = torch.empty(col.numel(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_edge_cosines(_ptr(rowptr), _ptr(col), n, _ptr(xhat), ldh, f, _ptr(revpos), _ptr(out),
-                                                _stream(dev)), "eps_edge_cosines")
+    out = torch.empty(col.numel(), dtype=_F32, device=dev)
+    _call("eps_edge_cosines", dev, rowptr, col, n, xhat, ldh, f, revpos, out)
     return out
 
 
@@ -1078,22 +965,18 @@ def pair_cn_backward(rowptr, col, c: torch.Tensor, u, v, g: torch.Tensor) -> tor
     common-neighbour sums raw_p = sum_w c[(u_p, w)] c[(v_p, w)] (eps_pair_cn_backward).  Order-independent: the same inputs --
     in any order of the pair list -- give the same bits."""
     dev = _need_gpu(rowptr, col, c, u, v, g)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(c, torch.float32, "c")
-    _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v"); _chk(g, torch.float32, "g")
+    _csr(rowptr, col); _chk(_F32, c=c, g=g); _chk(_I32, u=u, v=v)
     if c.numel() != col.numel():
         raise _lib.EpsError("pair_cn_backward: c and col differ in length")
     if u.numel() != v.numel() or g.numel() != u.numel():
         raise _lib.EpsError("pair_cn_backward: u, v and g differ in length")
     n, nnz = rowptr.numel() - 1, col.numel()
-    gc = torch.empty(nnz, dtype=torch.float32, device=dev)
+    gc = torch.empty(nnz, dtype=_F32, device=dev)
     if nnz == 0:
         return gc
-    lib = _lib.load()
-    ws_bytes = int(lib.eps_pair_cn_backward_workspace_bytes(nnz))
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.eps_pair_cn_backward(_ptr(rowptr), _ptr(col), _ptr(c), n, nnz, _ptr(u), _ptr(v), _ptr(g), u.numel(),
-                                            _ptr(gc), _ptr(ws), ws_bytes, _stream(dev)), "eps_pair_cn_backward")
+    ws_bytes = int(_lib.load().eps_pair_cn_backward_workspace_bytes(nnz))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=_I64, device=dev)
+    _call("eps_pair_cn_backward", dev, rowptr, col, c, n, nnz, u, v, g, u.numel(), gc, ws, ws_bytes)
     return gc
 
 
@@ -1105,8 +988,7 @@ def cos_features_backward(rowptr, col, val, xhat: torch.Tensor, nrm: torch.Tenso
     ``want_scaled``: -> (gxp, gxp / (rowsum(A) + 1e-6)), the second being what the smoothing's backward multiplies by A.
     Both are views of buffers with 128-byte aligned rows and zero pad columns."""
     dev = _need_gpu(rowptr, col, val, xhat, nrm, revpos, gc, row_strided=(xhat,))
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col"); _chk(val, torch.float32, "val")
-    _chk(xhat, torch.float32, "xhat"); _chk(nrm, torch.float32, "nrm"); _chk(revpos, torch.int32, "revpos"); _chk(gc, torch.float32, "gc")
+    _csr(rowptr, col, val); _chk(_F32, xhat=xhat, nrm=nrm, gc=gc); _chk(_I32, revpos=revpos)
     n = rowptr.numel() - 1
     if xhat.dim() != 2 or xhat.shape[0] != n or nrm.numel() != n:
         raise _lib.EpsError(f"cos_features_backward: xhat must be [{n}, F] and nrm [{n}], got {tuple(xhat.shape)} and {tuple(nrm.shape)}")
@@ -1119,23 +1001,19 @@ def cos_features_backward(rowptr, col, val, xhat: torch.Tensor, nrm: torch.Tenso
     if f < 1 or ldh % 4 or xhat.data_ptr() % 16:
         raise _lib.EpsError("cos_features_backward: xhat needs 16-byte aligned rows of at least one column (cos_node_features output)")
     ldg = (f + COS_ROW_FLOATS - 1) // COS_ROW_FLOATS * COS_ROW_FLOATS
-    gxp = torch.empty((n, ldg), dtype=torch.float32, device=dev)
-    gxs = torch.empty((n, ldg), dtype=torch.float32, device=dev) if want_scaled else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_cos_features_backward(_ptr(rowptr), _ptr(col), _ptr(val), n, _ptr(xhat), ldh, f, _ptr(nrm),
-                                                         _ptr(revpos), _ptr(gc), _ptr(gxp), _ptr(gxs), ldg, _stream(dev)),
-                   "eps_cos_features_backward")
+    gxp = torch.empty((n, ldg), dtype=_F32, device=dev)
+    gxs = torch.empty((n, ldg), dtype=_F32, device=dev) if want_scaled else None
+    _call("eps_cos_features_backward", dev, rowptr, col, val, n, xhat, ldh, f, nrm, revpos, gc, gxp, gxs, ldg)
     return (gxp[:, :f], gxs[:, :f]) if want_scaled else gxp[:, :f]
 
 
 def gcn_norm(rowptr, col, val) -> torch.Tensor:
     dev = _need_gpu(rowptr, col, val)
+    _csr(rowptr, col, val)
     n_rows = rowptr.numel() - 1
-    dis = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    out = torch.empty(col.numel(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_gcn_norm(_ptr(rowptr), _ptr(col), _ptr(val), n_rows, _ptr(dis), _ptr(out),
-                                            _stream(dev)), "eps_gcn_norm")
+    dis = torch.empty(n_rows, dtype=_F32, device=dev)
+    out = torch.empty(col.numel(), dtype=_F32, device=dev)
+    _call("eps_gcn_norm", dev, rowptr, col, val, n_rows, dis, out)
     return out
 
 
@@ -1143,7 +1021,7 @@ def gemm(a: torch.Tensor, b_nk: torch.Tensor, bias=None, relu=False, out=None, a
     """C = act(a @ b_nk.T + bias (+ C)); b_nk is [N,K] (torch.nn.Linear layout).  ``lower_only``: the product is symmetric and
     only its 128 x 128 tiles on and below the diagonal are computed (the rest of ``out`` is left as it is)."""
     dev = _need_gpu(a, b_nk, bias, out, row_strided=(a, b_nk, out))
-    _chk(a, torch.float32, "a"); _chk(b_nk, torch.float32, "b"); _chk(bias, torch.float32, "bias")
+    _chk(_F32, a=a, b=b_nk, bias=bias, out=out)
     m, k = a.shape
     n = b_nk.shape[0]
     if b_nk.shape[1] != k:
@@ -1151,22 +1029,19 @@ def gemm(a: torch.Tensor, b_nk: torch.Tensor, bias=None, relu=False, out=None, a
     if out is None:
         if accumulate:
             raise _lib.EpsError("gemm: accumulate needs out")
-        out = torch.empty((m, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_gemm_f32(_ptr(a), a.stride(0), _ptr(b_nk), b_nk.stride(0), _ptr(bias), int(relu) | (2 if lower_only else 0),
-                                            int(accumulate), _ptr(out), out.stride(0), m, n, k, _stream(dev)),
-                   "eps_gemm_f32")
+        out = torch.empty((m, n), dtype=_F32, device=dev)
+    _call("eps_gemm_f32", dev, a, a.stride(0), b_nk, b_nk.stride(0), bias, int(relu) | (2 if lower_only else 0), int(accumulate), out,
+          out.stride(0), m, n, k)
     return out
 
 
 def dense_adjacency(rowptr, col, n_nodes: int, pad_to: int = 128) -> torch.Tensor:
     """float32 [Np, Np] (Np = n_nodes rounded up to ``pad_to``): 1.0 at every stored entry, 0 elsewhere (eps_dense_adjacency)."""
     dev = _need_gpu(rowptr, col)
-    _chk(rowptr, torch.int64, "rowptr"); _chk(col, torch.int32, "col")
+    _csr(rowptr, col)
     np_ = (int(n_nodes) + pad_to - 1) // pad_to * pad_to
-    a = torch.empty((max(np_, 1), max(np_, 1)), dtype=torch.float32, device=dev)[:np_, :np_]
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_dense_adjacency(_ptr(rowptr), _ptr(col), int(n_nodes), np_, np_, _ptr(a), _stream(dev)), "eps_dense_adjacency")
+    a = torch.empty((max(np_, 1), max(np_, 1)), dtype=_F32, device=dev)[:np_, :np_]
+    _call("eps_dense_adjacency", dev, rowptr, col, int(n_nodes), np_, np_, a)
     return a
 
 
@@ -1183,58 +1058,50 @@ def dense_cn_candidates(rowptr, col, n_nodes: int, directed: bool = False, check
         return None
     c = torch.empty_like(a)
     gemm(a, a, out=c, lower_only=True)               # (symmetric: half the tiles ...
-    lib = _lib.load()
     if directed:                                     #  ... and a transposed copy for the readers of whole rows)
-        with torch.cuda.device(dev):
-            _lib.check(lib.eps_dense_mirror_lower(_ptr(c), n_nodes, c.stride(0), _stream(dev)), "eps_dense_mirror_lower")
-    counts = torch.empty(n_nodes + 1, dtype=torch.int64, device=dev)
+        _call("eps_dense_mirror_lower", dev, c, n_nodes, c.stride(0))
+    counts = torch.empty(n_nodes + 1, dtype=_I64, device=dev)
     counts[n_nodes:] = 0
-    with torch.cuda.device(dev):
-        _lib.check(lib.eps_dense_candidates(_ptr(a), _ptr(c), n_nodes, a.stride(0), 0 if directed else 1, _ptr(counts), None, None, None,
-                                            None, _stream(dev)), "eps_dense_candidates")
-        colptr = torch.zeros(n_nodes + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts[:n_nodes], 0, out=colptr[1:])
-        total = int(colptr[-1].item())
-        keys = torch.empty((total, 3), dtype=torch.float32, device=dev) if as_rows else torch.empty(total, dtype=torch.int64, device=dev)
-        vals = torch.empty(total, dtype=torch.float32, device=dev)
-        if total:
-            _lib.check(lib.eps_dense_candidates(_ptr(a), _ptr(c), n_nodes, a.stride(0), 0 if directed else 1, None, _ptr(colptr),
-                                                None if as_rows else _ptr(keys), _ptr(vals), _ptr(keys) if as_rows else None,
-                                                _stream(dev)), "eps_dense_candidates")
+    half = 0 if directed else 1
+    _call("eps_dense_candidates", dev, a, c, n_nodes, a.stride(0), half, counts, None, None, None, None)
+    colptr = torch.zeros(n_nodes + 1, dtype=_I64, device=dev)
+    torch.cumsum(counts[:n_nodes], 0, out=colptr[1:])
+    total = int(colptr[-1].item())
+    keys = torch.empty((total, 3), dtype=_F32, device=dev) if as_rows else torch.empty(total, dtype=_I64, device=dev)
+    vals = torch.empty(total, dtype=_F32, device=dev)
+    if total:
+        _call("eps_dense_candidates", dev, a, c, n_nodes, a.stride(0), half, None, colptr, None if as_rows else keys, vals,
+              keys if as_rows else None)
     return keys, vals
 
 
 def mlp_decode(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
                apply_sigmoid=True) -> torch.Tensor:
     dev = _need_gpu(h, u, v, *weights, *biases)
-    _chk(h, torch.float32, "h"); _chk(u, torch.int32, "u"); _chk(v, torch.int32, "v")
+    _chk(_F32, h=h); _chk(_I32, u=u, v=v)
     L = len(weights)
     hd = h.shape[1]
     for i, (w, b) in enumerate(zip(weights, biases)):
-        _chk(w, torch.float32, f"w{i}"); _chk(b, torch.float32, f"b{i}")
+        _chk(_F32, **{f"w{i}": w, f"b{i}": b})
         exp = (1 if i == L - 1 else hd, hd)
         if tuple(w.shape) != exp:
             raise _lib.EpsError(f"mlp_decode: layer {i} weight {tuple(w.shape)} != {exp} "
                                 f"(hidden width must equal the embedding width, last layer out=1)")
     n = u.numel()
-    out = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(n, dtype=_F32, device=dev)
     wp = (ctypes.c_void_p * L)(*[w.data_ptr() for w in weights])
     bp = (ctypes.c_void_p * L)(*[b.data_ptr() for b in biases])
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_mlp_decode(_ptr(h), h.shape[0], hd, _ptr(u), _ptr(v), n, wp, bp, L,
-                                              int(apply_sigmoid), _ptr(out), _stream(dev)), "eps_mlp_decode")
+    _call("eps_mlp_decode", dev, h, h.shape[0], hd, u, v, n, wp, bp, L, int(apply_sigmoid), out)
     return out
 
 
 def kth_largest(x: torch.Tensor, k: int) -> torch.Tensor:
     """The k-th largest value of a float32 device vector (1-element device tensor; no host round trip): radix select."""
     dev = _need_gpu(x)
-    _chk(x, torch.float32, "x")
-    lib = _lib.load()
-    out = torch.empty(1, dtype=torch.float32, device=dev)
-    ws = torch.empty((int(lib.eps_kth_largest_workspace_bytes()) + 7) // 8, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.eps_kth_largest_f32(_ptr(x), x.numel(), int(k), _ptr(out), _ptr(ws), _stream(dev)), "eps_kth_largest_f32")
+    _chk(_F32, x=x)
+    out = torch.empty(1, dtype=_F32, device=dev)
+    ws = torch.empty((int(_lib.load().eps_kth_largest_workspace_bytes()) + 7) // 8, dtype=_I64, device=dev)
+    _call("eps_kth_largest_f32", dev, x, x.numel(), int(k), out, ws)
     return out
 
 
@@ -1242,20 +1109,17 @@ def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four
     rounds; per round one all-reduce of the 256-bin histogram (1 KiB) -- no host round trip.  ``world`` == 1: no collective."""
+    from . import dist as epd
     dev = _need_gpu(x)
-    _chk(x, torch.float32, "x")
-    lib = _lib.load()
-    state = torch.empty(int(lib.eps_kth_largest_workspace_bytes()) // 4, dtype=torch.int32, device=dev)
-    out = torch.empty(1, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        _lib.check(lib.eps_kth_begin(_ptr(state), int(k), st), "eps_kth_begin")
-        for shift in (24, 16, 8, 0):
-            _lib.check(lib.eps_kth_hist_f32(_ptr(x), x.numel(), _ptr(state), shift, st), "eps_kth_hist_f32")
-            from . import dist as epd
-            if world > 1 or epd.FORCE_COLLECTIVES:
-                epd.all_reduce_sum_(state[4:260])
-            _lib.check(lib.eps_kth_pick(_ptr(state), shift, _ptr(out), st), "eps_kth_pick")
+    _chk(_F32, x=x)
+    state = torch.empty(int(_lib.load().eps_kth_largest_workspace_bytes()) // 4, dtype=_I32, device=dev)
+    out = torch.empty(1, dtype=_F32, device=dev)
+    _call("eps_kth_begin", dev, state, int(k))
+    for shift in (24, 16, 8, 0):
+        _call("eps_kth_hist_f32", dev, x, x.numel(), state, shift)
+        if world > 1 or epd.FORCE_COLLECTIVES:
+            epd.all_reduce_sum_(state[4:260])
+        _call("eps_kth_pick", dev, state, shift, out)
     return out
 
 
@@ -1270,73 +1134,85 @@ def select_compact(keys: Optional[torch.Tensor], vals: torch.Tensor, k: int, cou
     back LARGER: the entries beyond ``room`` were counted, not stored (a list sized for the worst case need not be mirrored by
     outputs of that size; the caller repeats the call with more room in the rare case)."""
     dev = _need_gpu(keys, vals)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals")
+    _chk(_I64, keys=keys); _chk(_F32, vals=vals)
     n = vals.numel()
-    lib = _lib.load()
-    words = (int(lib.eps_select_compact_workspace_bytes()) + 7) // 8
+    words = (int(_lib.load().eps_select_compact_workspace_bytes()) + 7) // 8
     # (one state per call, from the caching allocator: stream-ordered -- the block is handed out again only behind this launch on
     #  this stream, whatever other streams or however many calls are pending; r04's ring of 16 per device was neither)
-    state = torch.empty(words, dtype=torch.int64, device=dev)
-    kth = torch.empty(2, dtype=torch.float32, device=dev)
+    state = torch.empty(words, dtype=_I64, device=dev)
+    kth = torch.empty(2, dtype=_F32, device=dev)
     out_k = out_v = n_out = None
     if compact:
         if keys is None:
             raise _lib.EpsError("select_compact: the compaction needs keys")
         room = n if room is None else max(1, min(int(room), n))
-        out_k = torch.empty(room, dtype=torch.int64, device=dev)
-        out_v = torch.empty(room, dtype=torch.float32, device=dev)
-        n_out = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev), _timed(dev, "select_compact", n):
-        _lib.check(lib.eps_select_compact(_ptr(keys), _ptr(vals), n, count_ptr, int(k), int(mode), float(params[0]), float(params[1]),
-                                          float(params[2]), kth.data_ptr(), kth.data_ptr() + 4, _ptr(out_k), _ptr(out_v),
-                                          0 if room is None else int(room), _ptr(n_out), _ptr(state), _stream(dev)), "eps_select_compact")
+        out_k = torch.empty(room, dtype=_I64, device=dev)
+        out_v = torch.empty(room, dtype=_F32, device=dev)
+        n_out = torch.empty(1, dtype=_I64, device=dev)
+    _call("eps_select_compact", dev, keys, vals, n, count_ptr, int(k), int(mode), float(params[0]), float(params[1]),
+          float(params[2]), kth.data_ptr(), kth.data_ptr() + 4, out_k, out_v, 0 if room is None else int(room), n_out, state,
+          timed=("select_compact", n))
     return out_k, out_v, n_out, kth[0:1], kth[1:2]
+
+
+def _compact(name: str, keys: torch.Tensor, vals: torch.Tensor, *cuts):
+    """Body of compact_at_least / compact_between: the entries the library's ``name`` keeps under ``cuts``, in fresh arrays."""
+    dev = _need_gpu(keys, vals, *cuts)
+    _chk(_I64, keys=keys); _chk(_F32, vals=vals)
+    n = keys.numel()
+    out_k = torch.empty(n, dtype=_I64, device=dev)
+    out_v = torch.empty(n, dtype=_F32, device=dev)
+    n_out = torch.empty(1, dtype=_I64, device=dev)
+    _call(name, dev, keys, vals, n, *cuts, out_k, out_v, n_out)
+    return out_k, out_v, n_out
 
 
 def compact_at_least(keys: torch.Tensor, vals: torch.Tensor, cut: Optional[torch.Tensor]):
     """(keys, vals, n) -- the survivors (key >= 0) with score >= ``cut`` (1-element float32 DEVICE tensor; None: all of them)
     compacted to the front of fresh arrays, ``n`` a 1-element int64 device tensor (no host read)."""
-    dev = _need_gpu(keys, vals, cut)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals"); _chk(cut, torch.float32, "cut")
-    n = keys.numel()
-    out_k = torch.empty(n, dtype=torch.int64, device=dev)
-    out_v = torch.empty(n, dtype=torch.float32, device=dev)
-    n_out = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_compact_at_least(_ptr(keys), _ptr(vals), n, _ptr(cut), _ptr(out_k), _ptr(out_v), _ptr(n_out),
-                                                    _stream(dev)), "eps_compact_at_least")
-    return out_k, out_v, n_out
+    _chk(_F32, cut=cut)
+    return _compact("eps_compact_at_least", keys, vals, cut)
 
 
 def compact_between(keys: torch.Tensor, vals: torch.Tensor, lo: Optional[torch.Tensor], hi: Optional[torch.Tensor]):
     """(keys, vals, n) -- the entries (key >= 0) with lo <= score < hi (1-element float32 DEVICE tensors; None: open end)
     compacted to the front of fresh arrays, ``n`` a 1-element int64 device tensor (no host read)."""
-    dev = _need_gpu(keys, vals, lo, hi)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals"); _chk(lo, torch.float32, "lo"); _chk(hi, torch.float32, "hi")
-    n = keys.numel()
-    out_k = torch.empty(n, dtype=torch.int64, device=dev)
-    out_v = torch.empty(n, dtype=torch.float32, device=dev)
-    n_out = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_compact_between(_ptr(keys), _ptr(vals), n, _ptr(lo), _ptr(hi), _ptr(out_k), _ptr(out_v), _ptr(n_out),
-                                                   _stream(dev)), "eps_compact_between")
-    return out_k, out_v, n_out
+    _chk(_F32, lo=lo, hi=hi)
+    return _compact("eps_compact_between", keys, vals, lo, hi)
 
 
 def sort_pairs_by_u(keys: torch.Tensor, id_bits: int = 32, v_block_shift: int = 0) -> torch.Tensor:
     """Survivor keys v << 32 | u (u < v, any order) -> u << 32 | v sorted by (u, v), what ``rescore_runs`` wants: two stable
     radix sorts over the id bits (eps_sort_pairs_by_u)."""
     dev = _need_gpu(keys)
-    _chk(keys, torch.int64, "keys")
+    _chk(_I64, keys=keys)
     n = keys.numel()
-    out = torch.empty(n, dtype=torch.int64, device=dev)
+    out = torch.empty(n, dtype=_I64, device=dev)
     if n:
-        lib = _lib.load()
-        with torch.cuda.device(dev), _timed(dev, "sort_pairs_by_u", n):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_sort_pairs_by_u_workspace_bytes(n))
-            _lib.check(lib.eps_sort_pairs_by_u(_ptr(keys), n, int(id_bits), int(v_block_shift), _ptr(out), wsp, wsb, _stream(dev)),
-                       "eps_sort_pairs_by_u")
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_sort_pairs_by_u_workspace_bytes(n))
+        _call("eps_sort_pairs_by_u", dev, keys, n, int(id_bits), int(v_block_shift), out, wsp, wsb, timed=("sort_pairs_by_u", n))
     return out
+
+
+def _topk_rows(sel_keys, sel_vals, m: int, k: int, id_bits: int, perm, as_pairs: bool = False):
+    """Body of select_rows / select_rows_pairs / select_topk: the first min(k, 2 m) directed rows of the first ``m`` selected
+    pairs, as keys [take] or, ``as_pairs``, as the (u; v) tensor [2, take] -- and their scores."""
+    dev = _need_gpu(sel_keys, sel_vals, perm)
+    _chk(_I64, sel_keys=sel_keys, perm=perm); _chk(_F32, sel_vals=sel_vals)
+    k = int(k)
+    take = min(k, 2 * m)
+    rows = torch.empty((2, take) if as_pairs else take, dtype=_I64, device=dev)
+    out_v = torch.empty(take, dtype=_F32, device=dev)
+    if take:
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_select_topk_rows_workspace_bytes(m))
+        head = (sel_keys, sel_vals, m, k, int(id_bits))
+        if as_pairs:
+            _call("eps_select_topk_rows_pairs", dev, *head, perm, rows, take, out_v, wsp, wsb, timed=("select_rows", m))
+        elif perm is None:
+            _call("eps_select_topk_rows", dev, *head, rows, out_v, wsp, wsb)
+        else:
+            _call("eps_select_topk_rows_relabelled", dev, *head, perm, rows, out_v, wsp, wsb)
+    return rows, out_v
 
 
 def select_rows(sel_keys: torch.Tensor, sel_vals: torch.Tensor, k: int, id_bits: int = 32,
@@ -1345,40 +1221,43 @@ def select_rows(sel_keys: torch.Tensor, sel_vals: torch.Tensor, k: int, id_bits:
     job-wide cut): mirror + stable radix sorts (eps_select_topk_rows).  No host read: m is the arrays' length.
     ``perm`` (int64 [n_nodes]): the pairs are in the labels of a relabelled graph whose id i is the caller's perm[i]; the rows
     come out -- and are ordered -- in the caller's labels."""
-    dev = _need_gpu(sel_keys, sel_vals, perm)
-    _chk(sel_keys, torch.int64, "sel_keys"); _chk(sel_vals, torch.float32, "sel_vals"); _chk(perm, torch.int64, "perm")
-    m, k = sel_keys.numel(), int(k)
-    take = min(k, 2 * m)
-    out_k = torch.empty(take, dtype=torch.int64, device=dev)
-    out_v = torch.empty(take, dtype=torch.float32, device=dev)
-    if take:
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_select_topk_rows_workspace_bytes(m))
-            if perm is None:
-                _lib.check(lib.eps_select_topk_rows(_ptr(sel_keys), _ptr(sel_vals), m, k, int(id_bits), _ptr(out_k), _ptr(out_v), wsp, wsb,
-                                                    _stream(dev)), "eps_select_topk_rows")
-            else:
-                _lib.check(lib.eps_select_topk_rows_relabelled(_ptr(sel_keys), _ptr(sel_vals), m, k, int(id_bits), _ptr(perm), _ptr(out_k),
-                                                               _ptr(out_v), wsp, wsb, _stream(dev)), "eps_select_topk_rows_relabelled")
-    return out_k, out_v
+    return _topk_rows(sel_keys, sel_vals, sel_keys.numel(), k, id_bits, perm)
+
+
+def select_rows_pairs(sel_keys: torch.Tensor, sel_vals: torch.Tensor, k: int, id_bits: int = 32,
+                      perm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``select_rows`` with the rows written as the proposal tensor itself: (pairs int64 [2, min(k, 2 m)] as (u; v), scores)
+    (eps_select_topk_rows_pairs) -- no tensor ops over the K rows afterwards."""
+    return _topk_rows(sel_keys, sel_vals, sel_keys.numel(), k, id_bits, perm, as_pairs=True)
+
+
+def select_topk(keys: torch.Tensor, vals: torch.Tensor, k: int, id_bits: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best DIRECTED rows (score descending, key ascending) of a list of unordered survivors of ``filter_scan``
+    (key = v << 32 | u, u < v; no -1 slots): (keys int64, scores float32), sorted.  eps_select_topk_cut (radix select of the
+    cut + compaction) -> one host read of the count -> eps_select_topk_rows (mirror + stable radix sorts).  ``id_bits``:
+    every node id is below 2**id_bits (fewer sort passes)."""
+    dev = _need_gpu(keys, vals)
+    _chk(_I64, keys=keys); _chk(_F32, vals=vals)
+    n, k = keys.numel(), int(k)
+    if vals.numel() != n:
+        raise _lib.EpsError("select_topk: keys and vals differ in length")
+    sel_k = torch.empty(n, dtype=_I64, device=dev)
+    sel_v = torch.empty(n, dtype=_F32, device=dev)
+    n_sel = torch.zeros(1, dtype=_I64, device=dev)
+    _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_select_topk_cut_workspace_bytes())
+    _call("eps_select_topk_cut", dev, keys, vals, n, k, sel_k, sel_v, n_sel, wsp, wsb)
+    return _topk_rows(sel_k, sel_v, int(n_sel.item()), k, id_bits, None)
 
 
 # ---- the tail of the filter step with device-side sizes (csrc/tail_sort.hip, r06) ------------------------------------------------
-_TAIL_STATE = {}
-
-
 def tail_state(dev) -> torch.Tensor:
     """The state block of the tail kernels for (device, current stream): zeroed ONCE here -- the kernels that consume it leave it
     zeroed, so a step issues no memset for it."""
-    key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    st = _TAIL_STATE.get(key)
-    if st is None:
-        st = _TAIL_STATE[key] = torch.zeros((int(_lib.load().eps_tail_state_bytes()) + 7) // 8 + 32, dtype=torch.int64, device=dev)
-    return st
+    return _scratch(("tail", torch.cuda.current_stream(dev).cuda_stream), dev, 1,
+                    lambda: (int(_lib.load().eps_tail_state_bytes()) + 7) // 8 + 32, zero=True)
 
 
-def _tail_state_ptr(dev):
+def _tail_addr(dev):
     st = tail_state(dev)
     return ctypes.c_void_p(st.data_ptr() + (-st.data_ptr()) % 256)
 
@@ -1388,21 +1267,15 @@ def tail_state_reset(dev) -> None:
     tail_state(dev).zero_()
 
 
-def _dev_count(n_dev):
-    """A device count argument: None, a raw device address (Survivors.count_ptr), or a 1-element int64 tensor."""
-    if n_dev is None or isinstance(n_dev, int):
-        return n_dev
-    return n_dev.data_ptr()
-
-
+# (a device count argument -- ``n_dev`` / ``m_dev`` below -- is None, a raw device address (Survivors.count_ptr) or a 1-element
+#  int64 tensor)
 def score_hist(keys: Optional[torch.Tensor], vals: torch.Tensor, n_dev, base: torch.Tensor, above: Optional[torch.Tensor] = None) -> None:
     """Add the histogram of the list's live scores (buckets of their distance to ``base``, a 1-element float32 device tensor) to
     the tail state (eps_score_hist).  ``n_dev``: device count that bounds the list (None: its length)."""
     dev = _need_gpu(keys, vals, base, above)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals"); _chk(base, torch.float32, "base"); _chk(above, torch.float32, "above")
-    with torch.cuda.device(dev), _timed(dev, "select_compact", vals.numel()):
-        _lib.check(_lib.load().eps_score_hist(_ptr(keys), _ptr(vals), vals.numel(), _dev_count(n_dev), _ptr(base), _ptr(above),
-                                              _tail_state_ptr(dev), _stream(dev)), "eps_score_hist")
+    _chk(_I64, keys=keys, n_dev=n_dev); _chk(_F32, vals=vals, base=base, above=above)
+    _call("eps_score_hist", dev, keys, vals, vals.numel(), n_dev, base, above, _tail_addr(dev),
+          timed=("select_compact", vals.numel()))
 
 
 def score_pick_compact(keys: Optional[torch.Tensor], vals: torch.Tensor, n_dev, base: torch.Tensor, k: int, above: Optional[torch.Tensor] = None,
@@ -1413,20 +1286,18 @@ def score_pick_compact(keys: Optional[torch.Tensor], vals: torch.Tensor, n_dev, 
     to ``base``), ``thr`` derived from it as in ``select_compact``; the live entries with value >= thr are compacted into arrays
     of ``room`` entries (more are counted in n_out, not stored); ``swap_halves`` exchanges the key halves on the way."""
     dev = _need_gpu(keys, vals, base, above)
+    _chk(_I64, keys=keys, n_dev=n_dev); _chk(_F32, vals=vals, base=base, above=above)
     n = vals.numel()
-    kth = torch.empty(2, dtype=torch.float32, device=dev)
+    kth = torch.empty(2, dtype=_F32, device=dev)
     out_k = out_v = n_out = None
     if keys is not None:
         room = max(1, n if room is None else min(int(room), max(n, 1)))
-        out_k = torch.empty(room, dtype=torch.int64, device=dev)
-        out_v = torch.empty(room, dtype=torch.float32, device=dev) if want_vals else None
-        n_out = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev), _timed(dev, "select_compact", n):
-        _lib.check(_lib.load().eps_score_pick_compact(_ptr(keys), _ptr(vals), n, _dev_count(n_dev), _ptr(base), _ptr(above), int(k), int(mode),
-                                                      float(params[0]), float(params[1]), float(params[2]), int(bool(swap_halves)),
-                                                      kth.data_ptr(), kth.data_ptr() + 4, _ptr(out_k), _ptr(out_v),
-                                                      0 if out_k is None else int(room), _ptr(n_out), _tail_state_ptr(dev), _stream(dev)),
-                   "eps_score_pick_compact")
+        out_k = torch.empty(room, dtype=_I64, device=dev)
+        out_v = torch.empty(room, dtype=_F32, device=dev) if want_vals else None
+        n_out = torch.empty(1, dtype=_I64, device=dev)
+    _call("eps_score_pick_compact", dev, keys, vals, n, n_dev, base, above, int(k), int(mode), float(params[0]), float(params[1]),
+          float(params[2]), int(bool(swap_halves)), kth.data_ptr(), kth.data_ptr() + 4, out_k, out_v,
+          0 if out_k is None else int(room), n_out, _tail_addr(dev), timed=("select_compact", n))
     return out_k, out_v, n_out, kth[0:1], kth[1:2]
 
 
@@ -1439,30 +1310,25 @@ def score_hist_into(keys: Optional[torch.Tensor], vals: torch.Tensor, n_dev, bas
     """``score_hist`` into an int32 array of the caller's (``score_bins()`` words, zeroed by the caller): the histogram a rank of a
     sharded step sends to the others (eps_score_hist_into)."""
     dev = _need_gpu(keys, vals, base, above, hist)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals"); _chk(base, torch.float32, "base"); _chk(above, torch.float32, "above")
-    _chk(hist, torch.int32, "hist")
+    _chk(_I64, keys=keys, n_dev=n_dev); _chk(_F32, vals=vals, base=base, above=above); _chk(_I32, hist=hist)
     if hist.numel() < score_bins() or not hist.is_contiguous():
         raise _lib.EpsError("score_hist_into: hist must hold score_bins() contiguous words")
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_score_hist_into(_ptr(keys), _ptr(vals), vals.numel(), _dev_count(n_dev), _ptr(base), _ptr(above),
-                                                   _ptr(hist), _stream(dev)), "eps_score_hist_into")
+    _call("eps_score_hist_into", dev, keys, vals, vals.numel(), n_dev, base, above, hist)
 
 
 def score_deal_plan(hists: torch.Tensor, k: int, base: torch.Tensor):
     """(cut float32[1], splitters float32[world - 1], counts int64[world, world], nsel int64[world]) from the ranks' gathered score
     histograms ``hists`` (int32 [world, >= score_bins()], row-contiguous): eps_score_deal_plan -- device tensors, no host read."""
     dev = _need_gpu(hists, base, row_strided=(hists,))
-    _chk(hists, torch.int32, "hists"); _chk(base, torch.float32, "base")
+    _chk(_I32, hists=hists); _chk(_F32, base=base)
     if hists.dim() != 2 or hists.stride(1) != 1 or hists.shape[1] < score_bins():
         raise _lib.EpsError("score_deal_plan: hists must be [world, >= score_bins()] with unit column stride")
     world = hists.shape[0]
-    cut = torch.empty(1, dtype=torch.float32, device=dev)
-    sp = torch.empty(max(world - 1, 1), dtype=torch.float32, device=dev)
-    counts = torch.empty((world, world), dtype=torch.int64, device=dev)
-    nsel = torch.empty(world, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_score_deal_plan(_ptr(hists), hists.stride(0), world, int(k), _ptr(base), _ptr(cut), _ptr(sp), _ptr(counts),
-                                                   _ptr(nsel), _stream(dev)), "eps_score_deal_plan")
+    cut = torch.empty(1, dtype=_F32, device=dev)
+    sp = torch.empty(max(world - 1, 1), dtype=_F32, device=dev)
+    counts = torch.empty((world, world), dtype=_I64, device=dev)
+    nsel = torch.empty(world, dtype=_I64, device=dev)
+    _call("eps_score_deal_plan", dev, hists, hists.stride(0), world, int(k), base, cut, sp, counts, nsel)
     return cut, sp[:world - 1], counts, nsel
 
 
@@ -1470,15 +1336,13 @@ def radix_sort_by_u(keys: torch.Tensor, n_dev, id_bits: int = 32, v_block_shift:
     """``sort_pairs_by_u`` in one cooperative launch with the list's length read on the device (eps_radix_sort_by_u): the first
     min(*n_dev, len(keys)) keys v << 32 | u -> u << 32 | v in the order eps_rescore_runs wants; the rest of the output is undefined."""
     dev = _need_gpu(keys)
-    _chk(keys, torch.int64, "keys")
+    _chk(_I64, keys=keys, n_dev=n_dev)
     n = keys.numel()
-    out = torch.empty(n, dtype=torch.int64, device=dev)
+    out = torch.empty(n, dtype=_I64, device=dev)
     if n:
-        lib = _lib.load()
-        with torch.cuda.device(dev), _timed(dev, "sort_pairs_by_u", n):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_radix_sort_workspace_bytes(n))
-            _lib.check(lib.eps_radix_sort_by_u(_ptr(keys), n, _dev_count(n_dev), int(id_bits), int(v_block_shift), _ptr(out), wsp, wsb,
-                                               _tail_state_ptr(dev), _stream(dev)), "eps_radix_sort_by_u")
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_radix_sort_workspace_bytes(n))
+        _call("eps_radix_sort_by_u", dev, keys, n, n_dev, int(id_bits), int(v_block_shift), out, wsp, wsb, _tail_addr(dev),
+              timed=("sort_pairs_by_u", n))
     return out
 
 
@@ -1487,100 +1351,33 @@ def radix_sort_rows(sel_keys: torch.Tensor, sel_vals: torch.Tensor, m_dev, k: in
     -> (pairs int64 [2, cap] as (u; v), scores float32 [cap], n_rows 1-element int64 device tensor) with cap = min(k, 2 len);
     the first n_rows = min(k, 2 m) columns are the rows of the declared order, the rest undefined."""
     dev = _need_gpu(sel_keys, sel_vals, perm)
-    _chk(sel_keys, torch.int64, "sel_keys"); _chk(sel_vals, torch.float32, "sel_vals"); _chk(perm, torch.int64, "perm")
+    _chk(_I64, sel_keys=sel_keys, perm=perm, m_dev=m_dev); _chk(_F32, sel_vals=sel_vals)
     m_max, k = sel_keys.numel(), int(k)
     cap = min(k, 2 * m_max)
-    pairs = torch.empty((2, cap), dtype=torch.int64, device=dev)
-    scores = torch.empty(cap, dtype=torch.float32, device=dev)
-    n_rows = torch.zeros(1, dtype=torch.int64, device=dev) if cap == 0 else torch.empty(1, dtype=torch.int64, device=dev)
+    pairs = torch.empty((2, cap), dtype=_I64, device=dev)
+    scores = torch.empty(cap, dtype=_F32, device=dev)
+    n_rows = torch.zeros(1, dtype=_I64, device=dev) if cap == 0 else torch.empty(1, dtype=_I64, device=dev)
     if cap:
-        lib = _lib.load()
-        with torch.cuda.device(dev), _timed(dev, "select_rows", m_max):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_radix_sort_workspace_bytes(2 * m_max))
-            _lib.check(lib.eps_radix_sort_rows(_ptr(sel_keys), _ptr(sel_vals), m_max, _dev_count(m_dev), k, int(id_bits), _ptr(perm),
-                                               _ptr(pairs), cap, _ptr(scores), _ptr(n_rows), wsp, wsb, _tail_state_ptr(dev), _stream(dev)),
-                       "eps_radix_sort_rows")
+        _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_radix_sort_workspace_bytes(2 * m_max))
+        _call("eps_radix_sort_rows", dev, sel_keys, sel_vals, m_max, m_dev, k, int(id_bits), perm, pairs, cap, scores, n_rows, wsp, wsb,
+              _tail_addr(dev), timed=("select_rows", m_max))
     return pairs, scores, n_rows
 
 
 def rescore_runs_dev(rowptr, col, fixw: torch.Tensor, n_nodes: int, keys_by_u: torch.Tensor, n_dev: torch.Tensor) -> torch.Tensor:
     """``rescore_runs`` over the first min(*n_dev, len) keys (eps_rescore_runs_dev); the other outputs are undefined."""
     dev = _need_gpu(rowptr, col, fixw, keys_by_u, n_dev)
-    _chk(keys_by_u, torch.int64, "keys_by_u"); _chk(fixw, torch.int64, "fixw"); _chk(n_dev, torch.int64, "n_dev")
-    out = torch.empty(keys_by_u.numel(), dtype=torch.float32, device=dev)
+    _csr(rowptr, col); _chk(_I64, keys_by_u=keys_by_u, fixw=fixw, n_dev=n_dev)
+    out = torch.empty(keys_by_u.numel(), dtype=_F32, device=dev)
     if keys_by_u.numel():
-        with torch.cuda.device(dev), _timed(dev, "rescore_runs", keys_by_u.numel()):
-            _lib.check(_lib.load().eps_rescore_runs_dev(_ptr(rowptr), _ptr(col), _ptr(fixw), int(n_nodes), _ptr(keys_by_u), keys_by_u.numel(),
-                                                        _ptr(n_dev), _ptr(out), _stream(dev)), "eps_rescore_runs_dev")
+        _call("eps_rescore_runs_dev", dev, rowptr, col, fixw, int(n_nodes), keys_by_u, keys_by_u.numel(), n_dev, out,
+              timed=("rescore_runs", keys_by_u.numel()))
     return out
-
-
-def select_rows_pairs(sel_keys: torch.Tensor, sel_vals: torch.Tensor, k: int, id_bits: int = 32,
-                      perm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``select_rows`` with the rows written as the proposal tensor itself: (pairs int64 [2, min(k, 2 m)] as (u; v), scores)
-    (eps_select_topk_rows_pairs) -- no tensor ops over the K rows afterwards."""
-    dev = _need_gpu(sel_keys, sel_vals, perm)
-    _chk(sel_keys, torch.int64, "sel_keys"); _chk(sel_vals, torch.float32, "sel_vals"); _chk(perm, torch.int64, "perm")
-    m, k = sel_keys.numel(), int(k)
-    take = min(k, 2 * m)
-    pairs = torch.empty((2, take), dtype=torch.int64, device=dev)
-    out_v = torch.empty(take, dtype=torch.float32, device=dev)
-    if take:
-        lib = _lib.load()
-        with torch.cuda.device(dev), _timed(dev, "select_rows", m):
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_select_topk_rows_workspace_bytes(m))
-            _lib.check(lib.eps_select_topk_rows_pairs(_ptr(sel_keys), _ptr(sel_vals), m, k, int(id_bits), _ptr(perm), _ptr(pairs), take,
-                                                      _ptr(out_v), wsp, wsb, _stream(dev)), "eps_select_topk_rows_pairs")
-    return pairs, out_v
-
-
-_SELECT_WS = {}
-
-
-def _aligned_ws(dev, n_bytes: int):
-    """(tensor, 256-byte aligned pointer, bytes from there) of a grow-only per-device scratch."""
-    need = (int(n_bytes) + 7) // 8 + 32
-    key = (dev.type, dev.index)
-    if key not in _SELECT_WS or _SELECT_WS[key].numel() < need:
-        _SELECT_WS.pop(key, None)
-        _SELECT_WS[key] = torch.empty(int(need * 1.25), dtype=torch.int64, device=dev)
-    ws = _SELECT_WS[key]
-    off = (-ws.data_ptr()) % 256
-    return ws, ctypes.c_void_p(ws.data_ptr() + off), ws.numel() * 8 - off
-
-
-def select_topk(keys: torch.Tensor, vals: torch.Tensor, k: int, id_bits: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The k best DIRECTED rows (score descending, key ascending) of a list of unordered survivors of ``filter_scan``
-    (key = v << 32 | u, u < v; no -1 slots): (keys int64, scores float32), sorted.  eps_select_topk_cut (radix select of the
-    cut + compaction) -> one host read of the count -> eps_select_topk_rows (mirror + stable radix sorts).  ``id_bits``:
-    every node id is below 2**id_bits (fewer sort passes)."""
-    dev = _need_gpu(keys, vals)
-    _chk(keys, torch.int64, "keys"); _chk(vals, torch.float32, "vals")
-    n, k = keys.numel(), int(k)
-    if vals.numel() != n:
-        raise _lib.EpsError("select_topk: keys and vals differ in length")
-    lib = _lib.load()
-    sel_k = torch.empty(n, dtype=torch.int64, device=dev)
-    sel_v = torch.empty(n, dtype=torch.float32, device=dev)
-    n_sel = torch.zeros(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _, wsp, wsb = _aligned_ws(dev, lib.eps_select_topk_cut_workspace_bytes())
-        _lib.check(lib.eps_select_topk_cut(_ptr(keys), _ptr(vals), n, k, _ptr(sel_k), _ptr(sel_v), _ptr(n_sel), wsp, wsb,
-                                           _stream(dev)), "eps_select_topk_cut")
-        m = int(n_sel.item())
-        take = min(k, 2 * m)
-        out_k = torch.empty(take, dtype=torch.int64, device=dev)
-        out_v = torch.empty(take, dtype=torch.float32, device=dev)
-        if take:
-            _, wsp, wsb = _aligned_ws(dev, lib.eps_select_topk_rows_workspace_bytes(m))
-            _lib.check(lib.eps_select_topk_rows(_ptr(sel_k), _ptr(sel_v), m, k, int(id_bits), _ptr(out_k), _ptr(out_v), wsp, wsb,
-                                                _stream(dev)), "eps_select_topk_rows")
-    return out_k, out_v
 
 
 def pack_keys(score: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: int = 0) -> torch.Tensor:
     dev = _need_gpu(score, ids)
-    _chk(score, torch.float32, "score"); _chk(ids, torch.int64, "ids")
+    _chk(_F32, score=score); _chk(_I64, ids=ids)
     # the key holds the id in its low 32 bits: an id the kernel would truncate aliases another candidate's key
     if ids is not None and ids.numel():
         lo, hi = torch.aminmax(ids)
@@ -1589,19 +1386,16 @@ def pack_keys(score: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: 
                                 "(use shard-relative ids and merge_ranked_lists for longer candidate lists)")
     elif ids is None and (id_base < 0 or id_base + score.numel() > 1 << 32):
         raise _lib.EpsError("pack_keys: id_base + n exceeds the 32-bit id field of the key")
-    keys = torch.empty(score.numel(), dtype=torch.int64, device=dev)  # bit pattern of the uint64 key
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_pack_keys(_ptr(score), _ptr(ids), id_base, score.numel(), _ptr(keys),
-                                             _stream(dev)), "eps_pack_keys")
+    keys = torch.empty(score.numel(), dtype=_I64, device=dev)  # bit pattern of the uint64 key
+    _call("eps_pack_keys", dev, score, ids, id_base, score.numel(), keys)
     return keys
 
 
 def unpack_keys(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     dev = _need_gpu(keys)
+    _chk(_I64, keys=keys)
     n = keys.numel()
-    score = torch.empty(n, dtype=torch.float32, device=dev)
-    ids = torch.empty(n, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eps_unpack_keys(_ptr(keys), n, _ptr(score), _ptr(ids), _stream(dev)),
-                   "eps_unpack_keys")
+    score = torch.empty(n, dtype=_F32, device=dev)
+    ids = torch.empty(n, dtype=_I64, device=dev)
+    _call("eps_unpack_keys", dev, keys, n, score, ids)
     return score, ids

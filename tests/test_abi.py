@@ -30,8 +30,48 @@ def test_library_exports_every_declared_symbol(eps):
     assert lib.eps_version() == eps._lib.ABI_VERSION == 7
 
 
+def _kind(c_type):
+    """The ctypes-level kind of a C type of the header: every pointer is one kind; int32_t and int are one ctypes type here."""
+    c_type = re.sub(r"\bconst\b", "", c_type).strip()
+    if "*" in c_type or "[" in c_type:
+        return "pointer"
+    return {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint32_t": "uint32", "float": "float", "double": "double"}[c_type]
+
+
+def _ctypes_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int32: "int32", ctypes.c_int: "int32", ctypes.c_int64: "int64", ctypes.c_uint32: "uint32",
+            ctypes.c_float: "float", ctypes.c_double: "double"}[t]
+
+
+def declared_prototypes():
+    """name -> (return kind, [argument kinds]) of every ``ret name(args);`` of the header, comments stripped."""
+    text = open(os.path.join(ROOT, "include", "eps_abi.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    protos = {}
+    for ret, name, args in re.findall(r"^[ \t]*((?:const[ \t]+)?\w+[ \t\*]+)(eps_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        args = [a.strip() for a in args.split(",")] if args.strip() not in ("", "void") else []
+        # an argument is "type name": drop the trailing identifier, keep any * that sticks to it
+        kinds = [_kind(re.sub(r"\b[A-Za-z_]\w*\s*(\[\s*\])?$", lambda m: m.group(1) or "", a)) for a in args]
+        assert name not in protos, f"{name} declared twice"
+        protos[name] = (_kind(ret), kinds)
+    return protos
+
+
 def test_python_signatures_cover_header(eps):
+    """_lib.SIGNATURES mirrors the header by hand: same names, and per symbol the same return kind, the same number of arguments
+    and the same kind per argument (a wrong width or a missing argument there corrupts a call silently)."""
     assert sorted(eps._lib.SIGNATURES) == declared_symbols()
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols(), "a declaration of eps_abi.h was not parsed as a prototype"
+    for name, (ret, kinds) in sorted(protos.items()):
+        res, args = eps._lib.SIGNATURES[name]
+        assert _ctypes_kind(res) == ret, f"{name}: returns {ret} in the header, {res.__name__} in SIGNATURES"
+        assert len(args) == len(kinds), f"{name}: {len(kinds)} arguments in the header, {len(args)} in SIGNATURES"
+        for i, (a, kd) in enumerate(zip(args, kinds)):
+            assert _ctypes_kind(a) == kd, f"{name}: argument {i} is {kd} in the header, {a.__name__} in SIGNATURES"
 
 
 def test_argument_validation_without_gpu(eps):

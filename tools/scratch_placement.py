@@ -17,8 +17,8 @@ def run():
     torch.cuda.synchronize(); return time.perf_counter() - t0
 for rep in range(6):
     t = [run() for _ in range(2)]
-    print(f"scratch #{rep}: ptr {ops._EXPAND_WS[('cuda', 0)].data_ptr():#x}  {t[0]*1e3:.1f} ms {t[1]*1e3:.1f} ms", flush=True)
-    ops._EXPAND_WS.clear(); torch.cuda.empty_cache()
+    print(f"scratch #{rep}: ptr {ops._SCRATCH[('expand', 'cuda', 0)].data_ptr():#x}  {t[0]*1e3:.1f} ms {t[1]*1e3:.1f} ms", flush=True)
+    ops._SCRATCH.clear(); torch.cuda.empty_cache()
     hog = [torch.empty(1 << 30, dtype=torch.uint8, device=dev) for _ in range(rep * 7)]   # shift where the next scratch lands
     ops._expand_scratch(dev, int(ops._lib.load().eps_expand_workspace_bytes(mp)))
     del hog
