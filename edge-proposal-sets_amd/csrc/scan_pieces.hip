@@ -1452,6 +1452,42 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
 // wave stages the shorter row in its own 2 KiB of LDS (no barrier: wave-private), spreads the other row over its lanes and
 // looks every entry up by a binary search in LDS.  Same exact float64 sums.
 #define RSS_THREADS 256
+#define RSS_TRIPS 4             // windows of 64 keys a wave is given, where the list is long enough (the grid is sized from this)
+
+// One short pair by the whole wave (u, v wave-uniform; stage = the wave's RS_SHORT words of LDS) -> its score, in every lane.
+static __device__ __forceinline__ float rss_score_pair(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                       const int64_t *__restrict__ fixw, int32_t *stage, int lane, int32_t u, int32_t v)
+{
+    const int64_t ub = rowptr[u], ue = rowptr[u + 1];
+    const int64_t vb = rowptr[v], ve = rowptr[v + 1];
+    const bool u_short = ue - ub <= ve - vb;
+    const int64_t sb = u_short ? ub : vb, se = u_short ? ue : ve;       // staged (the shorter: <= RS_SHORT entries)
+    const int64_t lb = u_short ? vb : ub, le = u_short ? ve : ue;       // spread over the lanes
+    const int ns = (int)(se - sb);
+    int pow2 = 1;
+    while (pow2 < ns) pow2 <<= 1;
+    for (int i = lane; i < pow2; i += 64) stage[i] = i < ns ? col[sb + i] : 0x7fffffff;
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    long long acc = 0ll;
+    for (int64_t i0 = lb; i0 < le; i0 += 64) {
+        const int64_t i = i0 + lane;
+        const int32_t w = i < le ? col[i] : -1;
+        int lo = 0;                                           // last position with stage[pos] <= w
+        for (int step = pow2 >> 1; step >= 1; step >>= 1)
+            if (stage[lo + step] <= w) lo += step;
+        if (w >= 0 && ns > 0 && stage[lo] == w) acc += (long long)fixw[w];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the next pair overwrites the staged row)
+    return (float)((double)acc * (1.0 / (double)(1ll << 40)));
+}
+
+// The search for the short pairs, 64 keys a trip: every lane loads ITS key and the two rowptr words of its u -- 64 chains of two
+// dependent latencies in flight at once -- a ballot says which lanes hold a short pair, and the wave scores those one after the
+// other (the body is wave-cooperative: u and v come from the owning lane).  One key a trip, read wave-uniformly, was 173 us of
+// bare latency per call on the bench graph: the survivors of a K = 4 M scan are pairs of hubs, NONE of its 2 M pairs is short,
+// and the pass is a filter over 16 MB of keys.  Waves are independent: no barrier, no atomics.
 __global__ __launch_bounds__(RSS_THREADS) void rescore_short_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                   const int64_t *__restrict__ fixw, const int64_t *__restrict__ keys,
                                                                   int64_t n, float *__restrict__ out, const int64_t *__restrict__ n_dev)
@@ -1465,33 +1501,21 @@ __global__ __launch_bounds__(RSS_THREADS) void rescore_short_kernel(const int64_
     int32_t *stage = s_stage[wib];
     const int64_t wave = (int64_t)blockIdx.x * (RSS_THREADS / 64) + wib;
     const int64_t n_waves = (int64_t)gridDim.x * (RSS_THREADS / 64);
-    for (int64_t pi = wave; pi < n; pi += n_waves) {
-        const int64_t key = keys[pi];
-        const int32_t u = (int32_t)(key >> 32), v = (int32_t)(key & 0xFFFFFFFFll);
-        const int64_t ub = rowptr[u], ue = rowptr[u + 1];
-        if (ue - ub > RS_SHORT) continue;                      // rescore_runs_kernel's
-        const int64_t vb = rowptr[v], ve = rowptr[v + 1];
-        const bool u_short = ue - ub <= ve - vb;
-        const int64_t sb = u_short ? ub : vb, se = u_short ? ue : ve;       // staged (the shorter: <= RS_SHORT entries)
-        const int64_t lb = u_short ? vb : ub, le = u_short ? ve : ue;       // spread over the lanes
-        const int ns = (int)(se - sb);
-        int pow2 = 1;
-        while (pow2 < ns) pow2 <<= 1;
-        for (int i = lane; i < pow2; i += 64) stage[i] = i < ns ? col[sb + i] : 0x7fffffff;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        long long acc = 0ll;
-        for (int64_t i0 = lb; i0 < le; i0 += 64) {
-            const int64_t i = i0 + lane;
-            const int32_t w = i < le ? col[i] : -1;
-            int lo = 0;                                           // last position with stage[pos] <= w
-            for (int step = pow2 >> 1; step >= 1; step >>= 1)
-                if (stage[lo + step] <= w) lo += step;
-            if (w >= 0 && ns > 0 && stage[lo] == w) acc += (long long)fixw[w];
+    for (int64_t p0 = wave * 64; p0 < n; p0 += n_waves * 64) {
+        int32_t my_u = 0, my_v = 0;
+        bool is_short = false;
+        if (p0 + lane < n) {
+            const int64_t key = keys[p0 + lane];
+            my_u = (int32_t)(key >> 32);
+            my_v = (int32_t)(key & 0xFFFFFFFFll);
+            is_short = rowptr[my_u + 1] - rowptr[my_u] <= RS_SHORT;       // (the others are rescore_runs_kernel's)
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-        if (lane == 0) out[pi] = (float)((double)acc * (1.0 / (double)(1ll << 40)));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the next pair overwrites the staged row)
+        for (unsigned long long todo = __ballot(is_short); todo; todo &= todo - 1) {
+            const int owner = __builtin_ctzll(todo);
+            const int32_t u = __builtin_amdgcn_readlane(my_u, owner), v = __builtin_amdgcn_readlane(my_v, owner);
+            const float score = rss_score_pair(rowptr, col, fixw, stage, lane, u, v);
+            if (lane == 0) out[p0 + owner] = score;
+        }
     }
 }
 
@@ -1571,7 +1595,9 @@ static int rescore_runs_launch(const int64_t *rowptr, const int32_t *col, const 
     hipLaunchKernelGGL(rescore_runs_kernel, dim3((unsigned)blocks), dim3(RS_THREADS), lds, s, rowptr, col, fixw, (int32_t)n_nodes, keys,
                        n, out, counter, n_dev);
     {
-        int64_t sb = (n + RSS_THREADS / 64 - 1) / (RSS_THREADS / 64);
+        // (a wave per RSS_TRIPS windows of 64 keys: a short list does not start waves that find no window)
+        const int64_t per_block = (int64_t)(RSS_THREADS / 64) * 64 * RSS_TRIPS;
+        int64_t sb = (n + per_block - 1) / per_block;
         const int64_t scap = (int64_t)eps_num_cus() * 8;
         if (sb > scap) sb = scap;
         hipLaunchKernelGGL(rescore_short_kernel, dim3((unsigned)sb), dim3(RSS_THREADS), 0, s, rowptr, col, fixw, keys, n, out, n_dev);
