@@ -97,22 +97,16 @@ int eps_take_counters8(unsigned int **counters, hipStream_t stream, const char *
 // for each of the larger ones (the rocPRIM sorts) inside whatever step happens to come first -- and filter.py is one fresh
 // process per graph (submit_job.py:20-21).  eps_warm_up launches one empty kernel per unit on a stream of its own and waits for
 // them: the host calls it from a background thread while the process is still reading its dataset.
-extern "C" void eps_warm_graph_prep(void *stream);
-extern "C" void eps_warm_scan_pieces(void *stream);
-extern "C" void eps_warm_scan_heads(void *stream);
-extern "C" void eps_warm_pair_intersect(void *stream);
-extern "C" void eps_warm_pair_grouped(void *stream);
-extern "C" void eps_warm_expand_score(void *stream);
-extern "C" void eps_warm_filter_scan(void *stream);
-extern "C" void eps_warm_spmm_csr(void *stream);
-extern "C" void eps_warm_gemm_f32(void *stream);
-extern "C" void eps_warm_dense_cn(void *stream);
-extern "C" void eps_warm_mlp_decode(void *stream);
-extern "C" void eps_warm_topk_keys(void *stream);
-extern "C" void eps_warm_topk_select(void *stream);
-extern "C" void eps_warm_tail_sort(void *stream);
-extern "C" void eps_warm_cosine_cn(void *stream);
-extern "C" void eps_warm_cosine_cn_bwd(void *stream);
+// The units, once: every source of the library but this one (csrc/Makefile: SRCS) defines eps_warm_<unit>; the declarations
+// and the calls below both come from this list (tests/test_abi.py holds it to SRCS).
+#define EPS_UNITS(X) \
+    X(graph_prep) X(scan_pieces) X(scan_tables) X(scan_heads) X(rescore) \
+    X(pair_intersect) X(pair_grouped) X(expand_score) X(filter_scan) X(spmm_csr) \
+    X(gemm_f32) X(dense_cn) X(mlp_decode) X(topk_keys) X(topk_select) \
+    X(tail_sort) X(katz_pairs) X(cosine_cn) X(cosine_cn_bwd)
+
+#define EPS_DECLARE_WARM(unit) extern "C" void eps_warm_##unit(void *stream);
+EPS_UNITS(EPS_DECLARE_WARM)
 
 extern "C" int eps_warm_up(void)
 {
@@ -121,22 +115,8 @@ extern "C" int eps_warm_up(void)
         eps_set_error("eps_warm_up: cannot create a stream");
         return EPS_ELAUNCH;
     }
-    eps_warm_graph_prep(s);
-    eps_warm_scan_pieces(s);
-    eps_warm_scan_heads(s);
-    eps_warm_pair_intersect(s);
-    eps_warm_pair_grouped(s);
-    eps_warm_expand_score(s);
-    eps_warm_filter_scan(s);
-    eps_warm_spmm_csr(s);
-    eps_warm_gemm_f32(s);
-    eps_warm_dense_cn(s);
-    eps_warm_mlp_decode(s);
-    eps_warm_topk_keys(s);
-    eps_warm_topk_select(s);
-    eps_warm_tail_sort(s);
-    eps_warm_cosine_cn(s);
-    eps_warm_cosine_cn_bwd(s);
+#define EPS_CALL_WARM(unit) eps_warm_##unit(s);
+    EPS_UNITS(EPS_CALL_WARM)
     const hipError_t e = hipStreamSynchronize(s);
     (void)hipStreamDestroy(s);
     if (e != hipSuccess) {

@@ -310,3 +310,7 @@ extern "C" int eps_katz_pair_scores(const int64_t *rowptr, const int32_t *col, c
     EPS_CHECK_LAUNCH("eps_katz_pair_scores");
     return EPS_OK;
 }
+
+// (one empty kernel per translation unit: launching it makes the HIP runtime load this unit's code object -- eps_warm_up)
+__global__ void katz_pairs_warm_kernel() {}
+extern "C" void eps_warm_katz_pairs(void *stream) { hipLaunchKernelGGL(katz_pairs_warm_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream); }

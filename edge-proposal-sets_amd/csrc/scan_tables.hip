@@ -1,0 +1,357 @@
+// The per-graph and per-weight-table builders of the one-pass scan (scan_pieces.hip), gfx950: small one-shot kernels, each followed
+// by its entry point.  Per graph: the id windows (bounds), the cuts of every row at the window ends, the two-hop paths of every
+// column per window.  Per weight table: the screening weights, the row sums that bound a pair's sum, the row records.  Per plan
+// table (eps_scan_plan, scan_pieces.hip): the column pack.  What the tables are for is told at the head of scan_pieces.hip.
+#include "eps_common.h"
+#include "scan_common.h"
+
+__device__ __forceinline__ uint32_t sp_wave_sum(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_readlane(sp_wave_incl_scan((int)x), 63);
+}
+
+extern "C" int32_t eps_scan_windows(void) { return SP_M; }
+
+// The window boundaries: M windows of equal stored-entry mass -- bounds[k] = 1 + the first node whose row ENDS at or beyond
+// k x nnz / M (rowptr is the prefix of the degrees), made non-decreasing; bounds[0] = 0, bounds[M] = N.  One small block.
+__global__ __launch_bounds__(64) void sp_bounds_kernel(const int64_t *__restrict__ rowptr, int64_t n_nodes, int32_t *__restrict__ bounds)
+{
+    __shared__ int32_t b[SP_M + 1];
+    const int k = threadIdx.x;
+    if (k <= SP_M) {
+        int64_t r = k == 0 ? 0 : n_nodes;
+        if (k > 0 && k < SP_M) {
+            const double target = (double)k * ((double)rowptr[n_nodes] / (double)SP_M);
+            int64_t lo = 0, hi = n_nodes;                     // smallest i with rowptr[i + 1] >= target (n_nodes if none)
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if ((double)rowptr[mid + 1] >= target) hi = mid; else lo = mid + 1;
+            }
+            r = lo + 1 < n_nodes ? lo + 1 : n_nodes;
+        }
+        b[k] = (int32_t)r;
+    }
+    __syncthreads();
+    if (k == 0) {
+        int32_t m = 0;
+        for (int i = 0; i <= SP_M; ++i) {
+            m = b[i] > m ? b[i] : m;
+            bounds[i] = m;
+        }
+    }
+}
+
+extern "C" int eps_scan_bounds(const int64_t *rowptr, int64_t n_nodes, int32_t *bounds, void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0 && n_nodes < (1ll << 31) && rowptr && bounds, "eps_scan_bounds: bad argument");
+    hipLaunchKernelGGL(sp_bounds_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rowptr, n_nodes, bounds);
+    EPS_CHECK_LAUNCH("eps_scan_bounds");
+    return EPS_OK;
+}
+
+// cuts[w][k] = number of entries of row w with id < bounds[k + 1], k = 0 .. SP_M - 1 (uint16: needs max degree < 65536)
+__global__ void sp_cuts_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t n_nodes,
+                               const int32_t *__restrict__ bounds, uint16_t *__restrict__ cuts)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes * SP_M; i += stride) {
+        const int64_t w = i / SP_M;
+        const int k = (int)(i % SP_M);
+        const int32_t bound = bounds[k + 1];
+        int64_t lo = rowptr[w], hi = rowptr[w + 1];
+        const int64_t wb = lo;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (col[mid] < bound) lo = mid + 1; else hi = mid;
+        }
+        cuts[i] = (uint16_t)(lo - wb);
+    }
+}
+
+extern "C" int eps_scan_cuts(const int64_t *rowptr, const int32_t *col, int64_t n_nodes, const int32_t *bounds, uint16_t *cuts,
+                             void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0, "eps_scan_cuts: negative size");
+    if (n_nodes == 0) return EPS_OK;
+    EPS_REQUIRE(rowptr && col && bounds && cuts, "eps_scan_cuts: null pointer");
+    EPS_REQUIRE(((uintptr_t)cuts & 15) == 0, "eps_scan_cuts: cuts must be 16-byte aligned");
+    int64_t blocks = (n_nodes * SP_M + 255) / 256;
+    const int64_t cap = (int64_t)eps_num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_cuts_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, n_nodes, bounds, cuts);
+    EPS_CHECK_LAUNCH("eps_scan_cuts");
+    return EPS_OK;
+}
+
+// wpaths[v][k] = two-hop half paths of column v that end in id window k: the sum over v's rows of the row head's entries
+// inside the window (exact, from the cut table).  One wave per column; the scan's planner then reads 128 bytes per column
+// instead of a cut row per (column, neighbour).
+__global__ void sp_window_paths_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                       const int32_t *__restrict__ revpos, const uint16_t *__restrict__ cuts, int64_t n_nodes,
+                                       const uint2 *__restrict__ heads, uint32_t *__restrict__ wpaths,
+                                       const int32_t *__restrict__ columns, int64_t n_columns)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    // (columns given: only those rows of the table are computed -- the bar sample of a one-shot run, r06)
+    const int64_t count = columns ? n_columns : n_nodes;
+    for (int64_t idx = wave; idx < count; idx += n_waves) {
+        const int64_t v = columns ? (int64_t)columns[idx] : idx;
+        const int64_t b = rowptr[v] + (heads ? (int64_t)heads[v].x : 0ll), e = rowptr[v + 1];      // (a skipped head is not walked)
+        uint32_t cnt[SP_M];
+#pragma unroll
+        for (int k = 0; k < SP_M; ++k) cnt[k] = 0u;
+        for (int64_t i = b + lane; i < e; i += 64) {
+            const uint32_t rev = (uint32_t)revpos[i];
+            const uint4 *row = (const uint4 *)(cuts + (size_t)col[i] * SP_M);
+            uint32_t prev = 0u;
+#pragma unroll
+            for (int q = 0; q < SP_M / 8; ++q) {
+                const uint4 c = row[q];
+                const uint32_t wds[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    uint32_t a = wds[h] & 0xFFFFu, bb = wds[h] >> 16;
+                    a = a < rev ? a : rev;
+                    bb = bb < rev ? bb : rev;
+                    cnt[q * 8 + h * 2] += a - prev;
+                    cnt[q * 8 + h * 2 + 1] += bb - a;
+                    prev = bb;
+                }
+            }
+        }
+        uint32_t mine = 0u;
+#pragma unroll
+        for (int k = 0; k < SP_M; ++k) {
+            const uint32_t s = sp_wave_sum(cnt[k]);
+            if (lane == k) mine = s;
+        }
+        if (lane < SP_M) wpaths[v * SP_M + lane] = mine;
+    }
+}
+
+extern "C" int eps_scan_window_paths(const int64_t *rowptr, const int32_t *col, const int32_t *revpos, const uint16_t *cuts,
+                                     int64_t n_nodes, const uint32_t *heads_or_null, uint32_t *wpaths, void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0, "eps_scan_window_paths: negative size");
+    if (n_nodes == 0) return EPS_OK;
+    EPS_REQUIRE(rowptr && col && revpos && cuts && wpaths && ((uintptr_t)cuts & 15) == 0, "eps_scan_window_paths: null or misaligned pointer");
+    int64_t blocks = (n_nodes + 3) / 4;
+    const int64_t cap = (int64_t)eps_num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_window_paths_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, revpos, cuts,
+                       n_nodes, (const uint2 *)heads_or_null, wpaths, (const int32_t *)nullptr, (int64_t)0);
+    EPS_CHECK_LAUNCH("eps_scan_window_paths");
+    return EPS_OK;
+}
+
+// The same table for the listed columns only (rows of other columns are left as they are): the bar sample of a one-shot run scans
+// ~1000 columns with the launch planning them itself -- the whole-graph table (0.7 ms) and the plan built from it (1.0 ms) are then
+// only built when a launch without skipped heads wants them.
+extern "C" int eps_scan_window_paths_columns(const int64_t *rowptr, const int32_t *col, const int32_t *revpos, const uint16_t *cuts,
+                                             int64_t n_nodes, const int32_t *columns, int64_t n_columns, uint32_t *wpaths, void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0 && n_columns >= 0, "eps_scan_window_paths_columns: negative size");
+    if (n_nodes == 0 || n_columns == 0) return EPS_OK;
+    EPS_REQUIRE(rowptr && col && revpos && cuts && columns && wpaths, "eps_scan_window_paths_columns: null pointer");
+    EPS_REQUIRE(((uintptr_t)cuts & 15) == 0, "eps_scan_window_paths_columns: cuts must be 16-byte aligned");
+    int64_t blocks = (n_columns + 3) / 4;
+    const int64_t cap = (int64_t)eps_num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_window_paths_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, revpos, cuts,
+                       n_nodes, (const uint2 *)nullptr, wpaths, columns, n_columns);
+    EPS_CHECK_LAUNCH("eps_scan_window_paths_columns");
+    return EPS_OK;
+}
+
+// fx32[i] = max(1, ceil(fixw[i] / 2^(40 - shift))): the node weights of the scan in the screening fixed point, rounded UP
+__global__ void sp_screen_weights_kernel(const int64_t *__restrict__ fixw, int64_t n, int shift, uint32_t *__restrict__ fx32,
+                                         unsigned int *__restrict__ bad)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int down = 40 - shift;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const long long f = fixw[i];
+        if (f < 0) {
+            atomicOr(bad, 1u);                        // negative weights: the sums are no upper bounds any more
+            fx32[i] = 1u;
+            continue;
+        }
+        const unsigned long long q = ((unsigned long long)f + ((1ull << down) - 1ull)) >> down;
+        if (q > 0xFFFFFFFFull) atomicOr(bad, 2u);
+        fx32[i] = q ? (uint32_t)q : 1u;
+    }
+}
+
+extern "C" int eps_scan_screen_weights(const int64_t *fixw, int64_t n, int32_t shift, uint32_t *fx32, uint32_t *bad,
+                                       void *stream)
+{
+    EPS_REQUIRE(n >= 0 && shift >= 0 && shift <= 40, "eps_scan_screen_weights: bad argument");
+    EPS_REQUIRE(bad, "eps_scan_screen_weights: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess) {
+        eps_set_error("eps_scan_screen_weights: cannot clear the flag");
+        return EPS_ELAUNCH;
+    }
+    if (n == 0) return EPS_OK;
+    EPS_REQUIRE(fixw && fx32, "eps_scan_screen_weights: null pointer");
+    int64_t blocks = (n + 255) / 256;
+    const int64_t cap = (int64_t)eps_num_cus() * 8;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_screen_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fixw, n, (int)shift, fx32, bad);
+    EPS_CHECK_LAUNCH("eps_scan_screen_weights");
+    return EPS_OK;
+}
+
+// ssum[v] = sum of the screening weights over row v, clamped to 2^31 - 1: no pair with endpoint v sums to more (the bound the
+// packed and 16-bit direct pieces are sized by).  One wave per row; on the way: the largest ssum per id window (-> smax, the
+// suffix maxima, by sp_suffix_max_kernel) and the smallest screening weight of a node with at least two neighbours (only such
+// a node is ever a common neighbour: the floor under a path's term that bounds the number of paths behind a sum).
+__global__ __launch_bounds__(256) void sp_row_sums_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                          const uint32_t *__restrict__ fx32, const int32_t *__restrict__ bounds,
+                                                          int64_t n_nodes, uint32_t *__restrict__ ssum, uint32_t *__restrict__ wmax,
+                                                          uint32_t *__restrict__ min_fx)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= n_nodes) return;
+    const int64_t b = rowptr[v], e = rowptr[v + 1];
+    unsigned long long acc = 0ull;
+    for (int64_t i = b + lane; i < e; i += 64) acc += fx32[col[i]];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    if (lane == 0) {
+        const uint32_t sv = acc < 0x7FFFFFFFull ? (uint32_t)acc : 0x7FFFFFFFu;
+        ssum[v] = sv;
+        int k = 0;                                            // the window of v: the last k with bounds[k] <= v
+        for (int step = 32; step >= 1; step >>= 1)
+            if (k + step < SP_M && bounds[k + step] <= (int32_t)v) k += step;
+        // (look before the atomic: the cells only move one way, so a value that cannot move them needs no atomic -- the last
+        //  window holds half the nodes, and 300 k atomics on one address would take 30 ms)
+        if (sv > __atomic_load_n(&wmax[k], __ATOMIC_RELAXED)) atomicMax(&wmax[k], sv);
+        if (e - b >= 2) {
+            const uint32_t fv = fx32[v];
+            if (fv < __atomic_load_n(min_fx, __ATOMIC_RELAXED)) atomicMin(min_fx, fv);
+        }
+    }
+}
+
+__global__ void sp_suffix_max_kernel(const uint32_t *__restrict__ wmax, uint32_t *__restrict__ smax)
+{
+    if (threadIdx.x == 0) {
+        uint32_t m = 0u;
+        smax[SP_M] = 0u;
+        for (int k = SP_M - 1; k >= 0; --k) {
+            m = wmax[k] > m ? wmax[k] : m;
+            smax[k] = m;
+        }
+    }
+}
+
+extern "C" int eps_scan_row_sums(const int64_t *rowptr, const int32_t *col, const uint32_t *fx32, const int32_t *bounds,
+                                 int64_t n_nodes, uint32_t *ssum, uint32_t *smax, uint32_t *min_fx, void *workspace, void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0 && n_nodes < (1ll << 31), "eps_scan_row_sums: bad size");
+    EPS_REQUIRE(smax && min_fx && workspace, "eps_scan_row_sums: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(workspace, 0, SP_M * sizeof(uint32_t), s) != hipSuccess || hipMemsetAsync(min_fx, 0xFF, sizeof(uint32_t), s) != hipSuccess) {
+        eps_set_error("eps_scan_row_sums: cannot clear the workspace");
+        return EPS_ELAUNCH;
+    }
+    if (n_nodes > 0) {
+        EPS_REQUIRE(rowptr && col && fx32 && bounds && ssum, "eps_scan_row_sums: null pointer");
+        hipLaunchKernelGGL(sp_row_sums_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, s, rowptr, col, fx32, bounds, n_nodes,
+                           ssum, (uint32_t *)workspace, min_fx);
+    }
+    hipLaunchKernelGGL(sp_suffix_max_kernel, dim3(1), dim3(64), 0, s, (const uint32_t *)workspace, smax);
+    EPS_CHECK_LAUNCH("eps_scan_row_sums");
+    return EPS_OK;
+}
+
+// rowrec[w * 32 + 0 .. 15] = the 32 cuts of row w, [16] = its first entry (rowptr, low word), [17] = its screening weight, rest 0:
+// one 128-byte line per node holds what the scan's walk gathers per row.
+__global__ __launch_bounds__(256) void sp_rowrec_kernel(const uint16_t *__restrict__ cuts, const int64_t *__restrict__ rowptr,
+                                                        const uint32_t *__restrict__ fx32, int64_t n_nodes, uint32_t *__restrict__ rowrec)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes * 32; i += stride) {
+        const int64_t w = i >> 5;
+        const int k = (int)(i & 31);
+        uint32_t x = 0u;
+        if (k < SP_M / 2) x = ((const uint32_t *)cuts)[w * (SP_M / 2) + k];
+        else if (k == 16) x = (uint32_t)rowptr[w];
+        else if (k == 17) x = fx32[w];
+        rowrec[i] = x;
+    }
+}
+
+extern "C" int eps_scan_row_records(const uint16_t *cuts, const int64_t *rowptr, const uint32_t *fx32, int64_t n_nodes, uint32_t *rowrec,
+                                    void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0 && n_nodes < (1ll << 31), "eps_scan_row_records: bad size");
+    if (n_nodes == 0) return EPS_OK;
+    EPS_REQUIRE(cuts && rowptr && fx32 && rowrec && ((uintptr_t)rowrec & 127) == 0 && ((uintptr_t)cuts & 3) == 0,
+                "eps_scan_row_records: null or misaligned pointer (row records are 128-byte lines)");
+    static_assert(SP_M == 32, "a row record holds 32 cuts in its first 64 bytes");
+    int64_t blocks = (n_nodes * 32 + 255) / 256;
+    const int64_t cap = (int64_t)eps_num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_rowrec_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cuts, rowptr, fx32, n_nodes, rowrec);
+    EPS_CHECK_LAUNCH("eps_scan_row_records");
+    return EPS_OK;
+}
+
+// ---- the per-column pack (r06) ---------------------------------------------------------------------------------------------
+// pack[e] for stored entry e = (v, j) of the scanned graph, CSR order (two uint4): what a single-round column's set-up wants of its
+// j-th neighbour w -- id, first entry, screening weight (row record words 16, 17), the reverse position, and the cuts of row w at
+// the ends of column v's first nine pieces (row record words 0..15, indexed by the plan's k1 - 1).  One wave per column.
+__global__ __launch_bounds__(256) void sp_pack_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                      const int32_t *__restrict__ revpos, const uint32_t *__restrict__ rowrec,
+                                                      const uint32_t *__restrict__ pptr, const uint4 *__restrict__ plan, int64_t n_nodes,
+                                                      uint4 *__restrict__ pack)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t v = wave; v < n_nodes; v += n_waves) {
+        const int64_t vb = rowptr[v], ve = rowptr[v + 1];
+        const uint32_t pb = pptr[v];
+        const int np = (int)(pptr[v + 1] - pb);
+        int k1 = 1;
+        if (lane < np && lane < 9) k1 = (int)((plan[pb + (uint32_t)lane].y >> 8) & 0xFFu);
+        int kk[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) kk[i] = __shfl(k1, i);
+        for (int64_t e = vb + lane; e < ve; e += 64) {
+            const uint32_t w = (uint32_t)col[e];
+            const uint32_t *__restrict__ rr = rowrec + (size_t)w * 32;
+            const uint16_t *__restrict__ cc = (const uint16_t *)rr;
+            uint32_t c[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) c[i] = i < np ? (uint32_t)cc[kk[i] - 1] : 0u;
+            pack[2 * e] = make_uint4(w, rr[16], rr[17], ((uint32_t)revpos[e] & 0xFFFFu) | (c[0] << 16));
+            pack[2 * e + 1] = make_uint4(c[1] | (c[2] << 16), c[3] | (c[4] << 16), c[5] | (c[6] << 16), c[7] | (c[8] << 16));
+        }
+    }
+}
+
+extern "C" int eps_scan_column_pack(const int64_t *rowptr, const int32_t *col, const int32_t *revpos, const uint32_t *rowrec,
+                                    const uint32_t *pptr, const uint32_t *plan, int64_t n_nodes, uint32_t *pack, void *stream)
+{
+    EPS_REQUIRE(n_nodes >= 0, "eps_scan_column_pack: negative size");
+    if (n_nodes == 0) return EPS_OK;
+    EPS_REQUIRE(rowptr && col && revpos && rowrec && pptr && plan && pack, "eps_scan_column_pack: null pointer");
+    EPS_REQUIRE(((uintptr_t)plan & 15) == 0 && ((uintptr_t)pack & 15) == 0 && ((uintptr_t)rowrec & 127) == 0,
+                "eps_scan_column_pack: misaligned table");
+    int64_t blocks = (n_nodes + 3) / 4;
+    const int64_t cap = (int64_t)eps_num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(sp_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, revpos, rowrec, pptr,
+                       (const uint4 *)plan, n_nodes, (uint4 *)pack);
+    EPS_CHECK_LAUNCH("eps_scan_column_pack");
+    return EPS_OK;
+}
+
+// (one empty kernel per translation unit: launching it makes the HIP runtime load this unit's code object -- eps_warm_up)
+__global__ void scan_tables_warm_kernel() {}
+extern "C" void eps_warm_scan_tables(void *stream) { hipLaunchKernelGGL(scan_tables_warm_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream); }

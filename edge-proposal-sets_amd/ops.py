@@ -641,7 +641,7 @@ def filter_scan(rowptr, col, revpos, fixw, n_nodes: int, columns: torch.Tensor, 
           columns.numel(), out.rec, ws, ws.numel() * 8, timed=("filter_scan_kernel", columns.numel()))
 
 
-# ------------------------------------------------------------------ one-pass threshold scan (csrc/scan_pieces.hip)
+# ------------------------------------------------------------------ one-pass threshold scan (csrc/scan_pieces.hip, scan_tables.hip, rescore.hip)
 def scan_windows() -> int:
     return int(_lib.load().eps_scan_windows())
 

@@ -254,7 +254,11 @@ int eps_filter_scan(const int64_t *rowptr, const int32_t *col, const int32_t *re
                     const int32_t *columns, int64_t n_columns, eps_survivors *out, void *workspace,
                     int64_t workspace_bytes, void *stream);
 
-/* ---- the same threshold scan in ONE pass over the two-hop paths (r03; csrc/scan_pieces.hip) --------------------------------
+/* ---- the same threshold scan in ONE pass over the two-hop paths (r03) ------------------------------------------------------
+ * csrc/scan_pieces.hip: the piece kernel, its planner and the launch (eps_scan_screen[_weighted], eps_scan_plan[_rewalk]);
+ * csrc/scan_tables.hip: the builders of the tables a launch reads (eps_scan_windows / _bounds / _cuts / _window_paths[_columns] /
+ * _screen_weights / _row_sums / _row_records / _column_pack); csrc/rescore.hip: the exact re-scoring of the survivors
+ * (eps_rescore_runs[_dev], eps_rescore_weighted).
  * Reports what eps_filter_scan reports -- key = (v << 32) | u, u < v, of every 2-hop non-edge of the given columns whose
  * score can exceed out->threshold (filter.py:96-142 + :160-161 under --keep_top) -- but a column is scored in PIECES (runs of
  * id windows of its endpoints) whose candidates each own a slot of an LDS table, so every path is read once and costs one
@@ -306,7 +310,7 @@ int eps_filter_scan(const int64_t *rowptr, const int32_t *col, const int32_t *re
  *                           piece had more ids to report than its set holds (results invalid: repeat the launch without
  *                           bit 16, on a plan without bit 24); value 16 (bit 4) = sketch pieces ran (informational). */
 int32_t eps_scan_windows(void);
-/* eps_rescore_runs: exact scores of screened survivors.  keys = (u << 32) | v, sorted ascending (runs of equal u: the hubs
+/* eps_rescore_runs (csrc/rescore.hip): exact scores of screened survivors.  keys = (u << 32) | v, sorted ascending (runs of equal u: the hubs
  * recur); fixw = eps_fixed_weights(node_w); out[i] = float32 of the exact int64 sum of the 2^-40 fixed-point weights over the
  * common neighbours of pair i -- bit-identical to eps_filter_scan's / eps_expand_fill's score.  Unit-valued adjacency.
  * eps_rescore_weighted: the same for an adjacency with stored values: term = (A[u,w] * A[v,w]) * node_w[w] in float32, each

@@ -74,6 +74,25 @@ def test_python_signatures_cover_header(eps):
             assert _ctypes_kind(a) == kd, f"{name}: argument {i} is {kd} in the header, {a.__name__} in SIGNATURES"
 
 
+def test_every_unit_of_the_library_is_warmed():
+    """eps_abi.h promises that eps_warm_up loads EVERY code object: each source the Makefile compiles, other than eps_common.hip
+    itself, defines eps_warm_<stem>, and the one list eps_warm_up declares and calls from (EPS_UNITS) names exactly those stems.
+    Text only: a unit added to SRCS and forgotten there pays its code-object load inside its first timed call."""
+    csrc = os.path.join(ROOT, "edge-proposal-sets_amd", "csrc")
+    srcs = re.search(r"^SRCS\s*:?=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    stems = [s[:-len(".hip")] for s in srcs if s != "eps_common.hip"]
+    assert len(stems) == len(srcs) - 1 and len(set(stems)) == len(stems)
+    for stem in stems:
+        text = open(os.path.join(csrc, stem + ".hip")).read()
+        assert re.search(r'^extern "C" void eps_warm_%s\(void \*stream\)\s*\{' % stem, text, flags=re.M), f"{stem}.hip defines no eps_warm_{stem}"
+        assert re.search(r"^__global__ void %s_warm_kernel\(\) \{\}" % stem, text, flags=re.M), f"{stem}.hip has no kernel to launch"
+    common = open(os.path.join(csrc, "eps_common.hip")).read()
+    units = re.search(r"^#define EPS_UNITS\(X\)((?:.*\\\n)*.*)$", common, flags=re.M).group(1)
+    listed = re.findall(r"\bX\((\w+)\)", units)
+    assert sorted(listed) == sorted(stems) and len(set(listed)) == len(listed)
+    assert "eps_warm_" not in re.sub(r"eps_warm_##unit|eps_warm_up|eps_warm_<unit>", "", common), "a warm call outside the list"
+
+
 def test_argument_validation_without_gpu(eps):
     """EINVAL paths return before any HIP call, so they are checkable on a CPU-only box."""
     lib = eps.load()

@@ -1,4 +1,4 @@
-"""GPU parity of the two launches behind eps_rescore_runs (csrc/scan_pieces.hip) against the kernels' own definition, computed
+"""GPU parity of the two launches behind eps_rescore_runs (csrc/rescore.hip) against the kernels' own definition, computed
 on the host: for a pair (u, v) the int64 sum of fixw[w] over w in N(u) & N(v), as float32(float64(sum) * 2^-40).  The sum is
 order-independent, so every comparison is bit for bit.
 

@@ -17,7 +17,7 @@ import eps_amd  # noqa: F401
 from eps_amd import ops, scan, synth
 from eps_amd.heuristics import node_weight_table
 
-RS_CHUNK, RS_SHORT = 256, 512                      # csrc/scan_pieces.hip
+RS_CHUNK, RS_SHORT = 256, 512                      # csrc/rescore.hip
 
 
 def main():
