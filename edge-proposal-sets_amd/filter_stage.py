@@ -14,6 +14,7 @@ output ``filtered_edges/{spec}_{edges}_{num}_{run}_sorted_edges.pt`` = float32 [
 from __future__ import annotations
 
 import argparse
+import math
 import time
 from pathlib import Path
 
@@ -23,7 +24,7 @@ from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
 from .heuristics import cosine_graph, node_weight_table, pair_scores_streamed, sigmoid_raw_cut
-from .models import build_model, default_model_configs
+from .models import DECODE_PRECISIONS, build_model, default_model_configs
 
 
 def make_parser():
@@ -47,7 +48,59 @@ def make_parser():
     parser.add_argument('--shard_proposals', action='store_true',
                         help='sharded runs (torchrun) under --keep_top: every rank writes the chunk of the sorted list it ordered '
                              '(<file>.shard{r}of{N}; rank.py reads the shards in rank order) instead of sending its rows to rank 0')
+    parser.add_argument('--decode_precision', type=str, default='fp32', choices=list(DECODE_PRECISIONS),
+                        help='GNN filters (gcn, sage, dea) under --keep_top K: bf16 screens every candidate block by its LOGIT on the '
+                             'bf16 matrix cores, keeps the ceil(G * ceil(K/2)) best unordered pairs, and decodes those once more in '
+                             'fp32, exactly as the fp32 run would.  Every score in the file is bit-identical to the fp32 decode of its '
+                             'pair and the rows follow the declared tie rule; only MEMBERSHIP can differ from the fp32 run: a pair '
+                             'whose bf16 rank falls beyond the kept ones is lost.  Single-process runs only.  Default fp32: the bare '
+                             'command is unchanged')
+    parser.add_argument('--decode_guard', type=float, default=None, metavar='G',
+                        help=f'with --decode_precision bf16: the screening pass keeps ceil(G * ceil(K/2)) pairs, G >= 1 '
+                             f'(default {DECODE_GUARD_DEFAULT:g}: see DESIGN 4.5d)')
     return parser
+
+
+DECODE_GUARD_DEFAULT = 4.0     # the rule: twice the smallest measured guard with recall 1.0 on both stand-ins; DESIGN 4.5d says what is measured
+BF16_FILTER_MODELS = ('gcn', 'sage', 'dea', 'dea_512')
+
+
+def screen_size(keep: int, guard: float) -> int:
+    """M = ceil(G * ceil(K/2)): the unordered pairs the bf16 screening pass keeps for the fp32 decode."""
+    k2 = (int(keep) + 1) // 2
+    return max(k2, int(math.ceil(float(guard) * k2)))
+
+
+def check_decode_args(args) -> None:
+    """--decode_precision / --decode_guard against the rest of the command line (model flags filled in by
+    ``default_model_configs``): a ValueError with the reason for every combination the bf16 screening pass does not serve --
+    raised before the dataset is read."""
+    precision = getattr(args, "decode_precision", "fp32") or "fp32"
+    guard = getattr(args, "decode_guard", None)
+    if precision not in DECODE_PRECISIONS:
+        raise ValueError(f"--decode_precision {precision}: one of {', '.join(DECODE_PRECISIONS)}")
+    if precision == "fp32":
+        if guard is not None:
+            raise ValueError("--decode_guard goes with --decode_precision bf16 (the fp32 decode screens nothing)")
+        return
+    if args.model not in BF16_FILTER_MODELS:
+        raise ValueError(f"--decode_precision bf16: --model {args.model} has no MLP decode (GNN filters only: gcn, sage, dea)")
+    if int(getattr(args, "keep_top", 0) or 0) <= 0:
+        raise ValueError("--decode_precision bf16 needs --keep_top K > 0: it screens for the K best rows; the whole file is fp32 work")
+    if int(args.keep_top) > scan.MAX_K:
+        raise ValueError(f"--decode_precision bf16: --keep_top {args.keep_top} is beyond the selection's {scan.MAX_K} rows")
+    if guard is not None and not guard >= 1.0:          # (NaN fails too)
+        raise ValueError(f"--decode_guard {guard}: the screening pass keeps G * ceil(K/2) pairs, G >= 1")
+    hc = args.hidden_channels
+    if hc is None or hc % 16 != 0 or hc > ops.BF16_MAX_HIDDEN:
+        raise ValueError(f"--decode_precision bf16: --model {args.model} with --hidden_channels {hc}: the bf16 decode kernel takes "
+                         f"a multiple of 16 up to {ops.BF16_MAX_HIDDEN} (wider or odd widths decode in fp32)")
+    if args.model in ('gcn', 'sage') and (args.num_layers is None or args.num_layers < 2):
+        raise ValueError(f"--decode_precision bf16: --num_layers {args.num_layers}: a one-layer decoder has no matrix work")
+    import os
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--decode_precision bf16 runs in one process: sharded runs would have to decode the kept pairs again "
+                         "on every rank before the gather (DESIGN 8)")
 
 
 def train_only_graph(split_edge, num_nodes: int, device) -> CSRGraph:
@@ -103,7 +156,18 @@ GNN_HALF = True            # GNN filters under --keep_top on symmetric graphs: d
 GNN_PRUNE_SLACK = 1 << 20  # gnn_half_topk re-cuts its kept pairs to the running bar when it holds more than 4 x ceil(K/2) + this
 
 
-def gnn_half_topk(args, model, data, keep: int, rank: int, world: int):
+def _decode(model, data, pairs, precision: str = "fp32"):
+    """The filter's scores of ``pairs`` as the model's forward gives them (sigmoid for LinkGNN, logits for DEA_GNN_JK), or, with
+    ``precision="bf16"``, the screening LOGITS of the bf16 kernel on the cached bf16 table."""
+    if precision != "bf16":
+        return model(data.x, pairs, data.adj_t).reshape(-1)
+    hb = model.embeddings_bf16(data.x, data.adj_t)
+    if hasattr(model, "linkpred"):
+        return model.linkpred.decode(hb, pairs, apply_sigmoid=False, precision="bf16")
+    return model.decode(hb, pairs, precision="bf16")
+
+
+def gnn_half_topk(args, model, data, keep: int, rank: int, world: int, precision: str = "fp32", guard: float = None):
     """The ``keep`` best proposals of a GNN filter, decoding each unordered candidate pair ONCE.
 
     The reference scores both orientations of a pair (filter.py:96-121), but LinkPredictor and DEA_GNN_JK decode h_u * h_v
@@ -113,13 +177,22 @@ def gnn_half_topk(args, model, data, keep: int, rank: int, world: int):
     (half the MFMA work -- the decode is all of this filter's time: 39.5 -> 20 s on the ppa stand-in), the pairs whose score
     reaches the running ceil(keep/2)-th best are kept, and the final selection mirrors them and orders the rows by the
     declared rule (score descending, then candidate order), exactly as the threshold scan's does (scan.select_topk).
-    -> (pairs int64 [2,<=keep], scores float32), candidates seen (both orientations counted)."""
+    -> (pairs int64 [2,<=keep], scores float32), candidates seen (both orientations counted).
+
+    ``precision="bf16"`` (--decode_precision; one process): the blocks are decoded by the bf16 kernel on LOGITS (a saturated
+    sigmoid of 1.0f would tie thousands of candidates), the running selection keeps the M = ceil(guard * ceil(keep/2)) best by
+    that logit, and the <= M (+ ties) kept pairs are decoded once more in fp32, exactly as the fp32 run calls it; selection,
+    mirroring and row order then run on those fp32 scores.  Every score written is therefore the fp32 decode of its pair bit
+    for bit and the order is the declared one; only membership can differ: a pair whose bf16 rank falls beyond M is lost."""
+    bf16 = precision == "bf16"
+    if bf16 and world > 1:
+        raise ValueError("--decode_precision bf16 runs in one process")
     g = data.adj_t
     dev = g.device
     revpos, md, sp = scan.reverse_positions(g), scan.max_degree(g), scan.window_splits(g)
     col_lo, col_hi = rank_column_range(g, rank, world)
     blocks = [(max(lo, col_lo), min(hi, col_hi)) for lo, hi in candidates.column_blocks(g) if lo < col_hi and hi > col_lo]
-    k2 = (keep + 1) // 2
+    k2 = screen_size(keep, DECODE_GUARD_DEFAULT if guard is None else guard) if bf16 else (keep + 1) // 2
     keys_l, vals_l, held, bar, n_seen = [], [], 0, None, 0
     if world > 1 and hasattr(model, "embeddings"):
         model.embeddings(data.x, data.adj_t)         # the row-sharded forward holds a collective: every rank reaches it
@@ -140,7 +213,7 @@ def gnn_half_topk(args, model, data, keep: int, rank: int, world: int):
         if pairs.shape[1] == 0:
             continue
         n_seen += 2 * pairs.shape[1]
-        sc = model(data.x, pairs, data.adj_t).reshape(-1)
+        sc = _decode(model, data, pairs, precision)
         if bar is not None:
             m = sc >= bar
             pairs, sc = pairs[:, m], sc[m]
@@ -154,6 +227,9 @@ def gnn_half_topk(args, model, data, keep: int, rank: int, world: int):
         keys, vals = keys_l[0], vals_l[0]
     else:
         keys, vals = torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev)
+    if bf16 and keys.numel():
+        # the kept pairs, decoded in fp32 (a pair's score does not depend on what else is in the call)
+        vals = _decode(model, data, torch.stack([keys & 0xFFFFFFFF, keys >> 32]).to(torch.int32))
     if world > 1:
         keys, vals = scan._gather_varlen(keys, world), scan._gather_varlen(vals, world)
         n_seen = _sum_over_ranks(n_seen)
@@ -287,6 +363,7 @@ class _Stopwatch:
 
 def run(args) -> str:
     args = default_model_configs(args)
+    check_decode_args(args)
     print(args)
     Path("filtered_edges").mkdir(exist_ok=True)
     if not torch.cuda.is_available():
@@ -406,12 +483,19 @@ def run(args) -> str:
             and data.adj_t.n_rows == data.adj_t.n_cols and data.adj_t.nnz() < 1 << 30 and scan.is_symmetric(data.adj_t)
             and (keep > 0 or int(scan.half_paths(data.adj_t).sum().item()) < 1 << 29)):     # (the whole file: lists that fit)
         with torch.no_grad():
-            best_pairs, best_scores, n_seen = gnn_half_topk(args, model, data, keep if keep else scan.MAX_K, rank, world)
+            best_pairs, best_scores, n_seen = gnn_half_topk(args, model, data, keep if keep else scan.MAX_K, rank, world,
+                                                            precision=getattr(args, "decode_precision", "fp32"),
+                                                            guard=getattr(args, "decode_guard", None))
         dt = watch.stop(n_seen)
-        print(f'GNN filter, each unordered pair decoded once ({args.model})')
+        print(f'GNN filter, each unordered pair decoded once ({args.model})'
+              + (f'; bf16 screening, {screen_size(keep, args.decode_guard or DECODE_GUARD_DEFAULT)} pairs decoded again in fp32'
+                 if getattr(args, "decode_precision", "fp32") == "bf16" else ''))
         print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
         return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world,
                      torch.cat([best_pairs.t().to(torch.float32), best_scores.unsqueeze(1)], 1))
+    if getattr(args, "decode_precision", "fp32") == "bf16":
+        raise ValueError("--decode_precision bf16: this graph does not take the half-list route of the GNN filters (it needs a "
+                         "symmetric adjacency on the device); run it in fp32")
     col_lo, col_hi = rank_column_range(data.adj_t, rank, world)
     n_seen = 0
     all_pairs, all_scores = [], []

@@ -249,6 +249,27 @@ REORDER_MIN_NODES = 100_000      # graphs from this size on run their GNN layers
 
 
 # ----------------------------------------------------------------------------------- decode
+DECODE_PRECISIONS = ("fp32", "bf16")
+
+
+def _check_precision(precision: str) -> None:
+    if precision not in DECODE_PRECISIONS:
+        raise ValueError(f"decode precision '{precision}': one of {', '.join(DECODE_PRECISIONS)}")
+
+
+def _bf16_decoder(module, layers):
+    """(weights, biases) of a decoder for eps_mlp_decode_bf16: ``layers()`` gives the float32 layers (any BatchNorm folded in
+    already, in float32); the hidden weights are rounded to bf16 AFTER that, the last layer and the biases stay float32.
+    Cached on ``module`` per version of its parameters and buffers."""
+    key = (tuple((p.data_ptr(), p._version) for p in module.parameters()),
+           tuple((b.data_ptr(), b._version) for b in module.buffers()))
+    if getattr(module, "_bf16_key", None) != key:
+        ws, bs = layers()
+        module._bf16_layers = ([ops.to_bf16(w) for w in ws[:-1]] + [ws[-1]], bs)
+        module._bf16_key = key
+    return module._bf16_layers
+
+
 class LinkPredictor(torch.nn.Module):
     """models.py:461-485: Hadamard -> (L-1) x [Linear, ReLU, dropout] -> Linear(hidden, out) -> sigmoid."""
 
@@ -266,13 +287,22 @@ class LinkPredictor(torch.nn.Module):
             lin.reset_parameters()
 
     @torch.no_grad()
-    def decode(self, h: torch.Tensor, edges: torch.Tensor, apply_sigmoid: bool = True) -> torch.Tensor:
-        """Fused gather + MLP + sigmoid over edges [2,B] (eps_mlp_decode) -> float32 [B].  Inference only."""
+    def decode(self, h: torch.Tensor, edges: torch.Tensor, apply_sigmoid: bool = True, precision: str = "fp32") -> torch.Tensor:
+        """Fused gather + MLP + sigmoid over edges [2,B] (eps_mlp_decode) -> float32 [B].  Inference only.
+        ``precision="bf16"``: the screening decode on the bf16 matrix cores (eps_mlp_decode_bf16); ``h`` is then the float32
+        table (converted here) or its bf16 bit patterns (int16, ``_CachedEmbeddings.embeddings_bf16``: converted once)."""
         heuristics.check_node_ids(edges, h.shape[0], "decode edges")   # the kernel gathers h[u], h[v] unchecked
         e = edges.to(device=h.device, dtype=torch.int32)
-        ws = [lin.weight.detach().contiguous() for lin in self.lins]
-        bs = [lin.bias.detach().contiguous() for lin in self.lins]
+        if precision == "bf16":
+            ws, bs = _bf16_decoder(self, self._decoder_layers)
+            hb = h.contiguous() if h.dtype == torch.int16 else ops.to_bf16(h.contiguous())
+            return ops.mlp_decode_bf16(hb, e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid)
+        _check_precision(precision)
+        ws, bs = self._decoder_layers()
         return ops.mlp_decode(h.contiguous(), e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid)
+
+    def _decoder_layers(self):
+        return ([lin.weight.detach().contiguous() for lin in self.lins], [lin.bias.detach().contiguous() for lin in self.lins])
 
     def forward(self, x_i: torch.Tensor, x_j: torch.Tensor) -> torch.Tensor:
         """Reference signature: two gathered [B,H] blocks -> [B,1].  (LinkGNN uses decode(), which gathers
@@ -314,6 +344,19 @@ class _CachedEmbeddings:
             self._h = h[inv].contiguous() if relabel else h
             self._h_key = key
         return self._h
+
+    _hb_key = None
+    _hb = None
+
+    @torch.no_grad()
+    def embeddings_bf16(self, x: Optional[torch.Tensor], adj: CSRGraph) -> torch.Tensor:
+        """The bf16 bit patterns (int16 [N, H]) of ``embeddings(x, adj)``, under the same cache key: built on the first bf16
+        decode after ``h`` changed, kept until it changes again."""
+        h = self.embeddings(x, adj)
+        if self._hb is None or self._hb_key != self._h_key:
+            self._hb = ops.to_bf16(h.contiguous())
+            self._hb_key = self._h_key
+        return self._hb
 
 
 class LinkGNN(_CachedEmbeddings, torch.nn.Module):
@@ -515,10 +558,21 @@ class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
         return h / n_out if self.jk_mode == 'mean' else h
 
     @torch.no_grad()
-    def decode(self, h: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
-        """Logits of the decoder over edges [2,B] (eps_mlp_decode with the BatchNorms folded in) -> float32 [B]."""
+    def decode(self, h: torch.Tensor, edges: torch.Tensor, precision: str = "fp32") -> torch.Tensor:
+        """Logits of the decoder over edges [2,B] (eps_mlp_decode with the BatchNorms folded in) -> float32 [B].
+        ``precision="bf16"``: eps_mlp_decode_bf16 on ``h`` (float32, or its bf16 bit patterns from ``embeddings_bf16``); the
+        BatchNorm is folded into ``lins.0`` in float32 first, the hidden weights are rounded to bf16 after."""
         heuristics.check_node_ids(edges, h.shape[0], "decode edges")   # the kernel gathers h[u], h[v] unchecked
         e = edges.to(device=h.device, dtype=torch.int32)
+        if precision == "bf16":
+            ws, bs = _bf16_decoder(self, self._decoder_layers)
+            hb = h.contiguous() if h.dtype == torch.int16 else ops.to_bf16(h.contiguous())
+            return ops.mlp_decode_bf16(hb, e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid=False)
+        _check_precision(precision)
+        ws, bs = self._decoder_layers()
+        return ops.mlp_decode(h.contiguous(), e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid=False)
+
+    def _decoder_layers(self):
         ws, bs = [], []
         for i, lin in enumerate(self.lins):
             w, b = lin.weight.detach(), lin.bias.detach()
@@ -526,7 +580,7 @@ class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
                 w, b = fold_batchnorm(w, b, self.mlp_bns[i])
             ws.append(w.contiguous())
             bs.append(b.contiguous())
-        return ops.mlp_decode(h.contiguous(), e[0].contiguous(), e[1].contiguous(), ws, bs, apply_sigmoid=False)
+        return ws, bs
 
     def forward(self, x_feature, edge_label_index, adj_t):
         if not self.training:

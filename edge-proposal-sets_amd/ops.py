@@ -1095,6 +1095,48 @@ def mlp_decode(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: S
     return out
 
 
+SIGNATURES = _lib.SIGNATURES      # name -> (restype, argtypes) of every export: the table tests/test_abi.py holds to the header
+BF16_MAX_HIDDEN = 256             # csrc/mlp_decode_bf16.hip: hdim % 16 == 0 && hdim <= 256, 2 <= layers
+
+
+def to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """The bfloat16 bit patterns of a float32 tensor (int16 storage, same shape), rounded to nearest even as torch's
+    ``.to(torch.bfloat16)`` rounds (eps_f32_to_bf16)."""
+    dev = _need_gpu(x)
+    _chk(_F32, x=x)
+    out = torch.empty(x.shape, dtype=_I16, device=dev)
+    _call("eps_f32_to_bf16", dev, x, x.numel(), out)
+    return out
+
+
+def mlp_decode_bf16(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+                    apply_sigmoid=True) -> torch.Tensor:
+    """``mlp_decode`` on the bf16 matrix cores (eps_mlp_decode_bf16): ``h`` [N, H] and the hidden ``weights`` [H, H] are bf16
+    bit patterns (int16, from ``to_bf16``); the last weight [1, H] and every bias are float32.  -> float32 [E]."""
+    dev = _need_gpu(h, u, v, *weights, *biases)
+    _chk(_I16, h=h); _chk(_I32, u=u, v=v)
+    L = len(weights)
+    if h.dim() != 2 or len(biases) != L:
+        raise _lib.EpsError("mlp_decode_bf16: h must be [N, H], with one bias per weight")
+    hd = h.shape[1]
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        _chk(_I16 if i < L - 1 else _F32, **{f"w{i}": w}); _chk(_F32, **{f"b{i}": b})
+        exp = (1 if i == L - 1 else hd, hd)
+        if tuple(w.shape) != exp:
+            raise _lib.EpsError(f"mlp_decode_bf16: layer {i} weight {tuple(w.shape)} != {exp} "
+                                f"(hidden width must equal the embedding width, last layer out=1)")
+        if b.numel() != exp[0]:
+            raise _lib.EpsError(f"mlp_decode_bf16: layer {i} bias holds {b.numel()} entries, not {exp[0]}")
+    n = u.numel()
+    if v.numel() != n:
+        raise _lib.EpsError("u and v differ in length")
+    out = torch.empty(n, dtype=_F32, device=dev)
+    wp = (ctypes.c_void_p * max(L, 1))(*[w.data_ptr() for w in weights])
+    bp = (ctypes.c_void_p * max(L, 1))(*[b.data_ptr() for b in biases])
+    _call("eps_mlp_decode_bf16", dev, h, h.shape[0], hd, u, v, n, wp, bp, L, int(apply_sigmoid), out)
+    return out
+
+
 def kth_largest(x: torch.Tensor, k: int) -> torch.Tensor:
     """The k-th largest value of a float32 device vector (1-element device tensor; no host round trip): radix select."""
     dev = _need_gpu(x)

@@ -507,6 +507,25 @@ int eps_mlp_decode(const float *h, int64_t n_nodes, int32_t hdim, const int32_t 
                    const float *const *b, int32_t n_layers, int apply_sigmoid, float *out,
                    void *stream);
 
+/* ---- K6b: the same decode on the bf16 matrix cores (screening precision) ---------------------
+ * eps_mlp_decode_bf16 replaces the same call site as eps_mlp_decode -- LinkPredictor.forward (models.py:478-485) as the
+ * filter stage calls it (filter.py:116-121) -- for callers that only have to FIND the best pairs: h is a bf16 table
+ * [n_nodes, hdim] (uint16 bit patterns, row-major, 16-byte aligned), w[l] for l < n_layers - 1 are bf16 [hdim, hdim]
+ * matrices, w[n_layers - 1] is the float32 [1, hdim] last layer, b[l] are float32 (hidden biases 16-byte aligned).
+ * v_mfma_f32_32x32x16_bf16, fp32 accumulate.  Fixed rounding points (RNE): x0 = bf16(float(h_u) * float(h_v)); every hidden
+ * layer adds its bias and applies ReLU in fp32, and all but the last are then rounded to bf16; the last hidden layer's
+ * output, the final dot, the bias and the sigmoid are fp32.  out: float32 [n_pairs].
+ * Supported: hdim % 16 == 0, hdim <= 256, 2 <= n_layers <= 8; anything else is EPS_EINVAL before any launch.
+ * eps_f32_to_bf16 replaces nothing of the reference (which has no reduced precision): out[i] = the bf16 bits of x[i], RNE,
+ * every NaN -> 0x7FC0 -- the bits of torch's float32 -> bfloat16; it prepares the table and the hidden weights of the call
+ * above (models.py:478-485 through filter.py:116-121 again).
+ * Both are additions, like eps_katz_* and eps_cos_* before them: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_mlp_decode_bf16(const uint16_t *h, int64_t n_nodes, int32_t hdim, const int32_t *u,
+                        const int32_t *v, int64_t n_pairs, const void *const *w,
+                        const float *const *b, int32_t n_layers, int apply_sigmoid, float *out,
+                        void *stream);
+int eps_f32_to_bf16(const float *x, int64_t n, uint16_t *out, void *stream);
+
 /* ---- top-K selection with the declared tie rule ------------------------------------------
  * Replaces `all_scores[:,2].sort(descending=True)` (filter.py:160-161) for the K rows rank.py
  * ever reads (rank.py:294).  Declared order: score descending, then `id` ascending (== a stable
