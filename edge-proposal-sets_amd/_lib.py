@@ -81,6 +81,11 @@ SIGNATURES = {
     "eps_mlp_decode": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _int, _vp, _vp]),
     "eps_mlp_decode_bf16": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _int, _vp, _vp]),
     "eps_f32_to_bf16": (_int, [_vp, _i64, _vp, _vp]),
+    "eps_mlp_decode_train": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _vp, _c.c_float, _int, _vp,
+                                    _vp, _vp]),
+    "eps_mlp_decode_backward_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "eps_mlp_decode_backward": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _i32, _vp,
+                                       _c.c_float, _int, _vp, _vp, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i64, _vp]),
     "eps_kth_largest_workspace_bytes": (_i64, []),
     "eps_kth_largest_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "eps_select_topk_rows_relabelled": (_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

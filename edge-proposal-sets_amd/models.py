@@ -252,6 +252,30 @@ REORDER_MIN_NODES = 100_000      # graphs from this size on run their GNN layers
 DECODE_PRECISIONS = ("fp32", "bf16")
 
 
+class _FusedDecode(torch.autograd.Function):
+    """The training decode on csrc/mlp_decode_train.hip: ``apply(h, edges, keep, keep_scale, *weights, *biases)`` -> scores [B].
+    ``edges``: int32 [2, B], ids checked by the caller; ``keep``: packed dropout masks (ops.pack_mask) or None.  The backward
+    recomputes the forward tile by tile (nothing but the inputs is saved) and is reproducible bit for bit."""
+
+    @staticmethod
+    def forward(ctx, h, edges, keep, keep_scale, *wb):
+        L = len(wb) // 2
+        h = h.contiguous()
+        ws, bs = [w.contiguous() for w in wb[:L]], [b.contiguous() for b in wb[L:]]
+        ctx.save_for_backward(h, edges, keep, *ws, *bs)
+        ctx.keep_scale = keep_scale
+        return ops.mlp_decode_train(h, edges[0], edges[1], ws, bs, keep=keep, keep_scale=keep_scale)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, edges, keep, *wb = ctx.saved_tensors
+        L = len(wb) // 2
+        need = ctx.needs_input_grad
+        gh, gw, gb = ops.mlp_decode_backward(h, edges[0], edges[1], wb[:L], wb[L:], grad_out.contiguous(), keep=keep,
+                                             keep_scale=ctx.keep_scale, want_h=need[0], want_params=any(need[4:]))
+        return (gh, None, None, None, *(gw or [None] * L), *(gb or [None] * L))
+
+
 def _check_precision(precision: str) -> None:
     if precision not in DECODE_PRECISIONS:
         raise ValueError(f"decode precision '{precision}': one of {', '.join(DECODE_PRECISIONS)}")
@@ -303,6 +327,25 @@ class LinkPredictor(torch.nn.Module):
 
     def _decoder_layers(self):
         return ([lin.weight.detach().contiguous() for lin in self.lins], [lin.bias.detach().contiguous() for lin in self.lins])
+
+    def decode_train(self, h: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+        """The training forward over edges [2,B] on the fused kernels (eps_mlp_decode_train / eps_mlp_decode_backward) ->
+        float32 [B], differentiable in ``h`` and in the layers.  Dropout: the keep masks are drawn here with torch's current
+        device generator (``torch.rand(B, H) >= p`` per hidden layer) and go to the kernel as bits."""
+        hd, L = h.shape[1], len(self.lins)
+        if h.dim() != 2 or hd % 4 != 0 or not ops.TRAIN_MIN_HIDDEN <= hd <= ops.TRAIN_MAX_HIDDEN or not 2 <= L <= 8 or any(
+                tuple(lin.weight.shape) != ((1 if i == L - 1 else hd), hd) for i, lin in enumerate(self.lins)):
+            raise ValueError(f"fused training decode: width {hd} with layers {[tuple(lin.weight.shape) for lin in self.lins]} is "
+                             f"outside the kernel's domain (one width H for the embedding and every hidden layer, H % 4 == 0, "
+                             f"{ops.TRAIN_MIN_HIDDEN} <= H <= {ops.TRAIN_MAX_HIDDEN}, 2 to 8 layers, one output); leave fused_decode off for this model")
+        heuristics.check_node_ids(edges, h.shape[0], "decode edges")   # the kernels gather h[u], h[v] unchecked
+        e = edges.to(device=h.device, dtype=torch.int32).contiguous()
+        keep, scale, p = None, 1.0, float(self.dropout)
+        if p > 0:
+            b = e.shape[1]
+            keep = torch.stack([ops.pack_mask(torch.rand(b, hd, device=h.device) >= p) for _ in range(L - 1)])
+            scale = 1.0 / (1.0 - p) if p < 1 else 0.0
+        return _FusedDecode.apply(h, e, keep, scale, *[lin.weight for lin in self.lins], *[lin.bias for lin in self.lins])
 
     def forward(self, x_i: torch.Tensor, x_j: torch.Tensor) -> torch.Tensor:
         """Reference signature: two gathered [B,H] blocks -> [B,1].  (LinkGNN uses decode(), which gathers
@@ -360,7 +403,9 @@ class _CachedEmbeddings:
 
 
 class LinkGNN(_CachedEmbeddings, torch.nn.Module):
-    """models.py:487-506."""
+    """models.py:487-506.  ``fused_decode`` (off by default): the training branch decodes through
+    ``LinkPredictor.decode_train`` (the fused HIP forward and backward) instead of the torch ops."""
+    fused_decode = False
 
     def __init__(self, emb, gnn, linkpred):
         super().__init__()
@@ -399,6 +444,8 @@ class LinkGNN(_CachedEmbeddings, torch.nn.Module):
             elif self.emb is not None:
                 x = torch.cat([self.emb.weight, x], dim=1)
             h = self.gnn(x, adj)
+            if self.fused_decode:
+                return self.linkpred.decode_train(h, edges).unsqueeze(1)
             return self.linkpred(h[edges[0]], h[edges[1]])
         h = self.embeddings(x, adj)
         return self.linkpred.decode(h, edges).unsqueeze(1)

@@ -1095,6 +1095,111 @@ def mlp_decode(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: S
     return out
 
 
+TRAIN_MIN_HIDDEN, TRAIN_MAX_HIDDEN = 32, 256     # csrc/mlp_decode_train.hip: hdim % 4 == 0, 32 <= hdim <= 256, 2 <= layers <= 8
+
+
+def mask_words(hdim: int) -> int:
+    return (int(hdim) + 31) // 32
+
+
+def pack_mask(mask: torch.Tensor) -> torch.Tensor:
+    """bool [..., H] -> int32 [..., ceil(H / 32)]: bit c & 31 of word c // 32 is mask[..., c] (the layout of the ``keep`` /
+    ``taken`` masks of eps_mlp_decode_train; the bits past H are zero).  Plain torch ops on the mask's device."""
+    hd = mask.shape[-1]
+    nw = mask_words(hd)
+    m = mask.to(torch.int64)
+    if nw * 32 != hd:
+        m = torch.nn.functional.pad(m, (0, nw * 32 - hd))
+    m = m.reshape(*mask.shape[:-1], nw, 32)
+    words = (m << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(-1)
+    return (words - ((words >> 31) << 32)).to(torch.int32)          # (uint32 bit patterns held as int32)
+
+
+def unpack_mask(words: torch.Tensor, hdim: int) -> torch.Tensor:
+    """The inverse of ``pack_mask``: int32 [..., ceil(H / 32)] -> bool [..., H]."""
+    bits = (words.to(torch.int64)[..., None] >> torch.arange(32, dtype=torch.int64, device=words.device)) & 1
+    return bits.reshape(*words.shape[:-1], -1)[..., :hdim].bool()
+
+
+def _decode_layers(who: str, hd: int, weights, biases):
+    L = len(weights)
+    if len(biases) != L:
+        raise _lib.EpsError(f"{who}: one bias per weight")
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        _chk(_F32, **{f"w{i}": w, f"b{i}": b})
+        exp = (1 if i == L - 1 else hd, hd)
+        if tuple(w.shape) != exp:
+            raise _lib.EpsError(f"{who}: layer {i} weight {tuple(w.shape)} != {exp} "
+                                f"(hidden width must equal the embedding width, last layer out=1)")
+        if b.numel() != exp[0]:
+            raise _lib.EpsError(f"{who}: layer {i} bias holds {b.numel()} entries, not {exp[0]}")
+    return L
+
+
+def _chk_keep(who: str, keep, L: int, n: int, hd: int) -> None:
+    _chk(_I32, keep=keep)
+    if keep is not None and tuple(keep.shape) != (L - 1, n, mask_words(hd)):
+        raise _lib.EpsError(f"{who}: keep must be int32 {(L - 1, n, mask_words(hd))} (pack_mask), got {tuple(keep.shape)}")
+
+
+def mlp_decode_train(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+                     keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, apply_sigmoid=True, want_taken=False):
+    """The training forward of the decode (eps_mlp_decode_train): ``mlp_decode`` with dropout given as bit masks.  ``keep``:
+    int32 [L - 1, E, ceil(H / 32)] (``pack_mask``; None = no dropout); a kept unit is multiplied by ``keep_scale`` after the ReLU.
+    -> scores float32 [E], or (scores, taken) with ``want_taken``: the same layout, set where a ReLU output was > 0."""
+    dev = _need_gpu(h, u, v, keep, *weights, *biases)
+    _chk(_F32, h=h); _chk(_I32, u=u, v=v)
+    if h.dim() != 2:
+        raise _lib.EpsError("mlp_decode_train: h must be [N, H]")
+    hd = h.shape[1]
+    L = _decode_layers("mlp_decode_train", hd, weights, biases)
+    n = u.numel()
+    if v.numel() != n:
+        raise _lib.EpsError("u and v differ in length")
+    _chk_keep("mlp_decode_train", keep, L, n, hd)
+    out = torch.empty(n, dtype=_F32, device=dev)
+    taken = torch.zeros((max(L - 1, 0), n, mask_words(hd)), dtype=_I32, device=dev) if want_taken else None
+    wp = (ctypes.c_void_p * max(L, 1))(*[w.data_ptr() for w in weights])
+    bp = (ctypes.c_void_p * max(L, 1))(*[b.data_ptr() for b in biases])
+    _call("eps_mlp_decode_train", dev, h, h.shape[0], hd, u, v, n, wp, bp, L, keep, float(keep_scale), int(apply_sigmoid), out, taken)
+    return (out, taken) if want_taken else out
+
+
+def mlp_decode_backward(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+                        grad_out: torch.Tensor, keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, apply_sigmoid=True,
+                        want_h=True, want_params=True):
+    """The gradients of ``mlp_decode_train`` (eps_mlp_decode_backward) given ``grad_out`` = dL/d(scores) float32 [E] ->
+    (grad_h [N, H] | None, [grad_w[l]] | None, [grad_b[l]] | None).  The same inputs give the same bits on every call: no
+    atomics; grad_h sums each node's incidences in the order of a stable sort of cat(u, v), done here."""
+    dev = _need_gpu(h, u, v, keep, grad_out, *weights, *biases)
+    _chk(_F32, h=h, grad_out=grad_out); _chk(_I32, u=u, v=v)
+    if h.dim() != 2:
+        raise _lib.EpsError("mlp_decode_backward: h must be [N, H]")
+    n_nodes, hd = h.shape
+    L = _decode_layers("mlp_decode_backward", hd, weights, biases)
+    n = u.numel()
+    if v.numel() != n or grad_out.numel() != n:
+        raise _lib.EpsError("mlp_decode_backward: u, v and grad_out differ in length")
+    _chk_keep("mlp_decode_backward", keep, L, n, hd)
+    wts = [w.t().contiguous() for w in weights[:-1]]
+    gw = [torch.empty_like(w) for w in weights] if want_params else None
+    gb = [torch.empty_like(b) for b in biases] if want_params else None
+    gh = torch.empty_like(h) if want_h else None
+    order = ptr = None
+    if want_h and n:
+        ids = torch.cat([u, v]).to(_I64)
+        order = torch.sort(ids, stable=True).indices.to(_I32)
+        ptr = torch.zeros(n_nodes + 1, dtype=_I64, device=dev)
+        torch.cumsum(torch.bincount(ids, minlength=n_nodes)[:n_nodes], 0, out=ptr[1:])
+    ws_bytes = int(_lib.load().eps_mlp_decode_backward_workspace_bytes(n, hd, L))
+    ws = torch.empty((ws_bytes + 7) // 8 + 2, dtype=_I64, device=dev)
+    arr = lambda ts, k: (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in ts])   # noqa: E731
+    _call("eps_mlp_decode_backward", dev, h, n_nodes, hd, u, v, n, arr(weights, L), arr(wts, L - 1), arr(biases, L), L, keep,
+          float(keep_scale), int(apply_sigmoid), grad_out, order, ptr, arr(gw, L) if want_params else None,
+          arr(gb, L) if want_params else None, gh, ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 16), ws_bytes)
+    return gh, gw, gb
+
+
 SIGNATURES = _lib.SIGNATURES      # name -> (restype, argtypes) of every export: the table tests/test_abi.py holds to the header
 BF16_MAX_HIDDEN = 256             # csrc/mlp_decode_bf16.hip: hdim % 16 == 0 && hdim <= 256, 2 <= layers
 

@@ -55,6 +55,7 @@ def make_parser():
     parser.add_argument('--synthetic', action="store_true", default=False)
     parser.add_argument('--load_model', type=str, default="")
     parser.add_argument('--train_cosine', action="store_true", default=False)   # train mlpcos's embedding (see run())
+    parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
     return parser
 
 
@@ -196,6 +197,11 @@ def _print_epoch(results, run_i: int, epoch: int, loss: float) -> None:
 def run(args):
     args = default_model_configs(args)
     print(args)
+    if getattr(args, 'fused_decode', False) and args.model not in ('gcn', 'sage'):
+        # (before any data is read)
+        raise ValueError(f"--fused_decode trains the LinkPredictor decoder of --model gcn / sage through the fused HIP kernels; "
+                         f"--model {args.model} has no such decoder (dea's decoder applies BatchNorm on batch statistics, which "
+                         f"needs a reduction across the kernel's edge tiles: not supported)")
     if args.model == 'mlpcos' and not args.load_model and not getattr(args, 'train_cosine', False):
         # (before any data is generated.  Training mlpcos is opt-in: the bare command keeps the refusal it always had)
         raise NotImplementedError("rank.py --model mlpcos trains its embedding through the cosine scores: pass --train_cosine "
@@ -219,6 +225,8 @@ def run(args):
         raise ValueError("Model not specified")
     data = data.to(device)
     model = build_model(args, data, device)
+    if getattr(args, 'fused_decode', False):
+        model.fused_decode = True
     print(f'using model {model}')
     evaluator, ks = evaluators[args.dataset], hits[args.dataset]
     print("Evaluating at hits: ", ks)

@@ -526,6 +526,38 @@ int eps_mlp_decode_bf16(const uint16_t *h, int64_t n_nodes, int32_t hdim, const 
                         void *stream);
 int eps_f32_to_bf16(const float *x, int64_t n, uint16_t *out, void *stream);
 
+/* ---- K6c: the same decode in TRAINING mode, forward and backward ---------------------------------
+ * Replaces, in training mode, the h[edges[0]] / h[edges[1]] gathers (models.py:506), LinkPredictor.forward with dropout
+ * (models.py:478-485: Hadamard -> (L-1) x [Linear, ReLU, dropout] -> Linear -> sigmoid) and what autograd records for them
+ * (train_and_eval.py:31-96).  Domain of both calls: hdim % 4 == 0, 32 <= hdim <= 256, 2 <= n_layers <= 8; anything else is
+ * EPS_EINVAL (the message names hdim= / n_layers=) before any launch; n_pairs == 0 succeeds without a launch.
+ * Masks: uint32 [n_layers - 1][n_pairs][ceil(hdim / 32)], bit c & 31 of word c / 32 of row e belongs to unit c of edge e.
+ *   keep  (in, or NULL = no dropout): a unit with its bit set is multiplied by keep_scale = 1 / (1 - p) AFTER the ReLU, any
+ *         other unit becomes 0.
+ *   taken (out, or NULL): set where the ReLU output is > 0, before dropout -- the branch the backward follows.
+ * eps_mlp_decode_train: out float32 [n_pairs]; with keep == NULL the scores are eps_mlp_decode's, bit for bit.
+ * eps_mlp_decode_backward: grad_out float32 [n_pairs] is dL/d(out); with apply_sigmoid the kernel multiplies by s (1 - s)
+ * itself.  wt[l] (l < n_layers - 1): W_l transposed, row-major [in, out], 16-byte aligned.  Outputs, each nullable (grad_w /
+ * grad_b are HOST arrays of n_layers device pointers, or NULL): grad_w[l] shaped like w[l], grad_b[l] like b[l], grad_h
+ * float32 [n_nodes, hdim] (every row is written).  grad_h needs the incidence list of the batch: inc_order int32
+ * [2 n_pairs] = the STABLE ascending argsort of the node ids cat(u, v), inc_ptr int64 [n_nodes + 1] = the first list
+ * position of every node (inc_ptr[n_nodes] = 2 n_pairs); the incidences of a node are summed in list order (a self pair
+ * u == v contributes twice: the derivative of h_u (.) h_u).  workspace: eps_mlp_decode_backward_workspace_bytes(...)
+ * bytes, 16-byte aligned, contents arbitrary.  No atomics; every summation order is a function of the shapes (and of the
+ * device's CU count) alone, so two calls on the same inputs return the same bits.
+ * Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_mlp_decode_train(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u,
+                         const int32_t *v, int64_t n_pairs, const float *const *w,
+                         const float *const *b, int32_t n_layers, const uint32_t *keep, float keep_scale,
+                         int apply_sigmoid, float *out, uint32_t *taken, void *stream);
+int64_t eps_mlp_decode_backward_workspace_bytes(int64_t n_pairs, int32_t hdim, int32_t n_layers);
+int eps_mlp_decode_backward(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u,
+                            const int32_t *v, int64_t n_pairs, const float *const *w, const float *const *wt,
+                            const float *const *b, int32_t n_layers, const uint32_t *keep, float keep_scale,
+                            int apply_sigmoid, const float *grad_out, const int32_t *inc_order, const int64_t *inc_ptr,
+                            float *const *grad_w, float *const *grad_b, float *grad_h, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
 /* ---- top-K selection with the declared tie rule ------------------------------------------
  * Replaces `all_scores[:,2].sort(descending=True)` (filter.py:160-161) for the K rows rank.py
  * ever reads (rank.py:294).  Declared order: score descending, then `id` ascending (== a stable
