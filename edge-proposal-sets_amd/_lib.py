@@ -127,6 +127,9 @@ SIGNATURES = {
     "eps_pair_cn_backward_workspace_bytes": (_i64, [_i64]),
     "eps_pair_cn_backward": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "eps_cos_features_backward": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "eps_csr_merge_workspace_bytes": (_i64, [_i64]),
+    "eps_csr_merge_count": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "eps_csr_merge_fill": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

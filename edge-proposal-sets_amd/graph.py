@@ -49,6 +49,15 @@ def _coalesce(row: torch.Tensor, col: torch.Tensor, val: Optional[torch.Tensor],
     return rowptr, ucol, uval
 
 
+def merge_keys(extra_edges: torch.Tensor) -> torch.Tensor:
+    """The batch ``CSRGraph.with_edges`` hands to the merge: both orientations of every extra edge [2, E] packed as
+    ``row << 32 | col`` (int64) and sorted ascending.  Repeats stay (the merge counts them); a self pair (u, u) appears twice,
+    as ``to_symmetric`` makes it.  Pure tensor ops on whichever device the edges live on."""
+    e = extra_edges.to(torch.int64)
+    u, v = e[0], e[1]
+    return torch.sort(torch.cat([(u << 32) | v, (v << 32) | u])).values
+
+
 class CSRGraph:
     """Coalesced CSR matrix [n_rows, n_cols]; float32 values or implicit ones."""
 
@@ -263,15 +272,35 @@ class CSRGraph:
                                           self.n_cols)
         return self._cache["tag"]
 
+    def with_edges(self, extra_edges: torch.Tensor, dataset_is_collab: bool) -> "CSRGraph":
+        """``add_edges`` for a graph that is resident already.  ``self`` must be the symmetrised graph of the base edge list
+        ALONE -- what ``add_edges(dataset, edge_index, edge_weight, <no edges>, N)`` returns; the result equals
+        ``add_edges(dataset, edge_index, edge_weight, extra_edges, N)`` array for array, by a merge per row
+        (ops.csr_merge) instead of two sorts of every stored entry.  Non-collab: the pattern, ``val is None``.  Collab:
+        S0 + E + E^T with repeats counted (the symmetrised sum is linear in the edge multiset), all ones -> None like
+        ``to_symmetric``.  A new graph with its own ``uid``: no cached table of ``self`` is carried over."""
+        assert self.n_rows == self.n_cols
+        from . import ops
+        xkeys = merge_keys(extra_edges.to(self.device))
+        rowptr, col, val = ops.csr_merge(self.rowptr, self.col, self.val if dataset_is_collab else None, self.n_rows, xkeys,
+                                         want_val=bool(dataset_is_collab))
+        if val is not None and bool((val == 1).all()):
+            val = None
+        return CSRGraph(rowptr, col, val, self.n_rows, self.n_cols)
+
     def __repr__(self) -> str:
         return (f"CSRGraph(n_rows={self.n_rows}, n_cols={self.n_cols}, nnz={self.nnz()}, "
                 f"values={'float32' if self.val is not None else 'implicit 1'}, device={self.device})")
 
 
 def add_edges(dataset: str, edge_index: torch.Tensor, edge_weight: torch.Tensor, extra_edges: torch.Tensor,
-              num_nodes: int) -> CSRGraph:
+              num_nodes: int, base: Optional[CSRGraph] = None) -> CSRGraph:
     """Drop-in for rank.py:28-36: concatenate the extra (proposal) edges with weight 1, build the
-    adjacency, symmetrise with duplicate SUM, and reset values to 1 unless the dataset is collab."""
+    adjacency, symmetrise with duplicate SUM, and reset values to 1 unless the dataset is collab.
+    ``base``: this function's result for the same dataset and edge list WITHOUT extra edges, resident on the GPU -- the
+    extra edges are then merged into it (``CSRGraph.with_edges``) and nothing the size of the graph is sorted."""
+    if base is not None:
+        return base.with_edges(extra_edges, dataset == "collab")
     full_edge_index = torch.cat([edge_index, extra_edges.to(edge_index.device)], dim=-1)
     new_edge_weight = torch.ones(extra_edges.shape[1], dtype=torch.float32, device=edge_index.device)
     full_edge_weights = torch.cat([edge_weight.to(torch.float32).to(edge_index.device), new_edge_weight], 0)

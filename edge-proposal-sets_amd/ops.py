@@ -503,6 +503,37 @@ def relabel_graph(rowptr, col, val, perm: torch.Tensor, inv32: torch.Tensor, new
     return out_c, out_v
 
 
+def csr_merge(rowptr, col, val, n: int, xkeys: torch.Tensor, want_val: bool):
+    """(new_rowptr, new_col, new_val | None) of a coalesced square CSR graph [n, n] plus the batch ``xkeys`` -- int64, SORTED
+    ascending, each ``row << 32 | col``, both orientations put in by the caller, duplicates allowed (eps_csr_merge_count /
+    _fill: a merge per row, nothing the size of the graph is sorted).  ``want_val``: values are ``val`` (None = ones) + how
+    often the batch names the pair; otherwise the pattern alone.  A key outside [0, n) or an unsorted batch raises EpsError
+    (checked on the device, read with the new entry count: one host read per call).  An empty batch returns the arrays it
+    was given."""
+    dev = _need_gpu(rowptr, col, val, xkeys)
+    _csr(rowptr, col, val); _chk(_I64, xkeys=xkeys)
+    n, m = int(n), int(xkeys.numel())
+    if rowptr.numel() != n + 1:
+        raise _lib.EpsError(f"csr_merge: rowptr holds {rowptr.numel()} entries for n={n}")
+    if m == 0:
+        return rowptr, col, (val if want_val else None)
+    new_deg = torch.empty(n, dtype=_I64, device=dev)
+    xrank = torch.empty(m + 1, dtype=_I32, device=dev)
+    status = torch.empty(1, dtype=_I32, device=dev)                  # (the call clears it)
+    _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_csr_merge_workspace_bytes(m))
+    _call("eps_csr_merge_count", dev, rowptr, col, n, xkeys, m, new_deg, xrank, status, wsp, wsb)
+    new_rowptr = torch.zeros(n + 1, dtype=_I64, device=dev)
+    torch.cumsum(new_deg, 0, out=new_rowptr[1:])
+    st, nnz = torch.stack([status[0].to(_I64), new_rowptr[-1]]).tolist()
+    if st:
+        raise _lib.EpsError("csr_merge: " + (f"an edge names a node outside [0, {n}); " if st & 1 else "")
+                            + ("xkeys is not sorted ascending" if st & 2 else ""))
+    new_col = torch.empty(nnz, dtype=_I32, device=dev)
+    new_val = torch.empty(nnz, dtype=_F32, device=dev) if want_val else None
+    _call("eps_csr_merge_fill", dev, rowptr, col, val if want_val else None, n, xkeys, m, xrank, new_rowptr, nnz, new_col, new_val)
+    return new_rowptr, new_col, new_val
+
+
 def score_bound(rowptr, col, val, node_w, n_rows: int, n_cols: int) -> torch.Tensor:
     """1-element float64 DEVICE tensor: max over the rows of sum |A[v,w]| |node_w[w]| max_u |A[u,w]| (eps_score_bound)."""
     dev = _need_gpu(rowptr, col, val, node_w)

@@ -56,6 +56,7 @@ def make_parser():
     parser.add_argument('--load_model', type=str, default="")
     parser.add_argument('--train_cosine', action="store_true", default=False)   # train mlpcos's embedding (see run())
     parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
+    parser.add_argument('--no_incremental_graph', action="store_true", default=False)   # rebuild the graph from the edge list at every point
     return parser
 
 
@@ -135,19 +136,19 @@ class _SweepPoint:
     runs, and -- per run -- the model-selection state: the MIDDLE K's validation score decides which checkpoint is kept
     (rank.py:356-361) and which evaluation becomes the run's curve point (rank.py:376-379)."""
 
-    def __init__(self, args, index_end: int, ks, proposals, data, split_edge, ei_dev, ew_dev, device):
+    def __init__(self, args, index_end: int, ks, proposals, data, split_edge, ei_dev, ew_dev, device, base=None):
         self.args, self.index_end = args, int(index_end)
         self.select_key = f"Hits@{ks[1]}"
         self.loggers = {f'Hits@{k}': Logger(args.runs, args) for k in ks}
         extra = proposals[:self.index_end, :2].t().long()
         assert extra.size(0) == 2 and extra.size(1) == self.index_end
         if not args.only_supervision:
-            data.adj_t = add_edges(args.dataset, ei_dev, ew_dev, extra.to(device), data.num_nodes)
+            data.adj_t = add_edges(args.dataset, ei_dev, ew_dev, extra.to(device), data.num_nodes, base=base)
         append_supervision(args, split_edge, extra)
         data.full_adj_t = data.adj_t
         if args.dataset in ("collab", "email", "reddit"):       # validation edges join the graph the TEST edges are scored on
             with_valid = torch.cat([extra, to_undirected(split_edge['valid']['edge'].t())], dim=-1)
-            data.full_adj_t = add_edges(args.dataset, ei_dev, ew_dev, with_valid.to(device), data.num_nodes)
+            data.full_adj_t = add_edges(args.dataset, ei_dev, ew_dev, with_valid.to(device), data.num_nodes, base=base)
         self.best_valid = 0
 
     def start_run(self) -> None:
@@ -244,6 +245,11 @@ def run(args):
         args.epochs = 1
     n_epochs = (args.epochs or 1) if trains or not has_params else 1
     ei_dev, ew_dev = edge_index.to(device), edge_weight.to(device)
+    # the graph of the training edges alone, built once: every sweep point merges its proposals into it (graph.add_edges with
+    # ``base``; the same arrays as a rebuild from the concatenated edge list, which --no_incremental_graph keeps for A/B)
+    base = None
+    if not args.no_incremental_graph and (not args.only_supervision or args.dataset in ("collab", "email", "reddit")):
+        base = add_edges(args.dataset, ei_dev, ew_dev, ei_dev.new_zeros((2, 0)), data.num_nodes)
     _lib.warm_up_join()
 
     curves = []
@@ -251,7 +257,7 @@ def run(args):
         print('---------------------')
         print(f'Using {index_end} highest scoring edges')
         print('---------------------')
-        point = _SweepPoint(args, index_end, ks, proposals, data, split_edge, ei_dev, ew_dev, device)
+        point = _SweepPoint(args, index_end, ks, proposals, data, split_edge, ei_dev, ew_dev, device, base=base)
         for run_i in range(args.runs):
             point.start_run()
             optimizer = None

@@ -759,6 +759,33 @@ int eps_cos_features_backward(const int64_t *rowptr, const int32_t *col, const f
                               const float *xhat, int64_t ldh, int32_t f, const float *nrm, const int32_t *revpos,
                               const float *gc, float *gxp, float *gxs, int64_t ldg, void *stream);
 
+/* ---- Adding a sorted batch of edges to a resident graph (csrc/csr_merge.hip) ---------------------------------------------
+ * Replaces the adjacency rebuild of rank.py:28-36 (cat the training edges and the proposals, from_edge_index, to_symmetric)
+ * for a graph that is resident already: the base (rowptr int64[n + 1], col int32 ascending per row, val float32 or NULL =
+ * all ones; coalesced, square, n < 2^31) plus a batch xkeys int64[m], SORTED ascending, each row << 32 | col -- duplicates
+ * allowed, both orientations of an undirected edge put in by the caller (a self pair twice, as to_symmetric makes it).  The
+ * result is the coalesced sum: a stored pair keeps its place and gains the number of times the batch names it, a new pair
+ * is inserted at its column's place with that number as its value.  Sorting the batch is the caller's job; nothing the size
+ * of the graph is sorted.
+ *   eps_csr_merge_count: new_deg[r] (int64[n]) = deg(r) + the distinct columns of row r's keys that the base row lacks (the
+ *       row's keys are found by lower-bound searches on xkeys: no per-row pointer array).  xrank (int32[m + 1], out) is what
+ *       eps_csr_merge_fill needs of the batch.  *status (DEVICE int32, cleared by the call): bit 1 = a key with row or col
+ *       outside [0, n), bit 2 = xkeys not ascending; with a bit set the outputs mean nothing and the fill must not follow.
+ *       workspace: eps_csr_merge_workspace_bytes(m) bytes, 256-byte aligned, contents arbitrary (m == 0: may be NULL).
+ *   eps_csr_merge_fill:  new_rowptr (int64[n + 1]) = the exclusive prefix of new_deg (the caller's prefix sum), new_nnz its
+ *       last entry; writes EVERY entry of new_col (int32[new_nnz]) and, when given, new_val (float32[new_nnz]): base value
+ *       (1 for val == NULL) + multiplicity, resp. the multiplicity.  val and new_val both NULL: the pattern only.
+ * EPS_EINVAL before any launch: n outside [0, 2^31) (the message names n=), m outside [0, 2^31 - 1) (m=), a null rowptr.
+ * m == 0 launches nothing that reads xkeys and returns the base's degrees / arrays.  No atomics on the data: the same inputs
+ * give the same bits.  Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int64_t eps_csr_merge_workspace_bytes(int64_t m);
+int eps_csr_merge_count(const int64_t *rowptr, const int32_t *col, int64_t n, const int64_t *xkeys, int64_t m,
+                        int64_t *new_deg, int32_t *xrank, int32_t *status, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+int eps_csr_merge_fill(const int64_t *rowptr, const int32_t *col, const float *val_or_null, int64_t n, const int64_t *xkeys,
+                       int64_t m, const int32_t *xrank, const int64_t *new_rowptr, int64_t new_nnz, int32_t *new_col,
+                       float *new_val_or_null, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
