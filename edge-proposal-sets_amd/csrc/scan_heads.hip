@@ -93,12 +93,19 @@ extern "C" int eps_scan_hub_rows(const int64_t *rowptr, const int32_t *col, int6
     return EPS_OK;
 }
 
-// One thread per slot of the walked list: key = (v << 32) | u, val = the WALKED screening sum as raw bits (eps_scan_screen with a
-// head table).  The pair's complete screening sum = walked + head(u, v); at or above the bar it goes to `out` (score = sum x
-// 2^-shift, like a launch without heads).  A wave collects what passes in its own LDS buffer and reserves room in `out` once
-// per few hundred pairs: one atomic per wave and trip on the list's ONE counter would cost 11 ns each, 2.8 ms for the 250 k
-// trips of the ppa-like graph's walked list.
+// The walked list: key = (v << 32) | u, val = the WALKED screening sum as raw bits (eps_scan_screen with a head table).  The
+// pair's complete screening sum = walked + head(u, v); at or above the bar it goes to `out` (score = sum x 2^-shift, like a
+// launch without heads).  A wave collects what passes in its own LDS buffer and reserves room in `out` once per few hundred
+// pairs: one atomic per wave and trip on the list's ONE counter would cost 11 ns each, 2.8 ms for the 250 k trips of the
+// ppa-like graph's walked list.
+// A slot's probe is a chain of dependent loads -- key -> heads[v], rowptr[v] -> four ids of the head -> their four bitmap words
+// -- and with one slot per lane the kernel waited a full chain per trip (341 us for 216 MB).  So a wave takes 128 consecutive
+// slots a trip, two per lane (i0 + lane, i0 + 64 + lane), and issues every level of the FIRST probing trip for both slots before
+// it consumes either; the keys of its next 128 slots are on their way meanwhile.  Most slots leave after that first trip; the
+// rest finish their heads one after the other, four rows a trip, as before.  One thread hands the walk's candidate counter on
+// (out->n_candidates = in->n_candidates): the completed list stands for the launch.
 #define SH_WBUF 384
+#define SH_SLOTS 2             // slots per lane and trip
 __global__ __launch_bounds__(256) void sp_refine_kernel(const eps_survivors *__restrict__ in, const uint2 *__restrict__ heads,
                                                         const uint32_t *__restrict__ hubrows, int32_t n_hub, int64_t words,
                                                         const uint32_t *__restrict__ fx32, const int64_t *__restrict__ rowptr,
@@ -115,14 +122,18 @@ __global__ __launch_bounds__(256) void sp_refine_kernel(const eps_survivors *__r
     int64_t *wkey = s_key[wib];
     float *wval = s_val[wib];
     const uint32_t thr32 = sp_bar_units(out->threshold, shift);
+    const uint32_t words32 = (uint32_t)words;                    // (n_nodes < 2^31: a row has fewer than 2^26 words; 32 x 32 -> 64 bit products)
+    const bool reach = thr32 < SP_FLAG;                          // (a bar of +inf: nothing passes, nothing is probed)
     const unsigned long long handed = in->count;
-    const int64_t n = handed < (unsigned long long)in->capacity ? (int64_t)handed : (int64_t)in->capacity;
+    // (a graph without nodes has no pairs: the loads below take column 0 for a hole)
+    const int64_t n = n_nodes <= 0 ? 0 : handed < (unsigned long long)in->capacity ? (int64_t)handed : (int64_t)in->capacity;
+    if (blockIdx.x == 0 && threadIdx.x == 0) out->n_candidates = in->n_candidates;
     const int64_t *__restrict__ in_key = in->key;
     const uint32_t *__restrict__ in_val = (const uint32_t *)in->val;
     int64_t *__restrict__ out_key = out->key;
     float *__restrict__ out_val = out->val;
     const uint32_t out_cap = out->capacity;
-    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t stride = (int64_t)gridDim.x * (256 * SH_SLOTS);
     int held = 0;                                                // pairs in the wave's buffer (uniform)
     auto flush = [&]() {
         unsigned long long base = 0ull;
@@ -138,55 +149,130 @@ __global__ __launch_bounds__(256) void sp_refine_kernel(const eps_survivors *__r
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the buffer is rewritten from the front)
         held = 0;
     };
-    for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < n; i0 += stride) {
-        const int64_t i = i0 + lane;
-        const int64_t key = i < n ? in_key[i] : -1;
-        unsigned long long total = 0ull;   // (64 bits: a sketch piece's estimate may reach 2^32 - 1, and the head term comes on top)
-        bool pass = false;
-        if (key >= 0) {
-            const int32_t v = (int32_t)(key >> 32), u = (int32_t)(key & 0xFFFFFFFFll);
-            const uint2 hd = heads[v];
-            // the head term: the skipped rows of column v are its first hd.x neighbours (hubs, ids < n_hub); row w counts iff u
-            // is a neighbour of hub w -- bit u of hub w's bitmap row, four rows in flight
-            // From the END of the head -- ids ascend, degrees fall, weights grow: its heaviest rows first -- and only as far as the
-            // pair can still reach the bar: `rem` is the weight of the rows not looked at yet (hd.y = their sum at the start), and a
-            // slot whose walked sum + found + rem falls below the bar is out.  Most slots pass the walk's lowered threshold by
-            // little and share none of the first few rows: they leave after one trip (resource allocation skips dozens of rows
-            // per column: every slot used to pay for each).
-            uint32_t c = 0u, rem = hd.y;
-            const uint32_t s_walk = in_val[i];
-            const int32_t *__restrict__ vcol = col + rowptr[v];
-            const uint32_t *__restrict__ ubit = hubrows + ((uint32_t)u >> 5);
-            bool out_of_reach = thr32 >= SP_FLAG;
-            for (int j1 = (int)hd.x; j1 > 0 && !out_of_reach; j1 -= 4) {
-                uint32_t wq[4], mq[4], fq[4];
+    // (every load of a trip's first three levels is unconditional or under one test per slot, with an index that is valid for
+    //  holes and for lanes past the end as well: nothing stands between the loads of the two slots)
+    auto slot_key = [&](int64_t i) -> int64_t {
+        const int64_t k = in_key[i < n ? i : n - 1];
+        return i < n ? k : -1;
+    };
+    int64_t i0 = (int64_t)blockIdx.x * (256 * SH_SLOTS) + (int64_t)wib * (64 * SH_SLOTS);
+    int64_t key[SH_SLOTS];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) wq[q] = j1 - 1 - q >= 0 ? (uint32_t)vcol[j1 - 1 - q] : 0u;
+    for (int s = 0; s < SH_SLOTS; ++s) key[s] = i0 < n ? slot_key(i0 + s * 64 + lane) : -1;
+    for (; i0 < n; i0 += stride) {
+        int64_t nkey[SH_SLOTS];
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) nkey[s] = i0 + stride < n ? slot_key(i0 + stride + s * 64 + lane) : -1;
+        // level 1: the column's head (x_v, T_v), the start of its row and the slot's walked sum
+        int32_t u[SH_SLOTS];
+        uint2 hd[SH_SLOTS];
+        int64_t rp[SH_SLOTS];
+        uint32_t s_walk[SH_SLOTS];
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) {
+            const int64_t i = i0 + s * 64 + lane;
+            const int32_t v = key[s] >= 0 ? (int32_t)(key[s] >> 32) : 0;
+            u[s] = key[s] >= 0 ? (int32_t)(key[s] & 0xFFFFFFFFll) : 0;
+            hd[s] = heads[v];
+            rp[s] = rowptr[v];
+            s_walk[s] = in_val[i < n ? i : n - 1];
+        }
+        // the head term: the skipped rows of column v are its first hd.x neighbours (hubs, ids < n_hub); row w counts iff u
+        // is a neighbour of hub w -- bit u of hub w's bitmap row, four rows in flight
+        // From the END of the head -- ids ascend, degrees fall, weights grow: its heaviest rows first -- and only as far as the
+        // pair can still reach the bar: `rem` is the weight of the rows not looked at yet (hd.y = their sum at the start), and a
+        // slot whose walked sum + found + rem falls below the bar is out.  Most slots pass the walk's lowered threshold by
+        // little and share none of the first few rows: they leave after one trip (resource allocation skips dozens of rows
+        // per column: every slot used to pay for each).
+        // level 2: the last four ids of the head (a shorter head repeats its first id: weight 0 below)
+        int j1[SH_SLOTS];
+        uint32_t wq[SH_SLOTS][4], mq[SH_SLOTS][4], fq[SH_SLOTS][4];
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) {
+            j1[s] = key[s] >= 0 && reach ? (int)hd[s].x : 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) wq[s][q] = 0u;
+            if (j1[s] > 0) {
+                const int32_t *__restrict__ vcol = col + rp[s];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wq[s][q] = (uint32_t)vcol[j1[s] - 1 - q > 0 ? j1[s] - 1 - q : 0];
+            }
+        }
+        // level 3: their bitmap words, all eight on their way before a weight is looked up (the choice between the weights in LDS
+        // and in the L2 is one uniform branch around both slots, not one per row: the compiler waits at every join)
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mq[s][q] = 0u;
+            if (j1[s] > 0) {
+                const uint32_t *__restrict__ ubit = hubrows + ((uint32_t)u[s] >> 5);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) mq[s][q] = ubit[(size_t)wq[s][q] * words32];
+            }
+        }
+        if (fx_lds) {
+#pragma unroll
+            for (int s = 0; s < SH_SLOTS; ++s)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) fq[s][q] = s_fx[wq[s][q]];       // (wq = 0 where there is no row: dropped below)
+        } else {
+#pragma unroll
+            for (int s = 0; s < SH_SLOTS; ++s)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) fq[s][q] = j1[s] > 0 ? fx32[wq[s][q]] : 0u;
+        }
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (j1[s] - 1 - q < 0) fq[s][q] = 0u;
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) {
+            uint32_t c = 0u, rem = hd[s].y;
+            bool out_of_reach = !reach;
+            if (j1[s] > 0) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    mq[q] = ubit[(size_t)wq[q] * words];
-                    fq[q] = j1 - 1 - q >= 0 ? (fx_lds ? s_fx[wq[q]] : fx32[wq[q]]) : 0u;
+                    rem -= fq[s][q];
+                    if ((mq[s][q] >> ((uint32_t)u[s] & 31u)) & 1u) c += fq[s][q];
                 }
+                out_of_reach = (unsigned long long)s_walk[s] + c + rem < (unsigned long long)thr32;
+                // the rare slot that is still in reach after its heaviest four rows: the rest of its head, four rows a trip
+                const int32_t *__restrict__ vcol = col + rp[s];
+                const uint32_t *__restrict__ ubit = hubrows + ((uint32_t)u[s] >> 5);
+                for (int j = j1[s] - 4; j > 0 && !out_of_reach; j -= 4) {
+                    uint32_t wr[4], mr[4], fr[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    rem -= fq[q];
-                    if ((mq[q] >> ((uint32_t)u & 31u)) & 1u) c += fq[q];
+                    for (int q = 0; q < 4; ++q) wr[q] = j - 1 - q >= 0 ? (uint32_t)vcol[j - 1 - q] : 0u;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        mr[q] = ubit[(size_t)wr[q] * words32];
+                        fr[q] = j - 1 - q >= 0 ? (fx_lds ? s_fx[wr[q]] : fx32[wr[q]]) : 0u;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        rem -= fr[q];
+                        if ((mr[q] >> ((uint32_t)u[s] & 31u)) & 1u) c += fr[q];
+                    }
+                    out_of_reach = (unsigned long long)s_walk[s] + c + rem < (unsigned long long)thr32;
                 }
-                out_of_reach = (unsigned long long)s_walk + c + rem < (unsigned long long)thr32;
             }
-            total = (unsigned long long)s_walk + c;
-            pass = !out_of_reach && total >= (unsigned long long)thr32;
-        }
-        const unsigned long long m = __ballot(pass);
-        if (m) {
-            if (pass) {
-                const int at = held + __popcll(m & ((1ull << lane) - 1ull));
-                wkey[at] = key;
-                wval[at] = (float)total * scale;
+            // (64 bits: a sketch piece's estimate may reach 2^32 - 1, and the head term comes on top)
+            const unsigned long long total = (unsigned long long)s_walk[s] + c;
+            const bool pass = key[s] >= 0 && !out_of_reach && total >= (unsigned long long)thr32;
+            const unsigned long long m = __ballot(pass);
+            if (m) {
+                if (pass) {
+                    const int at = held + __popcll(m & ((1ull << lane) - 1ull));
+                    wkey[at] = key[s];
+                    wval[at] = (float)total * scale;
+                }
+                held += __popcll(m);
+                if (held > SH_WBUF - 64) flush();
             }
-            held += __popcll(m);
-            if (held > SH_WBUF - 64) flush();
         }
+#pragma unroll
+        for (int s = 0; s < SH_SLOTS; ++s) key[s] = nkey[s];
     }
     if (held) flush();
 }

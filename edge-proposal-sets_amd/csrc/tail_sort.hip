@@ -275,7 +275,8 @@ extern "C" int eps_score_deal_plan(const uint32_t *hists, int64_t row_stride, in
 // ---- eps_score_pick_compact ----------------------------------------------------------------------------------------------
 // Every workgroup reads the histogram, finds the highest bucket b* with at least k values at or above it (the same arithmetic
 // on the same counters: no broadcast) and derives the threshold from that bucket's lower edge; then the entries at or above
-// the threshold are compacted.  The last workgroup to finish publishes the count and leaves the state zeroed.
+// the threshold are compacted -- tile by tile of TS_T x 8 entries, ONE reservation on the output counter per workgroup and tile
+// (the sixteen waves' counts meet in LDS).  The last workgroup to finish publishes the count and leaves the state zeroed.
 __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__restrict__ keys, const float *__restrict__ vals,
                                                                int64_t n_max, const unsigned long long *__restrict__ n_dev,
                                                                const float *__restrict__ base, const float *__restrict__ above,
@@ -284,10 +285,12 @@ __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__
                                                                float *__restrict__ thr_out, int64_t *__restrict__ out_keys,
                                                                float *__restrict__ out_vals, int64_t out_cap, int64_t *__restrict__ n_out)
 {
-    __shared__ uint32_t s_part[TS_T];
+    __shared__ uint32_t s_wsum[TS_W];                        // the prefix: sums of the waves' buckets
+    __shared__ uint32_t s_wtot[TS_W];                        // the compaction: entries a wave keeps of the tile at hand ...
+    __shared__ unsigned long long s_wbase[TS_W];             // ... and where they go
     __shared__ uint32_t s_bstar;
     __shared__ uint32_t s_last;
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
     int64_t n = n_max;
     if (n_dev) {
         const unsigned long long c = *n_dev;
@@ -303,18 +306,21 @@ __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__
         c[j] = b >= 0 ? __atomic_load_n(&st->hist[b], __ATOMIC_RELAXED) : 0u;
         mine += c[j];
     }
-    s_part[tid] = mine;
+    // inclusive scan of the per-thread sums (from the top bucket down): inside a wave by shuffles, then the sums of the waves
+    // before this one -- two workgroup barriers in all (a Hillis-Steele scan over the 1024 values in LDS took twenty)
+    uint32_t scan = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(scan, d);
+        if (lane >= d) scan += t;
+    }
+    if (lane == 63) s_wsum[wib] = scan;
     if (tid == 0) s_bstar = 0xFFFFFFFFu;
     __syncthreads();
-    // inclusive scan of the per-thread sums (from the top bucket down): Hillis-Steele over 1024 values in LDS
-    for (int d = 1; d < TS_T; d <<= 1) {
-        const uint32_t add = tid >= d ? s_part[tid - d] : 0u;
-        __syncthreads();
-        s_part[tid] += add;
-        __syncthreads();
-    }
+#pragma unroll
+    for (int w = 0; w < TS_W; ++w) scan += w < wib ? s_wsum[w] : 0u;
     {
-        const uint64_t incl = s_part[tid], before = incl - mine;
+        const uint64_t incl = scan, before = incl - mine;
         if (k != 0 && before < k && incl >= k) {            // the k-th best value lies in one of this thread's buckets
             uint64_t run = before;
 #pragma unroll
@@ -353,9 +359,13 @@ __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__
     }
     const float floor_v = above ? *above : -__builtin_inff();
     if (out_keys) {
-        const int64_t wave = ((int64_t)blockIdx.x * TS_T + tid) >> 6, n_waves = ((int64_t)gridDim.x * TS_T) >> 6;
+        // A workgroup takes tiles of TS_T x U entries, so its waves make the same trips and can meet at a barrier: their counts go
+        // to LDS, one thread draws ONE reservation on st->n_out for the sixteen of them and hands every wave its base.  (One
+        // atomic per wave and trip -- 4000 a call on the one word, served one by one at ~11 ns -- was half of this kernel.)
         constexpr int U = 8;
-        for (int64_t c0 = wave * 64 * U; c0 < n; c0 += n_waves * 64 * U) {
+        const int64_t tile = (int64_t)TS_T * U;
+        for (int64_t t0 = (int64_t)blockIdx.x * tile; t0 < n; t0 += (int64_t)gridDim.x * tile) {
+            const int64_t c0 = t0 + (int64_t)wib * (64 * U);
             int64_t kq[U];
             float sq[U];
             unsigned int bits = 0;
@@ -378,12 +388,24 @@ __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__
                 const int t = __shfl_up(incl, d);
                 if (lane >= d) incl += t;
             }
-            const int total = __shfl(incl, 63);
-            if (total == 0) continue;
-            unsigned long long basep = 0;
-            if (lane == 0) basep = atomicAdd(&st->n_out, (unsigned long long)total);
-            const unsigned int blo = __shfl((unsigned int)basep, 0), bhi = __shfl((unsigned int)(basep >> 32), 0);
-            unsigned long long pos = (((unsigned long long)bhi << 32) | blo) + (unsigned long long)(incl - cnt);
+            if (lane == 63) s_wtot[wib] = (uint32_t)incl;
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t tot[TS_W], sum = 0u;
+#pragma unroll
+                for (int w = 0; w < TS_W; ++w) {
+                    tot[w] = s_wtot[w];
+                    sum += tot[w];
+                }
+                unsigned long long at = sum ? atomicAdd(&st->n_out, (unsigned long long)sum) : 0ull;
+#pragma unroll
+                for (int w = 0; w < TS_W; ++w) {
+                    s_wbase[w] = at;
+                    at += tot[w];
+                }
+            }
+            __syncthreads();       // (the next tile's counts are written after this barrier, its bases after the next one)
+            unsigned long long pos = s_wbase[wib] + (unsigned long long)(incl - cnt);
 #pragma unroll
             for (int j = 0; j < U; ++j)
                 if (bits & (1u << j)) {

@@ -352,7 +352,14 @@ __global__ __launch_bounds__(256) void sel_count_runs_kernel(const int64_t *__re
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(runs, (unsigned long long)c);
+    // one atomic per workgroup, and none for a count of zero: every adder hits the same word, and the word serves them one by one
+    __shared__ unsigned int s_c[4];
+    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int t = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+        if (t) atomicAdd(runs, (unsigned long long)t);
+    }
 }
 
 // out[i] = (u << 32) | v of the order that is kept: the blocked one while its runs stay long (runs given), else the (u, v) one

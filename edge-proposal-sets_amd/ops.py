@@ -779,7 +779,8 @@ def scan_hub_rows(rowptr, col, n_hub: int) -> torch.Tensor:
 
 def scan_refine(walked: "Survivors", heads, hubrows, fx32, rowptr, col, n_nodes: int, shift: int, out: "Survivors") -> None:
     """Complete the walked sums of a launch with skipped heads (eps_scan_refine): every valid slot of ``walked`` gets its pair's
-    exact head term added; sums at or above ``out``'s bar are appended to ``out`` (compact, scores in 2^-shift units x 2^-shift)."""
+    exact head term added; sums at or above ``out``'s bar are appended to ``out`` (compact, scores in 2^-shift units x 2^-shift), and ``out`` takes over
+    the walk's candidate counter (``rec[4]``)."""
     dev = _need_gpu(heads, hubrows, fx32, rowptr, col)
     _chk_heads(heads, n_nodes); _chk(_I32, hubrows=hubrows, fx32=fx32); _csr(rowptr, col)
     if hubrows.dim() != 2 or hubrows.shape[1] != scan_hub_row_words(n_nodes) or fx32.numel() != n_nodes:

@@ -638,8 +638,8 @@ def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, bo
                             batch_from(g, columns), screen.rowrec,
                             column_records(g, screen, columns, heads.plan, heads.heads, heads.live, ("colrec", columns.data_ptr(), columns.numel())),
                             column_pack(g, screen, heads) if variant_is_main(g, screen) else None)
+            # (the refine kernel hands the walk's candidate counter on to `out` itself: no copy launch)
             ops.scan_refine(walked, heads.heads, hub_rows(g), screen.fx32, g.rowptr, g.col, g.n_rows, screen.shift, out)
-            out.rec[4:5].copy_(walked.rec[4:5])              # (candidates the walk touched)
             out.walked_slots = walked.rec[1:2]
         elif screen is not None:
             bounds, cuts = screen_tables(g)

@@ -370,7 +370,8 @@ int eps_scan_row_records(const uint16_t *cuts, const int64_t *rowptr, const uint
  *                        of fx32[w] over the skipped rows w = col[rowptr[v] + j], j < x_v, that hold u (bit u of hub row w) -- added;
  *                        sums at or above out->threshold (in table units, as eps_scan_screen rounds it) are appended to `out`
  *                        (compact: out->count = their number; val = sum x 2^-shift) -- the list a launch without heads reports,
- *                        in another order.  out->count must be zeroed by the caller. */
+ *                        in another order.  out->count must be zeroed by the caller; out->n_candidates = walked->n_candidates
+ *                        (the completed list stands for the launch that walked). */
 int eps_scan_heads(const int64_t *rowptr, const int32_t *col, const uint32_t *fx32, int64_t n_nodes, int32_t n_hub,
                    uint32_t budget, int32_t max_rows, uint32_t *heads, void *stream);
 int64_t eps_scan_hub_row_words(int64_t n_nodes);
