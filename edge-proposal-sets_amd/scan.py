@@ -1,25 +1,25 @@
 """Exact top-K of the filter stage's candidate set without the candidate list (``filter.py --keep_top K``).
 
-The reference generates every 2-hop non-edge (filter.py:96-109), scores all of them (:113-142), sorts all E rows
-(:160-161) -- and rank.py:294 reads the first ``num_sorted_edge``.  Here the whole candidate set is still scored, but
-by ``eps_filter_scan`` (csrc/filter_scan.hip), which reports only the candidates above a bar:
+The reference generates every 2-hop non-edge (filter.py:96-109), scores all of them (:113-142), sorts all E rows (:160-161) -- and
+rank.py:294 reads the first ``num_sorted_edge``.  Here every candidate is still scored, but only those above a bar are reported:
 
-1. the bar is ESTIMATED from a column sample: every ``SAMPLE_STRIDE``-th column of the heaviest-first order is scanned
-   with no bar at all, and the score that ``SAFETY x K`` candidates of the whole graph are expected to exceed is read
-   off the sample (on the device: no host round trip);
-2. ONE launch scans all columns against that bar;
-3. the result is VERIFIED: if at least K candidates survived, the K best of them under the declared rule (score
-   descending, then candidate order ascending) ARE the K best of the whole set -- exact, whatever the estimate was.
-   Too few survivors (bar too high) or more than the list holds (bar too low) -> the bar is corrected from what was
-   found and step 2 repeats.
+1. the bar is ESTIMATED (``estimate_bar``): every ``SAMPLE_STRIDE``-th column of the heaviest-first order is scanned with no
+   bar, and the score that ``SAFETY x K`` candidates of the whole graph are expected to exceed is read off on the device;
+2. ONE launch scans all columns against it (``_launch``): the one-pass piece kernel (csrc/scan_pieces.hip: screening sums in
+   coarse fixed point from tables cached per graph and weight table, ``Screen``), under a bar without the columns' heaviest
+   hub rows (``HeadTables``; csrc/scan_heads.hip completes the walked list) -- or eps_filter_scan (exact sums, two passes);
+3. the tail: a pre-filter keeps the survivors that can reach the K/2 best pairs, they are re-scored exactly, and the cut is
+   the K/2-th best exact score (``_device_tail`` on one rank; ``_prefilter`` + ``_cut_*`` on a job);
+4. the step is VERIFIED from one status row per rank (``StepStatus``; ``_pack_status`` on the device, read back once): enough
+   pairs at or above the cut, no list overflowed, the cut reaches every pre-filter threshold, usable heads -- then the K best
+   rows under the declared rule (score descending, then candidate order ascending) ARE the K best of the whole set, whatever
+   the estimate was.  Else ``_Retry`` names what the next launch changes and the launch repeats (``scan_topk``).
 
-Symmetry: the kernel scores each unordered pair {u, v} once (u < v) and the list is mirrored here; candidate order is
-the reference's column-major order, i.e. ascending key (v << 32 | u).
+Each unordered pair {u, v} is scored once (u < v) and mirrored at the end; candidate order is the reference's: key (v << 32 | u).
 
-Multi-GPU (one process per GPU): rank r scans the columns ``order[r::world]`` of the same heaviest-first order
-(balanced to within one column of every weight class); the graph is replicated; the sample and therefore the bar are
-computed redundantly and identically on every rank; the survivor lists are all-gathered (a few MB) and the selection
-runs on every rank -- no collective on the data path.
+Multi-GPU (one process per GPU): rank r scans the columns ``order[r::world]`` of the same heaviest-first order; the graph is
+replicated; every rank re-scores its own survivors, ONE exchange carries status rows and score histograms, every rank derives
+the same cut and deal plan from it, and the final ordering is dealt over the ranks by score range (``_deal_rows``).
 """
 from __future__ import annotations
 
@@ -179,13 +179,8 @@ def max_degree(g: CSRGraph) -> int:
     return g._cache["max_degree"]
 
 
-def weight_cache(g: CSRGraph, name: str, node_w: Optional[torch.Tensor], build):
-    """Per-graph cache of a table derived from a weight tensor (see ``CSRGraph.weight_cached``)."""
-    return g.weight_cached(name, node_w, build)
-
-
 def fixed_weights(g: CSRGraph, node_w: torch.Tensor) -> torch.Tensor:
-    return weight_cache(g, "fixw", node_w, lambda: ops.fixed_weights(node_w))
+    return g.weight_cached("fixw", node_w, lambda: ops.fixed_weights(node_w))
 
 
 def scan_graph(g: CSRGraph, build: bool = False):
@@ -215,7 +210,7 @@ def _scan_weights(g: CSRGraph, gs: CSRGraph, perm, node_w: torch.Tensor) -> torc
     """Fixed-point weight table in the labels of the scanned graph (cached on the original graph per weight tensor)."""
     if perm is None:
         return fixed_weights(g, node_w)
-    return weight_cache(g, "fixw_relabelled", node_w, lambda: ops.fixed_weights(node_w[perm].contiguous()))
+    return g.weight_cached("fixw_relabelled", node_w, lambda: ops.fixed_weights(node_w[perm].contiguous()))
 
 
 def _original_keys(keys: torch.Tensor, perm) -> torch.Tensor:
@@ -919,7 +914,11 @@ def _ordered_rows_distributed(keys: torch.Tensor, vals: torch.Tensor, k: int, bi
     return rows_k[:k], rows_v[:k]
 
 
-_XCHG_HEAD = 16                    # int32 words in front of a rank's scores in the step's one exchange (six int64 status words, padded)
+_XCHG_HEAD = 16                    # int32 words in front of a rank's scores in the step's one exchange (the status row, padded)
+# a rank's status row on the wire, whatever path it takes: int32 words [slots lo hi, candidates lo hi, n_sel lo hi, cut, kernel
+# status, pre_thr, walked lo hi, bar] -- the fields of StepStatus in their order (_pack_status / _unpack_status)
+_STATUS_WIDTHS = (2, 2, 2, 1, 1, 1, 2, 1)
+_STATUS_WORDS = sum(_STATUS_WIDTHS)
 _NEG_INF_BITS = -8388608           # float32 -inf as int32
 
 
@@ -992,85 +991,146 @@ def _capacity(slots_wanted: int, slack: Optional[int] = None) -> int:
     return cap
 
 
-# _verdict's result: the next action, the launches counted, whether the next launch under a bar takes a head table built for its
-# bar (drop_heads: screen.head_cur = None), and the call's walked-list overflows and head tables built for another bar
+# kernel status bits (include/eps_abi.h, eps_scan_screen's *status) that the step looks at; any other bit is a full hash table
+_KS_HEADS_HIGHER_BAR = 4           # some head is as heavy as the bar: the head table was built for a higher bar
+_KS_SKETCH_SET_FULL = 8            # a sketch piece had more ids to report than its set holds
+_KS_SKETCH_RAN = 16                # sketch pieces ran (informational)
+
+
+class StepStatus(namedtuple("StepStatus", "slots candidates n_sel cut_bits kernel pre_thr_bits walked bar_bits")):
+    """One rank's row of a step's status table: list slots handed out, candidates counted, pairs selected, the job-wide cut, the
+    kernel's status word, the pre-filter threshold, walked-list slots, the bar.  The floats are kept as their int32 bits (zero
+    where a launch has none) and read through the views below."""
+    __slots__ = ()
+    cut = property(lambda self: _f32_from_bits(self.cut_bits))
+    pre_thr = property(lambda self: _f32_from_bits(self.pre_thr_bits))
+    bar = property(lambda self: _f32_from_bits(self.bar_bits))
+    cut_is_neg_inf = property(lambda self: self.cut_bits & 0xFFFFFFFF == 0xFF800000)
+
+
+_ZERO = {}                         # device -> int32[2] of zeros (never written): the absent parts of a status row
+
+
+def _pack_status(slots, candidates, n_sel=None, cut=None, status=None, pre_thr=None, walked=None, bar=None, extra=()) -> torch.Tensor:
+    """A status row as int32[_STATUS_WORDS] on the device: views of the 1-element tensors at hand (int64 counts, float32 / int32
+    words), ONE cat launch, no dtype conversions; None -- no status, threshold, walked list or bar, n_sel / cut not known yet --
+    is zero.  ``extra``: 1-element tensors whose words follow the row."""
+    if slots.device not in _ZERO:
+        _ZERO[slots.device] = torch.zeros(2, dtype=torch.int32, device=slots.device)
+    parts = zip((slots, candidates, n_sel, cut, status, pre_thr, walked, bar), _STATUS_WIDTHS)
+    return torch.cat([_ZERO[slots.device][:w] if p is None else p.view(torch.int32) for p, w in parts] + [p.view(torch.int32) for p in extra])
+
+
+def _unpack_status(words, extra: int = 0):
+    """The StepStatus of a packed row read back (a list of int32 values) -- the one place where lo / hi halves are joined: a low
+    half is taken unsigned, one-word fields stay as read.  ``extra`` 64-bit words behind the row: -> (StepStatus, their values)."""
+    it = iter(words)
+    vals = [next(it) if w == 1 else (next(it) & 0xFFFFFFFF) | (next(it) << 32) for w in _STATUS_WIDTHS + (2,) * extra]      # (lo, then hi)
+    return (StepStatus(*vals[:8]), vals[8:]) if extra else StepStatus(*vals)
+
+
+# _Retry.verdict's result: the next action, the launches counted, whether the next launch under a bar takes a head table built for
+# its bar (drop_heads: screen.head_cur = None), and the call's walked-list overflows and head tables built for another bar
 Verdict = namedtuple("Verdict", "action launches drop_heads head_trouble head_stale")
 
 
-def _verdict(table, capacity: int, walked_cap: int, head_budget: Optional[int], shift: Optional[int], screened: bool,
-             rescore_all: bool, k2: int, bar_set: bool, launches: int, head_trouble: int = 0, head_stale: int = 0) -> Verdict:
-    """Whether a launch's selection IS the job's k2 best pairs ("done") or what the next launch changes, from the status ``table``
-    (per rank: slots, candidates, n_sel, cut bits, kernel status, pre-filter threshold bits, walked slots, bar bits); ``head_budget``
-    (table units), ``shift``: None without heads.  The first check that fails names the action: status bit 3 "sketch off" (other
-    unknown bits raise); a void head table "grow walked list" / "rebuild heads" / "heads off"; an unsound pre-filter "rescore all"
-    (these repeat the SAME launch); an overflowing list "rescan below cut" / "rescan wider" (-inf cut); too few "lower bar" / "drop bar"."""
-    def again(action: str, failing: str, drop_heads: bool = False) -> Verdict:
-        n = launches - 1                                  # (the same launch again, not a corrected bar: it does not count twice)
-        if n + 2 > MAX_LAUNCHES:
-            raise ops._lib.EpsError(f"scan_topk: {failing} kept failing")
-        return Verdict(action, n, drop_heads, head_trouble, head_stale)
+class _Retry:
+    """What one scan_topk call carries from launch to launch: ``verdict`` reads a launch's status table, ``apply`` makes the
+    verdict's changes -- neither touches the device."""
 
-    if any(t[4] & 8 for t in table):
-        # (status bit 3: a sketch piece had more ids to report than its set holds -- a bar far below what K asks for: the launch is
-        #  void, the call goes on with hashed packed pieces)
-        return again("sketch off", "launches with sketch pieces")
-    if any(t[4] & ~(4 | 16) for t in table):
-        raise ops._lib.EpsError("scan_topk: eps_scan_screen reported a full hash table (status %s)" % [t[4] for t in table])
-    drop_heads = False
-    if head_budget is not None:
-        # The head table was taken without looking at the bar.  A head as heavy as the bar (status bit 2: the bar fell since the
-        # table was built), a bar below the lowest one the table -- and its list of live columns -- was built for, or a walked
-        # list that overflowed: the launch is void; twice in a row: this call goes on without heads.
-        bar_units = _f32_from_bits(table[0][7]) * 2.0 ** shift
-        overflow = any(t[6] > walked_cap for t in table)
-        stale = any(t[4] & 4 for t in table) or head_budget > HEAD_KEEP[1] * bar_units
-        # (a budget out of range on a good launch only costs time: the NEXT launch takes a table for its bar)
-        drop_heads = overflow or stale or not HEAD_KEEP[0] * bar_units <= head_budget <= HEAD_KEEP[1] * bar_units
-        if overflow or stale:
-            # two causes, two remedies (ADVICE r05): a table built for another bar is simply rebuilt; only an overflowing walked
-            # list grows the list and counts toward giving heads up for this call
-            head_trouble, head_stale = head_trouble + overflow, head_stale + (not overflow)
-            action = "heads off" if head_trouble >= 2 or head_stale >= 3 else "grow walked list" if overflow else "rebuild heads"
-            return again(action, "launches with skipped heads", drop_heads)
-    slot_overflow = any(t[0] > capacity for t in table)
-    cut_is_inf = (table[0][3] & 0xFFFFFFFF) == 0xFF800000
-    if screened and not rescore_all and not slot_overflow:
-        # the pre-filter was sound iff the cut reaches every rank's threshold (floats compared through their bits on the host).
-        # A cut of -inf -- fewer than k2 re-scored pairs job-wide -- is NOT exempt (ADVICE r04): with uneven shards one rank's
-        # pre-filter may have held back pairs that belong to the k2 best while another rank had too few to fill its share, so
-        # any finite threshold above a -inf cut sends the step round again with everything re-scored.  Only when no rank
-        # filtered at all (every threshold -inf) does -inf mean "fewer than k2 pairs survived": the bar is lowered below.
-        cut_f = float("-inf") if cut_is_inf else _f32_from_bits(table[0][3])
-        if any(cut_f < _f32_from_bits(t[5]) for t in table):
+    def __init__(self, launches: int, wanted: int, head_list: int, use_heads: bool, sketch: bool, head_trouble: int = 0,
+                 head_stale: int = 0, sketch_void: int = 0, rescore_all: bool = False):
+        # launches counted so far (bar samples included; a void launch does not count twice); slots the next launch's list is sized for
+        self.launches, self.wanted = launches, wanted
+        # the walked list holds head_list times the survivor list; whether launches under a bar skip heads / run sketch pieces
+        self.head_list, self.use_heads, self.sketch = head_list, use_heads, sketch
+        # this call's walked-list overflows, head tables built for another bar, launches voided by a full sketch set
+        self.head_trouble, self.head_stale, self.sketch_void = head_trouble, head_stale, sketch_void
+        # every survivor is re-scored (a pre-filter threshold lay above the job-wide cut); what "estimate" aims the new bar at (x K)
+        self.rescore_all, self.safety = rescore_all, None
+
+    def verdict(self, table, *, capacity: int, walked_cap: int, head_budget: Optional[int], shift: Optional[int], screened: bool,
+                k2: int, bar_set: bool) -> Verdict:
+        """Whether a launch's selection IS the job's k2 best pairs ("done") or what the next launch changes, from the status ``table``
+        (a StepStatus per rank); ``head_budget`` (table units), ``shift``: None without heads.  The first check that fails names the
+        action: a full sketch set "sketch off" (unknown status bits raise); a void head table "grow walked list" / "rebuild heads" /
+        "heads off"; an unsound pre-filter "rescore all" (these repeat the SAME launch); an overflowing list "rescan below cut" /
+        "rescan wider" (-inf cut); too few "lower bar" / "drop bar"."""
+        launches, head_trouble, head_stale = self.launches, self.head_trouble, self.head_stale
+
+        def again(action: str, failing: str, drop_heads: bool = False) -> Verdict:
+            n = launches - 1                                  # (the same launch again, not a corrected bar: it does not count twice)
+            if n + 2 > MAX_LAUNCHES:
+                raise ops._lib.EpsError(f"scan_topk: {failing} kept failing")
+            return Verdict(action, n, drop_heads, head_trouble, head_stale)
+
+        if any(t.kernel & _KS_SKETCH_SET_FULL for t in table):
+            # (a bar far below what K asks for: the launch is void, the call goes on with hashed packed pieces)
+            return again("sketch off", "launches with sketch pieces")
+        if any(t.kernel & ~(_KS_HEADS_HIGHER_BAR | _KS_SKETCH_RAN) for t in table):
+            raise ops._lib.EpsError("scan_topk: eps_scan_screen reported a full hash table (status %s)" % [t.kernel for t in table])
+        drop_heads = False
+        if head_budget is not None:
+            # The head table was taken without looking at the bar.  A head as heavy as the bar (the bar fell since the table was
+            # built), a bar below the lowest one the table -- and its list of live columns -- was built for, or a walked list that
+            # overflowed: the launch is void; twice in a row: this call goes on without heads.
+            bar_units = table[0].bar * 2.0 ** shift
+            overflow = any(t.walked > walked_cap for t in table)
+            stale = any(t.kernel & _KS_HEADS_HIGHER_BAR for t in table) or head_budget > HEAD_KEEP[1] * bar_units
+            # (a budget out of range on a good launch only costs time: the NEXT launch takes a table for its bar)
+            drop_heads = overflow or stale or not HEAD_KEEP[0] * bar_units <= head_budget <= HEAD_KEEP[1] * bar_units
+            if overflow or stale:
+                # two causes, two remedies (ADVICE r05): a table built for another bar is simply rebuilt; only an overflowing walked
+                # list grows the list and counts toward giving heads up for this call
+                head_trouble, head_stale = head_trouble + overflow, head_stale + (not overflow)
+                action = "heads off" if head_trouble >= 2 or head_stale >= 3 else "grow walked list" if overflow else "rebuild heads"
+                return again(action, "launches with skipped heads", drop_heads)
+        slot_overflow = any(t.slots > capacity for t in table)
+        if screened and not self.rescore_all and not slot_overflow and any(table[0].cut < t.pre_thr for t in table):
+            # the pre-filter was sound iff the cut reaches every rank's threshold (floats compared on the host).
+            # A cut of -inf -- fewer than k2 re-scored pairs job-wide -- is NOT exempt (ADVICE r04): with uneven shards one rank's
+            # pre-filter may have held back pairs that belong to the k2 best while another rank had too few to fill its share, so
+            # any finite threshold above a -inf cut sends the step round again with everything re-scored.  Only when no rank
+            # filtered at all (every threshold -inf) does -inf mean "fewer than k2 pairs survived": the bar is lowered below.
             return again("rescore all", "the re-scoring pre-filter", drop_heads)
-    if slot_overflow:
-        # the bar was too low for the list.  What was kept is a subset of the survivors, so the k2-th best score among it (the
-        # cut, job-wide) is a lower bound of the final cut: scan again just below it, with more room (a level of tied scores --
-        # common-neighbour counts -- may hold far more pairs than K)
-        return Verdict("rescan wider" if cut_is_inf else "rescan below cut", launches, drop_heads, head_trouble, head_stale)
-    # (a launch with skipped heads counts the candidates its walk touched, not all of them: fewer than k2 selected under a bar
-    #  then always means "lower the bar" -- the launch without one counts them all)
-    n_cand, n_sel = sum(t[1] for t in table), sum(t[2] for t in table)
-    if bar_set and n_sel < (k2 if head_budget is not None else min(k2, n_cand)):
-        return Verdict("drop bar" if launches > 3 else "lower bar", launches, drop_heads, head_trouble, head_stale)
-    return Verdict("done", launches, drop_heads, head_trouble, head_stale)
+        if slot_overflow:
+            # the bar was too low for the list.  What was kept is a subset of the survivors, so the k2-th best score among it (the
+            # cut, job-wide) is a lower bound of the final cut: scan again just below it, with more room (a level of tied scores --
+            # common-neighbour counts -- may hold far more pairs than K)
+            return Verdict("rescan wider" if table[0].cut_is_neg_inf else "rescan below cut", launches, drop_heads, head_trouble, head_stale)
+        # (a launch with skipped heads counts the candidates its walk touched, not all of them: fewer than k2 selected under a bar
+        #  then always means "lower the bar" -- the launch without one counts them all)
+        n_cand, n_sel = sum(t.candidates for t in table), sum(t.n_sel for t in table)
+        if bar_set and n_sel < (k2 if head_budget is not None else min(k2, n_cand)):
+            return Verdict("drop bar" if launches > 3 else "lower bar", launches, drop_heads, head_trouble, head_stale)
+        return Verdict("done", launches, drop_heads, head_trouble, head_stale)
 
-
-def _status_words(res: ops.Survivors, status, pre_thr, bar) -> List[torch.Tensor]:
-    """A rank's six int64 status words (1-element tensors; zero where the launch has none): [slots, candidates, kernel status,
-    pre-filter threshold bits, walked slots, bar bits] -- a row of the status table without n_sel and the cut (after the second)."""
-    zero = torch.zeros(1, dtype=torch.int64, device=res.rec.device)
-    return [res.rec[1:2], res.rec[4:5],
-            status.to(torch.int64) if status is not None else zero,
-            pre_thr.view(torch.int32).to(torch.int64) if pre_thr is not None else zero,
-            res.walked_slots if res.walked_slots is not None else zero,
-            bar.view(torch.int32).to(torch.int64) if bar is not None else zero]
+    def apply(self, v: Verdict, total_half: int, world: int) -> str:
+        """Take the verdict's counters and make its action's change; -> what becomes of the bar: "keep", "below cut" (the next
+        float below the cut), "estimate" (a new sample aimed at ``safety``: a quarter of the sample rank each time) or "none"."""
+        self.launches, self.head_trouble, self.head_stale = v.launches, v.head_trouble, v.head_stale
+        if v.action == "sketch off":
+            self.sketch, self.sketch_void = False, self.sketch_void + 1
+        elif v.action == "grow walked list":
+            self.head_list *= 2
+        elif v.action == "heads off":
+            self.use_heads = False
+        elif v.action == "rescore all":
+            self.rescore_all = True
+        elif v.action in ("rescan below cut", "rescan wider"):
+            self.wanted *= 4
+        elif v.action in ("lower bar", "drop bar"):
+            self.safety = SAFETY * 8 ** (self.launches - 1)
+            self.launches += 1                                # (the new estimate's sample launch, or its place)
+            if v.action == "drop bar":
+                self.wanted = 2 * total_half // world         # (room for every candidate)
+        return {"rescan below cut": "below cut", "lower bar": "estimate", "drop bar": "none"}.get(v.action, "keep")
 
 
 def _device_tail(g: CSRGraph, screen: Screen, res: ops.Survivors, bar: torch.Tensor, k: int, k2: int, params, bits: int, perm):
     """One rank under a bar: pre-filter, exact re-scoring (not for Screen.exact) and cut from score-bucket histograms
     (csrc/tail_sort.hip).  Threshold and cut are the lower edges of the buckets that hold the k2-th best screening / exact score
-    (<= the exact order statistics: a few pairs more are re-scored and sorted, the K rows are the same; _verdict checks both).
+    (<= the exact order statistics: a few pairs more are re-scored and sorted, the K rows are the same; _Retry.verdict checks both).
     -> (status table, selected keys, values, cut, pairs re-scored, rows).  TAIL_SORT = "library": library sorts, sized from the
     host (host read 1: the pre-filter's count), rows = None -- faster on MI355X than "radix": a grid-wide hand-over inside a kernel
     costs ~50 us there, a kernel boundary ~10 (profiles/r06/sort_probe.txt); "radix": cooperative sorts sized on the device, the
@@ -1100,23 +1160,13 @@ def _device_tail(g: CSRGraph, screen: Screen, res: ops.Survivors, bar: torch.Ten
         ops.score_hist(x_keys, x_vals, count, bar, above=bar)
         sel_k, sel_v, n_sel, cut, _ = ops.score_pick_compact(x_keys, x_vals, count, bar, k2, above=bar, swap_halves=not screen.exact,
                                                              room=sel_room)
+        row = (res.rec[1:2], res.rec[4:5], n_sel, cut, res.status, pre_thr, res.walked_slots, bar)
         if library:
-            # (the status vector as 32-bit words -- views, ONE cat launch, no dtype conversions: [slots lo hi, candidates lo hi,
-            #  n_sel lo hi, cut, kernel status, pre-filter threshold, walked slots lo hi, bar])
-            w32 = torch.cat([res.rec[1:2].view(torch.int32), res.rec[4:5].view(torch.int32), n_sel.view(torch.int32),
-                             cut.view(torch.int32), res.status, pre_thr.view(torch.int32),
-                             (res.walked_slots if res.walked_slots is not None else res.rec[1:2]).view(torch.int32),
-                             bar.view(torch.int32)]).tolist()                                 # the host read of the step
-            u64 = lambda lo, hi: (lo & 0xFFFFFFFF) | (hi << 32)                              # noqa: E731
-            table = [[u64(*w32[0:2]), u64(*w32[2:4]), u64(*w32[4:6]), w32[6], w32[7], w32[8],
-                      u64(*w32[9:11]) if res.walked_slots is not None else 0, w32[11]]]
-            return table, sel_k, sel_v, cut, 0 if screen.exact else nv, None
+            return [_unpack_status(_pack_status(*row).tolist())], sel_k, sel_v, cut, 0 if screen.exact else nv, None   # the host read of the step
         r_pairs, r_scores, n_rows = ops.radix_sort_rows(sel_k, sel_v, n_sel, k, bits, perm)
-        w = _status_words(res, res.status, pre_thr, bar)
-        row = torch.cat(w[:2] + [n_sel, cut.view(torch.int32).to(torch.int64)] + w[2:] + [n_valid, n_rows]).tolist()   # the host read
-        nv = row[8]
+        st, (nv, n_out) = _unpack_status(_pack_status(*row, extra=(n_valid, n_rows)).tolist(), extra=2)      # the host read
         if nv <= room:
-            return [row[:8]], sel_k, sel_v, cut, 0 if screen.exact else nv, (r_pairs, r_scores, row[9])
+            return [st], sel_k, sel_v, cut, 0 if screen.exact else nv, (r_pairs, r_scores, n_out)
         room = min(res.capacity, nv)
 
 
@@ -1124,7 +1174,7 @@ def _prefilter(g: CSRGraph, screen: Screen, res: ops.Survivors, bar, k2: int, pa
     """This rank's survivors of the one-pass kernel that can reach the job's k2 best, re-scored exactly (those that do not exceed
     the bar after all drop out).  -> (keys, scores, pre-filter threshold, pairs re-scored, room).  With t = lower(the k_pre-th best
     screening score of THIS rank's list) every pair that is not re-scored has an exact score < t (Screen.lower_bound), so the cut
-    is final iff it is >= every rank's t (_verdict).  k_pre = k2 / world: the shards are dealt round-robin out of one
+    is final iff it is >= every rank's t (_Retry.verdict).  k_pre = k2 / world: the shards are dealt round-robin out of one
     heaviest-first order, so a rank's (k2 / world)-th best sits at the job's k2-th best; lower() leaves ~4 % of margin."""
     k_pre = 0 if rescore_all else (k2 + world - 1) // world
     # (2 x k_pre pairs: lower() keeps ~10 % more than k_pre; tied scores at the threshold beyond the room: once more with room for all)
@@ -1144,24 +1194,22 @@ def _prefilter(g: CSRGraph, screen: Screen, res: ops.Survivors, bar, k2: int, pa
 def _read_exchange(got: torch.Tensor, nsel_all: torch.Tensor, cut: torch.Tensor, counts: torch.Tensor, world: int):
     """(status table, deal counts) of a sharded step from its exchange ``got``, the selection counts, the cut and the deal plan's
     counts: ONE host read -- fixed shapes, nothing waits for a size."""
-    heads6 = got[:, :12].contiguous().view(torch.int64)                                          # [world, 6]
-    st_all = torch.cat([heads6[:, :2], nsel_all.unsqueeze(1), cut.view(torch.int32).to(torch.int64).expand(world, 1),
-                        heads6[:, 2:]], 1)
-    flat = torch.cat([st_all.reshape(-1), counts.reshape(-1)]).tolist()                         # the host read of the step
-    return ([flat[r * 8:(r + 1) * 8] for r in range(world)],
-            [flat[8 * world + r * world:8 * world + (r + 1) * world] for r in range(world)])
+    rows = got[:, :_STATUS_WORDS].reshape(-1).to(torch.int64)        # (the ranks' packed rows, n_sel and the cut still empty)
+    flat = torch.cat([rows, cut.view(torch.int32).to(torch.int64), nsel_all, counts.reshape(-1)]).tolist()   # the host read of the step
+    nsel, deal = flat[rows.numel() + 1:][:world], flat[rows.numel() + 1 + world:]
+    return ([_unpack_status(flat[r * _STATUS_WORDS:(r + 1) * _STATUS_WORDS])._replace(n_sel=nsel[r], cut_bits=flat[rows.numel()])
+             for r in range(world)], [deal[r * world:(r + 1) * world] for r in range(world)])
 
 
-def _cut_from_histograms(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, bar: torch.Tensor, world: int):
+def _cut_from_histograms(keys: torch.Tensor, vals: torch.Tensor, row, k2: int, bar: torch.Tensor, world: int):
     """A sharded step under a bar (DIST_HIST): ONE exchange of 25 KB per rank -- every rank's histogram of its re-scored scores
-    over buckets of their distance to the (common) bar behind its six status words.  From it every rank derives in ONE launch
-    (ops.score_deal_plan) the cut -- the lower edge of the bucket of the k2-th best score: the K rows are the same --, everybody's
+    over buckets of their distance to the (common) bar behind its status row (``row``: _pack_status's
+    arguments).  From it every rank derives in ONE launch (ops.score_deal_plan) the cut -- the lower edge of the bucket of the k2-th best score: the K rows are the same --, everybody's
     selection count and the deal plan of the final ordering.  -> (selected keys, values, cut, status table, deal plan)."""
     from . import dist as epd
     bins = ops.score_bins()
-    head = torch.cat(words).view(torch.int32)
-    send = torch.zeros(_XCHG_HEAD + bins, dtype=torch.int32, device=head.device)
-    send[:head.numel()] = head
+    send = torch.zeros(_XCHG_HEAD + bins, dtype=torch.int32, device=vals.device)
+    send[:_STATUS_WORDS] = _pack_status(**row)
     ops.score_hist_into(keys, vals, None, bar, send[_XCHG_HEAD:], above=bar)
     got = epd._gather_into(send, world).view(world, _XCHG_HEAD + bins)
     cut, sp, counts, nsel_all = ops.score_deal_plan(got[:, _XCHG_HEAD:], k2, bar)
@@ -1170,16 +1218,15 @@ def _cut_from_histograms(keys: torch.Tensor, vals: torch.Tensor, words, k2: int,
     return sel_k, sel_v, cut, table, (sp, deal_c)
 
 
-def _cut_from_scores(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, room: int, world: int):
+def _cut_from_scores(keys: torch.Tensor, vals: torch.Tensor, row, k2: int, room: int, world: int):
     """The same from an exchange of the scores themselves (no bar -- small candidate sets -- or DIST_HIST off): every rank selects
     the same cut from the same gathered scores.  The exchange must hold the longest list, which tied scores at a pre-filter
     threshold may have grown beyond its ``room``: the ranks agree on it first (one all-reduced word)."""
     from . import dist as epd
     dev = vals.device
     room = max(room, -int(epd.all_reduce_min_(torch.tensor([-int(vals.numel())], dtype=torch.int64, device=dev)).item()))
-    head = torch.cat(words).view(torch.int32)
     send = torch.full((_XCHG_HEAD + room,), _NEG_INF_BITS, dtype=torch.int32, device=dev)
-    send[:head.numel()] = head
+    send[:_STATUS_WORDS] = _pack_status(**row)
     send[_XCHG_HEAD:_XCHG_HEAD + vals.numel()] = vals.view(torch.int32)
     got = epd._gather_into(send, world).view(world, _XCHG_HEAD + room)
     scores_all = got[:, _XCHG_HEAD:].contiguous().view(torch.float32)
@@ -1191,7 +1238,7 @@ def _cut_from_scores(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, roo
     return sel_k, sel_v, cut, table, (sp, deal_c)
 
 
-def _cut_local(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, screened: bool, world: int):
+def _cut_local(keys: torch.Tensor, vals: torch.Tensor, row, k2: int, screened: bool, world: int):
     """The cut -- the k2-th best score, -inf when fewer survived -- and the selection without an exchange of scores: one rank, or a
     job without the one-pass kernel or re-scoring everything (a job-wide select, an all-gather of the status rows); no deal plan."""
     if not _sharded(world) and screened:
@@ -1199,11 +1246,11 @@ def _cut_local(keys: torch.Tensor, vals: torch.Tensor, words, k2: int, screened:
     else:
         cut = ops.kth_largest_dist(vals, k2, world)
         sel_k, sel_v, n_sel = ops.compact_at_least(keys, vals, cut)
-    st = torch.cat(words[:2] + [n_sel, cut.view(torch.int32).to(torch.int64)] + words[2:])
+    st = _pack_status(n_sel=n_sel, cut=cut, **row)
     if _sharded(world):
         from . import dist as epd
-        return sel_k, sel_v, cut, torch.stack(epd.all_gather_list(st)).tolist(), None            # the host read of the step
-    return sel_k, sel_v, cut, [st.tolist()], None
+        st = torch.stack(epd.all_gather_list(st))
+    return sel_k, sel_v, cut, [_unpack_status(r) for r in st.view(-1, _STATUS_WORDS).tolist()], None      # the host read of the step
 
 
 def _ordered_rows(sel_k: torch.Tensor, sel_v: torch.Tensor, nsel_r: List[int], deal, k: int, bits: int, perm, rank: int,
@@ -1245,20 +1292,20 @@ def _ordered_rows(sel_k: torch.Tensor, sel_v: torch.Tensor, nsel_r: List[int], d
 
 
 def _step_stats(stats: dict, g: CSRGraph, screen: Optional[Screen], fixw, table, ht: Optional[HeadTables], capacity: int,
-                launches: int, sketch_void: int, n_rescored, shard, bar, rank: int, world: int) -> None:
+                state: _Retry, n_rescored, shard, bar, rank: int, world: int) -> None:
     """scan_topk's ``stats`` from the final status table.  survivors: DIRECTED rows at or above the job-wide cut; survivor_slots:
     list slots the launches handed out (chunks: holes included); bar: None or a 1-element device tensor; candidates: DIRECTED 2-hop
     non-edges the filter covered.  A launch with skipped heads counts only those its walk touched (`touched`); the exact number
     then comes from `candidate_count` (one counting scan per graph, cached) unless ``stats`` holds count=False (candidates None)."""
-    n_cand, n_sel = sum(t[1] for t in table), sum(t[2] for t in table)
+    n_cand, n_sel = sum(t.candidates for t in table), sum(t.n_sel for t in table)
     if ht is None and world == 1:
         g._cache.setdefault("n_candidates", n_cand)
     n_all = 2 * n_cand if ht is None else 2 * candidate_count(g, screen, fixw, rank, world) if stats.get("count", True) else None
-    stats.update(candidates=n_all, touched=2 * n_cand, launches=launches, survivors=2 * n_sel, heads=ht is not None, shard=shard,
-                 sketch=any(t[4] & 16 for t in table), sketch_void=sketch_void,      # (status bit 4: sketch pieces ran)
+    stats.update(candidates=n_all, touched=2 * n_cand, launches=state.launches, survivors=2 * n_sel, heads=ht is not None, shard=shard,
+                 sketch=any(t.kernel & _KS_SKETCH_RAN for t in table), sketch_void=state.sketch_void,
                  head_budget=None if ht is None else ht.budget * 2.0 ** -screen.shift,
-                 walked_slots=sum(t[6] for t in table) if ht is not None else None, rescored=n_rescored,
-                 survivor_slots=sum(min(t[0], capacity) for t in table), bar=bar)
+                 walked_slots=sum(t.walked for t in table) if ht is not None else None, rescored=n_rescored,
+                 survivor_slots=sum(min(t.slots, capacity) for t in table), bar=bar)
 
 
 def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: int = 1, stats: Optional[dict] = None,
@@ -1274,7 +1321,7 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     The stages, tables cached on the graph: the bar (estimate_bar: a sample launch; on the device) -> the main launch (_launch:
     under a bar with skipped heads) -> one rank under a bar: the device tail (_device_tail); else the pre-filter and exact
     re-scoring of this rank's list (_prefilter) and the job-wide cut with the status table (_cut_from_histograms, _cut_from_scores,
-    _cut_local) -> the verdict on the status table (_verdict), which VERIFIES the step -- else the launch repeats with what was
+    _cut_local) -> the verdict on the status table (_Retry.verdict), which VERIFIES the step -- else the launch repeats with what was
     learnt -> the rows (_ordered_rows) and the stats (_step_stats).  Host reads per step on one rank: two (the pre-filter's count,
     the status table); TAIL_SORT = "radix": one."""
     if relabel and scan_plausible(g):
@@ -1295,102 +1342,75 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     total_half = total_half_paths(g)
     k2 = (k + 1) // 2                    # the k-th best directed row belongs to the ceil(k/2)-th best unordered pair
     bits = max(1, min(32, int(g.n_rows - 1).bit_length()))
-    screen = None
-    if one_pass_available(g):
-        sc = screen_weights(g0, g, perm, node_w)
-        if sc.usable:
-            screen = sc
+    screen = screen_weights(g0, g, perm, node_w) if one_pass_available(g) else None
+    if screen is not None and not screen.usable:
+        screen = None
     if screen is None and g.val is not None:
         raise ops._lib.EpsError("scan_topk: this weighted graph / weight table does not fit the one-pass scan (see scan_available)")
     slack = _CHUNK_SLACK if screen is None else _PIECE_SLACK
-    launches = 0
-    bar = None
-    rescore_all = False                  # (set when a rank's pre-filter threshold turned out to lie above the job-wide cut)
-    if total_half > SMALL_SET and SAFETY * k < total_half:
-        bar = estimate_bar(g, fixw, k, rank=rank, world=world, screen=screen)
-        launches += 1
+    sampled = total_half > SMALL_SET and SAFETY * k < total_half
+    bar = estimate_bar(g, fixw, k, rank=rank, world=world, screen=screen) if sampled else None
     # unordered survivors expected: SAFETY x k / 2 over all ranks; the list holds four times that (the estimate has been within
-    # a factor 0.35 .. 1.7), or every candidate without a bar
-    wanted = (2 * total_half if bar is None else int(2 * SAFETY * k)) // world
-    capacity = _capacity(wanted, slack)
-    # skipped heads (csrc/scan_heads.hip): unit-valued graphs with a plan table, under a bar
-    use_heads = (HEADS and screen is not None and screen.has_plan and screen.ssum is not None and g.val is None
-                 and total_half >= HEAD_MIN_PATHS)
+    # a factor 0.35 .. 1.7), or every candidate without a bar.  Skipped heads (csrc/scan_heads.hip): unit-valued graphs with a
+    # plan table, under a bar
+    state = _Retry(int(sampled), (2 * total_half if bar is None else int(2 * SAFETY * k)) // world, HEAD_LIST, sketch=SKETCH_PIECES,
+                   use_heads=bool(HEADS and screen is not None and screen.has_plan and screen.ssum is not None and g.val is None
+                                  and total_half >= HEAD_MIN_PATHS))
+    capacity = _capacity(state.wanted, slack)
     _count_scan(g, screen)
-    head_list, head_trouble, head_stale = HEAD_LIST, 0, 0
-    sketch, sketch_void = SKETCH_PIECES, 0
     n_rescored = None
     while True:
-        if launches >= MAX_LAUNCHES:
-            raise ops._lib.EpsError(f"scan_topk: no usable bar after {launches} launches (k = {k}, capacity {capacity})")
+        if state.launches >= MAX_LAUNCHES:
+            raise ops._lib.EpsError(f"scan_topk: no usable bar after {state.launches} launches (k = {k}, capacity {capacity})")
         # sketch pieces (and the plan made for them: packed pieces of twice the paths) when the bar is several of the heaviest weight
         # (not when the screening sums ARE the scores -- Screen.exact, common neighbours: a sketch piece's sums are upper bounds, and
         #  nothing re-scores them there)
         def sketch_for(budget):
-            return bool(sketch and screen is not None and screen_variant(g) == 2 and not screen.exact
+            return bool(state.sketch and screen is not None and screen_variant(g) == 2 and not screen.exact
                         and (int(screen.w_max_units) + 2) * SKETCH_PIECE_PATHS < 1 << 32     # (no slot can wrap: screen_weights saw to it)
                         and budget >= HEAD_BETA * SKETCH_MIN_PATHS * screen.w_max_units)
-        ht = (_heads_for(g, screen, bar, sketch_for) if use_heads and bar is not None else None)
-        want_sketch = ht is not None and sketch_for(ht.budget)
-        walked_cap = max(1, min(int(head_list * capacity), ops.SURVIVOR_SLOTS_MAX)) if ht is not None else 0
+        ht = (_heads_for(g, screen, bar, sketch_for) if state.use_heads and bar is not None else None)
+        walked_cap = max(1, min(int(state.head_list * capacity), ops.SURVIVOR_SLOTS_MAX)) if ht is not None else 0
         res = _launch(g, fixw, mine if ht is None else live_columns(g, screen, ht, rank, world), float("-inf") if bar is None else bar,
-                      capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap,
-                      sketch=want_sketch)
-        launches += 1
+                      capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap, sketch=ht is not None and sketch_for(ht.budget))
+        state.launches += 1
         rows = deal = None
         if screen is not None:
             params = screen.lower_params(max_degree(g), None if ht is None else ht.d_used) + (4e-6,)
-        if (TAIL_DEVICE and not _sharded(world) and screen is not None and g.val is None and bar is not None and not rescore_all
+        if (TAIL_DEVICE and not _sharded(world) and screen is not None and g.val is None and bar is not None and not state.rescore_all
                 and k2 + (1 << 16) < (1 << 30)):
             table, sel_k, sel_v, cut, n_rescored, rows = _device_tail(g, screen, res, bar, k, k2, params, bits, perm)
         else:
             keys, vals, pre_thr, room = res.key, res.val, None, 0
             if screen is not None:
-                keys, vals, pre_thr, n_rescored, room = _prefilter(g, screen, res, bar, k2, params, world, rescore_all)
-            words = _status_words(res, None if screen is None else res.status, pre_thr, bar)
-            exchange = _sharded(world) and screen is not None and not rescore_all
-            if exchange and bar is not None and DIST_HIST:
-                sel_k, sel_v, cut, table, deal = _cut_from_histograms(keys, vals, words, k2, bar, world)
-            elif exchange:
-                sel_k, sel_v, cut, table, deal = _cut_from_scores(keys, vals, words, k2, room, world)
-            else:
-                sel_k, sel_v, cut, table, deal = _cut_local(keys, vals, words, k2, screen is not None, world)
-        v = _verdict(table, capacity, walked_cap, None if ht is None else ht.budget, None if ht is None else screen.shift,
-                     screen is not None, rescore_all, k2, bar is not None, launches, head_trouble, head_stale)
-        launches, head_trouble, head_stale = v.launches, v.head_trouble, v.head_stale
+                keys, vals, pre_thr, n_rescored, room = _prefilter(g, screen, res, bar, k2, params, world, state.rescore_all)
+            row = dict(slots=res.rec[1:2], candidates=res.rec[4:5], status=None if screen is None else res.status, pre_thr=pre_thr,
+                       walked=res.walked_slots, bar=bar)
+            exchange = _sharded(world) and screen is not None and not state.rescore_all
+            sel_k, sel_v, cut, table, deal = (_cut_from_histograms(keys, vals, row, k2, bar, world) if exchange and bar is not None and DIST_HIST
+                                              else _cut_from_scores(keys, vals, row, k2, room, world) if exchange
+                                              else _cut_local(keys, vals, row, k2, screen is not None, world))
+        v = state.verdict(table, capacity=capacity, walked_cap=walked_cap, head_budget=None if ht is None else ht.budget,
+                          shift=None if ht is None else screen.shift, screened=screen is not None, k2=k2, bar_set=bar is not None)
+        new_bar = state.apply(v, total_half, world)
         if v.drop_heads:
             screen.head_cur = None
         if v.action == "done":
             break
-        if v.action == "sketch off":
-            sketch, sketch_void = False, sketch_void + 1
-        elif v.action == "grow walked list":
-            head_list *= 2
-        elif v.action == "heads off":
-            use_heads = False
-        elif v.action == "rescore all":
-            rescore_all = True
-        elif v.action in ("rescan below cut", "rescan wider"):
-            if v.action == "rescan below cut":
-                bar = torch.nextafter(cut, torch.full_like(cut, float("-inf")))
-            wanted *= 4
-        elif v.action in ("lower bar", "drop bar"):
-            # (a quarter of the sample rank each time, then no bar at all)
-            bar = None if v.action == "drop bar" else estimate_bar(g, fixw, k, safety=SAFETY * 8 ** (launches - 1), rank=rank,
-                                                                   world=world, screen=screen)
-            launches += 1
-            if bar is None:
-                wanted = 2 * total_half // world
-        capacity = _capacity(wanted, slack)
-    if screen is not None and bar is not None:
+        if new_bar == "below cut":
+            bar = torch.nextafter(cut, torch.full_like(cut, float("-inf")))
+        elif new_bar == "estimate":
+            bar = estimate_bar(g, fixw, k, safety=state.safety, rank=rank, world=world, screen=screen)
+            if bar is None:                                   # (the sample cannot hold that many: no bar, as after "drop bar")
+                state.wanted = 2 * total_half // world
+        elif new_bar == "none":
+            bar = None
+        capacity = _capacity(state.wanted, slack)
+    if screen is not None and bar is not None and 0.0 < table[0].bar < float("inf"):
         # (the bar this scan ended with, for the next scan's estimate at the same K: see estimate_bar)
-        bar_f = _f32_from_bits(table[0][7])
-        if 0.0 < bar_f < float("inf"):
-            screen.bar_hint[(k, sample_stride(k), float(SAFETY))] = bar_f
-    if rows is not None:
-        pairs, scores, shard = rows[0][:, :rows[2]], rows[1][:rows[2]], None
-    else:
-        pairs, scores, shard = _ordered_rows(sel_k, sel_v, [t[2] for t in table], deal, k, bits, perm, rank, world, rows_on)
+        screen.bar_hint[(k, sample_stride(k), float(SAFETY))] = table[0].bar
+    pairs, scores, shard = ((rows[0][:, :rows[2]], rows[1][:rows[2]], None) if rows is not None else
+                            _ordered_rows(sel_k, sel_v, [t.n_sel for t in table], deal, k, bits, perm, rank, world, rows_on))
     if stats is not None:
-        _step_stats(stats, g, screen, fixw, table, ht, capacity, launches, sketch_void, n_rescored, shard, bar, rank, world)
+        _step_stats(stats, g, screen, fixw, table, ht, capacity, state, n_rescored, shard, bar, rank, world)
     return pairs, scores

@@ -173,6 +173,12 @@ def test_scan_topk_device_tail_is_bit_identical(eps, dev, kind, monkeypatch):
             for tail in ("library", "radix"):
                 assert torch.equal(out[tail][0], out[None][0]) and torch.equal(out[tail][1], out[None][1]), (kind, relabel, k, tail)
                 assert out[tail][2]["candidates"] == out[None][2]["candidates"]
+            # (the two device tails take the same cut from the same histograms: the same status row, however it travelled --
+            #  but for `walked_slots`: the walked list hands its slots out in chunks per workgroup, so the count depends on
+            #  which workgroup drew which column and differs between two launches of the same step)
+            for key in ("survivors", "launches", "touched", "survivor_slots"):
+                print(kind, relabel, k, key, out["library"][2][key], out["radix"][2][key])
+                assert out["library"][2][key] == out["radix"][2][key], (kind, relabel, k, key)
     assert _state_is_clean(eps, dev)
 
 

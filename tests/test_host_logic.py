@@ -420,24 +420,32 @@ def test_sketch_safe_shift_keeps_a_whole_piece_below_2_32():
 
 def _status(slots=100, cand=5000, n_sel=60, cut=1.0, status=0, thr=float("-inf"), walked=0, bar=0.5):
     """One rank's row of scan_topk's status table, as the step's host read returns it (float words as signed int32 bits)."""
+    from eps_amd import scan
     bits = lambda x: int(np.float32(x).view(np.int32))                    # noqa: E731
-    return [slots, cand, n_sel, bits(cut), status, bits(thr), walked, bits(bar)]
+    return scan.StepStatus(slots, cand, n_sel, bits(cut), status, bits(thr), walked, bits(bar))
+
+
+def _retry(**kw):
+    """A scan._Retry at the second launch: 400 slots wanted, walked list x 2, heads and sketch pieces on, nothing gone wrong yet."""
+    from eps_amd import scan
+    return scan._Retry(**{**dict(launches=2, wanted=400, head_list=2, use_heads=True, sketch=True), **kw})
 
 
 def _verdict(table, **kw):
-    """scan._verdict of a one-rank (or given) table: capacity 1000, k2 = 50, screened, under a bar, at the second launch, no heads
-    unless ``head_budget`` is given (then shift 8: the bar of 0.5 is 128 table units, budgets 38.4 .. 74.24 are in range)."""
+    """scan._Retry.verdict of a one-rank (or given) table: capacity 1000, k2 = 50, screened, under a bar, at the second launch, no
+    heads unless ``head_budget`` is given (then shift 8: the bar of 0.5 is 128 table units, budgets 38.4 .. 74.24 are in range);
+    ``launches``, ``head_trouble``, ``head_stale``, ``rescore_all``: the state's."""
     from eps_amd import scan
-    args = dict(capacity=1000, walked_cap=100, head_budget=None, shift=None, screened=True, rescore_all=False, k2=50,
-                bar_set=True, launches=2, head_trouble=0, head_stale=0)
+    state = _retry(**{f: kw.pop(f) for f in ("launches", "head_trouble", "head_stale", "rescore_all") if f in kw})
+    args = dict(capacity=1000, walked_cap=100, head_budget=None, shift=None, screened=True, k2=50, bar_set=True)
     if kw.get("head_budget") is not None:
         args["shift"] = 8
     args.update(kw)
-    return scan._verdict(table if isinstance(table[0], list) else [table], **args)
+    return state.verdict([table] if isinstance(table, scan.StepStatus) else table, **args)
 
 
 def test_scan_verdict_repeats_void_launches():
-    """scan._verdict, the step's retry decision: a void launch (sketch set full, head table void, pre-filter unsound) repeats the
+    """scan._Retry.verdict, the step's retry decision: a void launch (sketch set full, head table void, pre-filter unsound) repeats the
     SAME launch -- it does not count twice --, in the parent's order of checks; unknown status bits raise."""
     from eps_amd import ops
     v = _verdict(_status(status=8 | 16))
@@ -477,7 +485,7 @@ def test_scan_verdict_repeats_void_launches():
 
 
 def test_scan_verdict_corrects_the_bar():
-    """scan._verdict after a sound launch: an overflowing list rescans just below the cut with four times the list (under the same
+    """scan._Retry.verdict after a sound launch: an overflowing list rescans just below the cut with four times the list (under the same
     bar when the cut is -inf) -- before any pre-filter check; too few pairs above the bar lower it, and drop it after launch 3;
     and every repeat of the same launch ends the call with EpsError once it would pass MAX_LAUNCHES."""
     from eps_amd import ops, scan
@@ -503,3 +511,88 @@ def test_scan_verdict_corrects_the_bar():
                          (_status(status=4), {"head_budget": 64}, "skipped heads"), (_status(thr=2.0), {}, "re-scoring pre-filter")):
         with pytest.raises(ops._lib.EpsError, match=msg):
             _verdict(row, launches=scan.MAX_LAUNCHES, **kw)
+
+
+def test_status_row_round_trips_through_its_wire_format():
+    """scan._unpack_status(scan._pack_status(...).tolist()) is the row that went in -- counts beyond 32 bits, negative float and
+    status words, absent parts as zero, n_sel / cut filled in behind the exchange, extra words behind the row (floats through
+    their bits)."""
+    from eps_amd import ops, scan
+    i64 = lambda x: torch.tensor([x], dtype=torch.int64)                                  # noqa: E731
+    f32 = lambda x: torch.tensor([x], dtype=torch.float32)                                # noqa: E731
+    bits = lambda x: int(np.float32(x).view(np.int32))                                    # noqa: E731
+    assert scan._STATUS_WORDS == 12 <= scan._XCHG_HEAD
+    cand = 12_727_571_774                                                                  # (the ppa-like graph's candidates)
+    for cut in (float("-inf"), -3.25, 0.0, 1.5):
+        for kernel in (0, 4 | 16, (1 << 31) | 16):
+            k32 = kernel - (1 << 32) if kernel >> 31 else kernel                           # (as int32, what the device word reads as)
+            packed = scan._pack_status(i64(ops.SURVIVOR_SLOTS_MAX), i64(cand), i64(3_000_000_000), f32(cut),
+                                       torch.tensor([k32], dtype=torch.int32), f32(-0.75), i64(1 << 33), f32(0.085))
+            assert packed.dtype == torch.int32 and packed.shape == (12,)
+            st = scan._unpack_status(packed.tolist())
+            assert st == (ops.SURVIVOR_SLOTS_MAX, cand, 3_000_000_000, bits(cut), k32, bits(-0.75), 1 << 33, bits(0.085))
+            assert st.kernel & 0xFFFFFFFF == kernel and bool(st.kernel & scan._KS_SKETCH_RAN) == bool(kernel & 16)
+            assert bits(st.cut) == bits(cut) and bits(st.pre_thr) == bits(-0.75) and bits(st.bar) == bits(0.085)
+            assert st.cut_is_neg_inf == (cut == float("-inf"))
+            if cut == float("-inf"):
+                assert st.cut_bits & 0xFFFFFFFF == 0xFF800000 and st.cut_bits < 0
+    # every optional part absent: zeros (the shared zero is not written to)
+    st = scan._unpack_status(scan._pack_status(i64(7), i64(9)).tolist())
+    assert st == (7, 9, 0, 0, 0, 0, 0, 0) and not st.cut_is_neg_inf and st.bar == 0.0
+    assert scan._pack_status(i64(7), i64(9)).tolist() == [7, 0, 9, 0] + [0] * 8
+    # the exchange: the row travels without n_sel and the cut, they are filled in from the job-wide results
+    sent = scan._unpack_status(scan._pack_status(i64(100), i64(cand), status=torch.tensor([16], dtype=torch.int32),
+                                                 pre_thr=f32(0.5), walked=i64(300), bar=f32(0.25)).tolist())
+    assert (sent.n_sel, sent.cut_bits) == (0, 0)
+    full = sent._replace(n_sel=1 << 32, cut_bits=bits(float("-inf")))
+    assert full == (100, cand, 1 << 32, bits(float("-inf")), 16, bits(0.5), 300, bits(0.25)) and full.cut_is_neg_inf
+    assert full.cut == float("-inf") and full.pre_thr == 0.5 and full.bar == 0.25
+    # ... as scan._read_exchange does for every rank's row of the gathered exchange (the deal counts come back in the same read)
+    world = 3
+    got = torch.full((world, scan._XCHG_HEAD + 5), -5, dtype=torch.int32)
+    for r in range(world):
+        got[r, :12] = scan._pack_status(i64(100 + r), i64(cand + r), status=torch.tensor([16], dtype=torch.int32), pre_thr=f32(0.5 + r),
+                                        walked=i64(7 * r), bar=f32(0.25))
+    table, deal = scan._read_exchange(got, torch.tensor([5, 6, 1 << 33]), f32(float("-inf")), torch.arange(9).view(3, 3), world)
+    assert table == [(100 + r, cand + r, (5, 6, 1 << 33)[r], bits(float("-inf")), 16, bits(0.5 + r), 7 * r, bits(0.25)) for r in range(world)]
+    assert all(t.cut_is_neg_inf for t in table) and deal == [[0, 1, 2], [3, 4, 5], [6, 7, 8]]
+    # the radix tail's two words behind the row
+    st, extra = scan._unpack_status(scan._pack_status(i64(1), i64(2), i64(3), f32(4.0), extra=(i64(5_000_000_000), i64(6))).tolist(), extra=2)
+    assert st == (1, 2, 3, bits(4.0), 0, 0, 0, 0) and extra == [5_000_000_000, 6]
+
+
+def test_scan_retry_apply_transitions(monkeypatch):
+    """scan._Retry.apply: what each action of a verdict does to the step's state and to the bar -- the parent's if/elif chain at
+    the end of scan_topk's loop, case by case."""
+    from eps_amd import scan
+    monkeypatch.setattr(scan, "SAFETY", 2.0)
+    fields = ("launches", "wanted", "head_list", "use_heads", "sketch", "head_trouble", "head_stale", "sketch_void", "rescore_all")
+
+    def after(action, launches=2, trouble=0, stale=0, world=1, was=2, **kw):
+        """(what becomes of the bar, the fields that changed, the state) for a verdict with these counters on the state of ``_retry``
+        after ``was`` launches (10 001 half paths in the graph)."""
+        state = _retry(launches=was, **kw)
+        before = {f: getattr(state, f) for f in fields}
+        how = state.apply(scan.Verdict(action, launches, False, trouble, stale), 10_001, world)
+        return how, {f: getattr(state, f) for f in fields if getattr(state, f) != before[f]}, state
+
+    # repeats of the same launch: the verdict has already taken the launch back, apply counts nothing
+    assert after("sketch off", launches=1)[:2] == ("keep", {"launches": 1, "sketch": False, "sketch_void": 1})
+    assert after("sketch off", launches=1, sketch_void=1)[1]["sketch_void"] == 2
+    assert after("grow walked list", launches=1, trouble=1)[:2] == ("keep", {"launches": 1, "head_list": 4, "head_trouble": 1})
+    assert after("grow walked list", launches=1, trouble=1, head_list=4)[1]["head_list"] == 8
+    assert after("rebuild heads", launches=1, stale=1)[:2] == ("keep", {"launches": 1, "head_stale": 1})
+    assert after("heads off", launches=1, trouble=2)[:2] == ("keep", {"launches": 1, "head_trouble": 2, "use_heads": False})
+    assert after("rescore all", launches=1)[:2] == ("keep", {"launches": 1, "rescore_all": True})
+    # corrections of the bar
+    assert after("rescan below cut")[:2] == ("below cut", {"wanted": 1600})
+    assert after("rescan wider")[:2] == ("keep", {"wanted": 1600})
+    for launches in (2, 3):
+        how, changed, state = after("lower bar", launches=launches, was=launches)
+        assert (how, changed) == ("estimate", {"launches": launches + 1})
+        assert state.safety == 2.0 * 8 ** (launches - 1)
+    for world in (1, 3):
+        how, changed, _ = after("drop bar", launches=4, was=4, world=world)
+        assert (how, changed) == ("none", {"launches": 5, "wanted": 2 * 10_001 // world})
+    assert after("done")[:2] == ("keep", {})
+    assert after("done", launches=3, trouble=1, stale=2, was=3)[1] == {"head_trouble": 1, "head_stale": 2}
