@@ -130,6 +130,8 @@ SIGNATURES = {
     "eps_csr_merge_workspace_bytes": (_i64, [_i64]),
     "eps_csr_merge_count": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "eps_csr_merge_fill": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "eps_segment_topk_class_max": (_i64, [_i32]),
+    "eps_segment_topk": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

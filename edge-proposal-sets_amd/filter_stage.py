@@ -45,6 +45,11 @@ def make_parser():
     parser.add_argument('--dist_backend', type=str, default=None, choices=[None, 'nccl', 'gloo'])
     parser.add_argument('--synthetic', action="store_true", default=False)
     parser.add_argument('--keep_top', type=int, default=0)
+    parser.add_argument('--keep_per_node', type=int, default=0, metavar='k',
+                        help='for every node v, save only the k best of its candidates (u, v): score descending, then u ascending '
+                             '-- exactly the first k rows with second column v of the file the same command writes without the '
+                             'flag, in that file\'s order.  A node with fewer than k candidates keeps all of them.  With '
+                             '--keep_top K as well: the first K rows of that result.  Default 0: off, nothing changes')
     parser.add_argument('--shard_proposals', action='store_true',
                         help='sharded runs (torchrun) under --keep_top: every rank writes the chunk of the sorted list it ordered '
                              '(<file>.shard{r}of{N}; rank.py reads the shards in rank order) instead of sending its rows to rank 0')
@@ -101,6 +106,30 @@ def check_decode_args(args) -> None:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("--decode_precision bf16 runs in one process: sharded runs would have to decode the kept pairs again "
                          "on every rank before the gather (DESIGN 8)")
+
+
+def check_per_node_args(args) -> None:
+    """--keep_per_node against the rest of the command line: a ValueError that names the value for what the per-node cut
+    does not serve -- raised before the dataset is read."""
+    k = int(getattr(args, "keep_per_node", 0) or 0)
+    if k < 0:
+        raise ValueError(f"--keep_per_node {k}: the number of proposals kept per node is >= 0 (0: no per-node cut)")
+    if k and (getattr(args, "decode_precision", "fp32") or "fp32") == "bf16":
+        raise ValueError(f"--keep_per_node {k} with --decode_precision bf16: the bf16 pass screens for ONE global K "
+                         "(--keep_top); a per-node cut decodes in fp32")
+    if k >= 1 << 31:
+        raise ValueError(f"--keep_per_node {k}: the selection takes k < 2^31")
+
+
+def per_node_positions(pairs, score: torch.Tensor, v_lo: int, v_hi: int, k: int) -> torch.Tensor:
+    """Positions (ascending) of the candidates of one block of ``scored_blocks`` that the per-node cut keeps: for every column
+    of [v_lo, v_hi) its k best in the declared order (``ops.segment_topk``).  A ``ColumnBlock`` brings its column pointers; an
+    int [2,E] pair tensor is column-major, so its pointers are a search of its v row."""
+    if not isinstance(pairs, torch.Tensor):
+        return ops.segment_topk(pairs.colptr, score, k, counts=pairs.counts)
+    v = pairs[1].contiguous()
+    colptr = torch.searchsorted(v, torch.arange(v_lo, v_hi + 1, dtype=v.dtype, device=v.device)).to(torch.int64)
+    return ops.segment_topk(colptr, score.contiguous(), k)
 
 
 def train_only_graph(split_edge, num_nodes: int, device) -> CSRGraph:
@@ -363,6 +392,7 @@ class _Stopwatch:
 
 def run(args) -> str:
     args = default_model_configs(args)
+    check_per_node_args(args)
     check_decode_args(args)
     print(args)
     Path("filtered_edges").mkdir(exist_ok=True)
@@ -402,7 +432,13 @@ def run(args) -> str:
     _lib.warm_up_join()                  # (the background loads are done -- or given up on -- before anything is timed)
     watch = _Stopwatch(device)
     keep = int(args.keep_top)
-    if keep == 0 and args.model == "simple" and world == 1 and candidates.dense_cn_suits(data.adj_t):
+    # --keep_per_node: the threshold scan, the dense product and the half lists all cut (or mirror) GLOBALLY, so the run takes
+    # the block route with every candidate scored, cuts each column of each block there, and --keep_top is applied to the
+    # ordered result at the end (in a sharded run the counts printed are this rank's)
+    per_node = int(getattr(args, "keep_per_node", 0) or 0)
+    if per_node:
+        keep_rows, keep = keep, 0
+    if keep == 0 and not per_node and args.model == "simple" and world == 1 and candidates.dense_cn_suits(data.adj_t):
         # configs[0]: a small DENSE graph (ddi: N = 4,267, 11.7 % of all pairs are edges).  Common-neighbour counts = A A^T, ONE
         # product on the matrix cores (exact: counts < 2^24), the reference's candidate list a masked read of it in its own
         # column-major order, and the file's order ONE stable sort by the integer count -- no per-graph table, a dozen launches
@@ -449,7 +485,7 @@ def run(args) -> str:
                      None if best_pairs is None else torch.cat([best_pairs.t().to(torch.float32), best_scores.unsqueeze(1)], 1),
                      sharded=shards)
     full_w = (fused_node_weights(args, data.adj_t, ra_graph)
-              if keep == 0 and data.adj_t.val is None and scan.scan_available(data.adj_t) else None)
+              if keep == 0 and not per_node and data.adj_t.val is None and scan.scan_available(data.adj_t) else None)
     if (full_w is not None and candidates.fused_scores_fit(data.adj_t, full_w)
             and int(scan.half_paths(data.adj_t).sum().item()) < 1 << 29):      # (unordered pairs <= half paths: lists that fit)
         # the whole [E,3] file of a heuristic filter on a unit-valued symmetric graph: scores are symmetric too, so the list
@@ -479,7 +515,7 @@ def run(args) -> str:
             rows = torch.stack([(rows_k & 0xFFFFFFFF).to(torch.float32), (rows_k >> 32).to(torch.float32), rows_v], 1)
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
     from .models import DEA_GNN_JK, LinkGNN
-    if (GNN_HALF and 0 <= keep <= scan.MAX_K and isinstance(model, (LinkGNN, DEA_GNN_JK)) and data.adj_t.device.type == "cuda"
+    if (GNN_HALF and not per_node and 0 <= keep <= scan.MAX_K and isinstance(model, (LinkGNN, DEA_GNN_JK)) and data.adj_t.device.type == "cuda"
             and data.adj_t.n_rows == data.adj_t.n_cols and data.adj_t.nnz() < 1 << 30 and scan.is_symmetric(data.adj_t)
             and (keep > 0 or int(scan.half_paths(data.adj_t).sum().item()) < 1 << 29)):     # (the whole file: lists that fit)
         with torch.no_grad():
@@ -497,7 +533,7 @@ def run(args) -> str:
         raise ValueError("--decode_precision bf16: this graph does not take the half-list route of the GNN filters (it needs a "
                          "symmetric adjacency on the device); run it in fp32")
     col_lo, col_hi = rank_column_range(data.adj_t, rank, world)
-    n_seen = 0
+    n_seen, sel_s = 0, 0.0
     all_pairs, all_scores = [], []
     top = proposals.StreamingTopK(keep) if keep else None
     if world > 1 and hasattr(model, "embeddings"):
@@ -512,6 +548,14 @@ def run(args) -> str:
                 continue
             if keep:
                 top.push(pairs, score)          # blocks arrive in candidate (column-major) order
+            elif per_node:                      # every column of the block cut to its k best (csrc/segment_topk.hip)
+                torch.cuda.synchronize(device)
+                t0 = time.perf_counter()
+                pos = per_node_positions(pairs, score, v_lo, v_hi, per_node)
+                all_pairs.append(pairs[:, pos].long() if isinstance(pairs, torch.Tensor) else pairs.select(pos))
+                all_scores.append(score[pos])
+                torch.cuda.synchronize(device)
+                sel_s += time.perf_counter() - t0
             elif not isinstance(pairs, torch.Tensor):     # candidates.ColumnBlock, possibly padded
                 idx = pairs.valid()
                 all_pairs.append(pairs.select(idx))
@@ -521,6 +565,9 @@ def run(args) -> str:
                 all_scores.append(score)
             n_seen += n_blk
     dt = watch.stop(n_seen)
+    if per_node:
+        print(f'per-node cut: k = {per_node}, {sum(int(x.numel()) for x in all_scores)} rows kept of {n_seen} candidates seen; '
+              f'selected in {sel_s:.2f} s')
     print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
 
     if keep:
@@ -552,6 +599,8 @@ def run(args) -> str:
                                  scan._gather_varlen(pairs[1].contiguous(), world)])
             scores = scan._gather_varlen(scores, world)
         sorted_edges = proposals.sorted_edges_tensor(pairs, scores)          # filter.py:160-161
+        if per_node and keep_rows:
+            sorted_edges = sorted_edges[:keep_rows]      # --keep_top on top of the per-node cut: the first K rows of that file
     return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, sorted_edges)
 
 

@@ -1284,6 +1284,43 @@ def kth_largest(x: torch.Tensor, k: int) -> torch.Tensor:
     return out
 
 
+SEGMENT_TOPK_WAVE_MAX = 256    # csrc/segment_topk.hip SEG_WAVE_MAX: segments up to this long are one wave's work (keys in registers)
+SEGMENT_TOPK_LDS_MAX = 8192    # ... SEG_LDS_MAX: up to this long one workgroup's with the keys in LDS; longer ones are streamed
+                               # (eps_segment_topk_class_max(0 / 1) answers the same: tests/test_per_node_host.py holds the two together)
+
+
+def segment_topk(colptr: torch.Tensor, score: torch.Tensor, k: int, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Positions (int64, into ``score``) of the ``k`` best entries of every segment of ``score`` -- segment s is
+    [colptr[s], colptr[s + 1]), or [colptr[s], colptr[s] + counts[s]) in the padded layout of a ``ColumnBlock`` -- in the
+    declared order: score descending (``ordered_bits``), then position ascending.  A segment with at most ``k`` entries keeps
+    all of them.  The positions are ascending within each segment and the segments follow each other, so the result as a
+    whole is ascending: candidate order (eps_segment_topk; one host read, the size of the result)."""
+    dev = _need_gpu(colptr, score, counts)
+    _chk(_I64, colptr=colptr, counts=counts); _chk(_F32, score=score)
+    k = int(k)
+    if colptr.dim() != 1 or colptr.numel() < 1 or score.dim() != 1:
+        raise _lib.EpsError(f"segment_topk: colptr [n_seg + 1] and score [E] are vectors (got {tuple(colptr.shape)}, {tuple(score.shape)})")
+    n_seg = colptr.numel() - 1
+    if counts is not None and counts.shape != (n_seg,):
+        raise _lib.EpsError(f"segment_topk: counts holds {tuple(counts.shape)} entries for {n_seg} segments")
+    if k < 1:                      # (the library refuses it too; no tensor work for a call that cannot run)
+        raise _lib.EpsError(f"segment_topk: k={k} must lie in [1, 2^31)")
+    lens = (colptr[1:] - colptr[:-1]) if counts is None else counts
+    outptr = torch.zeros(n_seg + 1, dtype=_I64, device=dev)
+    torch.cumsum(torch.clamp(lens, min=0, max=k), 0, out=outptr[1:])
+    order = torch.argsort(lens, descending=True, stable=True).to(_I32)       # heaviest first, like candidates.heaviest_first
+    if n_seg:
+        # (one host read: the result's size, and that every segment lies inside the score array)
+        total, lo, hi = torch.stack([outptr[-1], colptr[:-1].min(), (colptr[:-1] + torch.clamp(lens, min=0)).max()]).tolist()
+        if lo < 0 or hi > score.numel():
+            raise _lib.EpsError(f"segment_topk: segments span [{lo}, {hi}) of a score array of {score.numel()} entries")
+    else:
+        total = 0
+    out = torch.empty(total, dtype=_I64, device=dev)
+    _call("eps_segment_topk", dev, colptr, counts, score, n_seg, k, outptr, order, out)
+    return out
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

@@ -787,6 +787,26 @@ int eps_csr_merge_fill(const int64_t *rowptr, const int32_t *col, const float *v
                        int64_t m, const int32_t *xrank, const int64_t *new_rowptr, int64_t new_nnz, int32_t *new_col,
                        float *new_val_or_null, void *stream);
 
+/* ---- Segmented top-k: the k best entries of every segment of a score array (csrc/segment_topk.hip) ----------------------
+ * filter.py --keep_per_node k: a block's candidates are column-major (column v, u ascending, one score each), so "node v's k
+ * best proposals" is a top-k per segment.  Segment s is [colptr[s], colptr[s + 1]) of score (colptr int64[n_seg + 1], device),
+ * or, with counts (int64[n_seg]) given, [colptr[s], colptr[s] + counts[s]): the padded upper-bound layout of a count-free
+ * expansion -- nothing beyond the counted entries is read.  Order: ordered_bits(score) descending (the key of eps_pack_keys:
+ * -0.0 ties +0.0), then position ascending.  outptr (int64[n_seg + 1], device) is the exclusive prefix of min(len_s, k): the
+ * caller's, the kept count of a segment is known before any selection.  out_pos (int64[outptr[n_seg]]) receives POSITIONS
+ * into the arrays, ascending within each segment; a segment of at most k entries keeps all of them.  order_or_null
+ * (int32[n_seg]): the hand-out order of the segments, heaviest first (a permutation of 0 .. n_seg - 1); it decides the load
+ * balance only, every segment is served whatever it holds; NULL = as numbered.
+ * Selection by threshold (radix select of the k-th key on LDS histograms, then everything above it and the FIRST ties), in
+ * ordered chunks: no resource depends on k, no atomics on global memory, the same inputs give the same bits.
+ * eps_segment_topk_class_max(cls): the longest segment of work class cls -- 0: one wave, keys in registers; 1: one workgroup,
+ * keys in LDS; longer segments are streamed once per radix round by one workgroup (-1 for any other cls).
+ * EPS_EINVAL before any pointer is touched: k outside [1, 2^31) (the message names k=), n_seg outside [0, 2^31) (n_seg=), a
+ * null colptr with n_seg > 0.  n_seg == 0 launches nothing.  Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int64_t eps_segment_topk_class_max(int32_t cls);
+int eps_segment_topk(const int64_t *colptr, const int64_t *counts_or_null, const float *score, int64_t n_seg, int64_t k,
+                     const int64_t *outptr, const int32_t *order_or_null, int64_t *out_pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
