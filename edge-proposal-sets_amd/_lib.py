@@ -86,6 +86,11 @@ SIGNATURES = {
     "eps_mlp_decode_backward_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "eps_mlp_decode_backward": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _i32, _vp,
                                        _c.c_float, _int, _vp, _vp, _vp, _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i64, _vp]),
+    "eps_mlp_decode_bn_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "eps_mlp_decode_bn_stats": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _i32, _vp, _vp, _vp, _i64, _vp]),
+    "eps_mlp_decode_bn_backward": (_int, [_vp, _i64, _i32, _vp, _vp, _i64, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _i32,
+                                          _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _vp, _c.c_float, _vp, _c.c_float, _vp, _vp, _vp,
+                                          _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _vp, _vp, _i64, _vp]),
     "eps_kth_largest_workspace_bytes": (_i64, []),
     "eps_kth_largest_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "eps_select_topk_rows_relabelled": (_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

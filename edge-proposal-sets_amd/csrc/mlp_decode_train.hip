@@ -252,6 +252,8 @@ __device__ __forceinline__ void t_colsum(const float (*Xs)[T_XLD], float *Gs, in
 // Workspace of the backward (floats, Bp = n_pairs rounded up to the tile):
 //   A  [(L-1)][Bp][H]  the input tile of every hidden layer          dZ [(L-1)][Bp][H]  dL/d(pre-activation)
 //   dx0 [Bp][H]        part [T_MAX_WG][T_GROW]                       dwp [T_DW_MAXS][H][H]
+// DX0 = false (the BatchNorm route below): the chain stops at dZ_0 -- no dA_0 product, dx0 stays unwritten.
+template <bool DX0>
 __global__ __launch_bounds__(T_THREADS, 2) void mlp_decode_bwd_kernel(const float *__restrict__ hmat, int32_t H,
                                                                       const int32_t *__restrict__ pu,
                                                                       const int32_t *__restrict__ pv, int64_t n_pairs,
@@ -346,6 +348,10 @@ __global__ __launch_bounds__(T_THREADS, 2) void mlp_decode_bwd_kernel(const floa
         for (int l = L - 2; l >= 0; --l) {
             t_spill(Xs, dZs + l * Bp * H, H, e0, w, lane);
             t_colsum(Xs, Gs[l], H, tid);         // grad_b[l]
+            if (!DX0 && l == 0) {
+                __syncthreads();                 // (the next tile's gather rewrites X)
+                break;
+            }
             if (l > 0) t_stage_keep(Ks, keep ? keep + (int64_t)(l - 1) * lstride : nullptr, nw, e0, n_pairs, tid);
             f32x16 acc[2];
             t_matmul(acc, Xs, tpick(prm.wt, l), H, w, has0, r, hh);   // dA_l[row][i] = sum_o dZ_l[row][o] W_l[o][i]
@@ -593,7 +599,7 @@ extern "C" int eps_mlp_decode_backward(const float *h, int64_t n_nodes, int32_t 
     int64_t blocks = eps_num_cus();          // 89 KiB of LDS: one workgroup per CU
     if (blocks > T_MAX_WG) blocks = T_MAX_WG;
     if (blocks > n_tiles) blocks = n_tiles;
-    hipLaunchKernelGGL(mlp_decode_bwd_kernel, dim3((unsigned)blocks), dim3(T_THREADS), 0, st, h, hdim, u, v, n_pairs, prm, n_layers,
+    hipLaunchKernelGGL((mlp_decode_bwd_kernel<true>), dim3((unsigned)blocks), dim3(T_THREADS), 0, st, h, hdim, u, v, n_pairs, prm, n_layers,
                        keep, keep_scale, apply_sigmoid, grad_out, As, dZs, dx0, part);
     EPS_CHECK_LAUNCH("eps_mlp_decode_backward");
 
@@ -622,6 +628,383 @@ extern "C" int eps_mlp_decode_backward(const float *h, int64_t n_nodes, int32_t 
                            n_pairs, inc_order, inc_ptr, dx0, grad_h);
     }
     EPS_CHECK_LAUNCH("eps_mlp_decode_backward");
+    return EPS_OK;
+}
+
+// ---- a two-layer decoder with BatchNorm1d on BATCH statistics between Linear(H, H) and the ReLU (DEA_GNN_JK) -------------------
+//   z = x0 W0^T + b0,  mu / var over the batch,  sigma = sqrt(var + eps),  y = gamma (z - mu) / sigma + beta,  a = relu(y) keep scale
+// With (mu, var) known the BatchNorm is a per-channel affine map: the forward is eps_mlp_decode_train on W' = diag(s) W0,
+// b' = s b0 + beta - s mu (s = gamma / sigma), folded by the caller.
+//   mlp_decode_bn_stats_kernel   per tile: gather, z = X W0^T + b0 on the decode's MFMA loop, then per column the tile's
+//                                (count, mean, M2) in float64, merged (Chan) into the workgroup's running triple; one row of
+//                                partials per workgroup.  mlp_decode_bn_merge_kernel merges the rows in workgroup order.
+//   the backward                 mlp_decode_bwd_kernel<false> on (W', b') spills x0 and dy = dL/dy and sums g' = sum dy (= grad
+//                                beta), grad w1, grad b1.
+//   mlp_decode_bn_dgamma_kernel  per tile: x0 from its spill, zhat = (x0 W0^T + b0 - mu) / sigma, grad gamma = sum_e dy zhat:
+//                                per-workgroup partials in float64, summed in workgroup order.
+//   mlp_decode_bn_dz_kernel      per tile: zhat again, then
+//                                dz = s (dy - g' / B - zhat grad_gamma / B) over the dy spill, and dx0 = dz W0.
+//                                grad W0 = dz^T x0 is mlp_decode_dw_kernel once more; grad b0 is exactly 0.
+// No atomics; every order is a function of the shapes and the CU count.
+#define T_SROW (2 * T_HMAX + 8)   // doubles per row of the statistics partials: mean[c], M2[T_HMAX + c], the row count at 2 * T_HMAX
+
+__device__ __forceinline__ void t_chan(double &cnt, double &mean, double &m2, double nt, double mt, double qt)
+{
+    const double tot = cnt + nt, delta = mt - mean;
+    mean += delta * (nt / tot);
+    m2 += qt + delta * delta * (cnt * nt / tot);
+    cnt = tot;
+}
+
+__global__ __launch_bounds__(T_THREADS, 4) void mlp_decode_bn_stats_kernel(const float *__restrict__ hmat, int32_t H,
+                                                                           const int32_t *__restrict__ pu,
+                                                                           const int32_t *__restrict__ pv, int64_t n_pairs,
+                                                                           const float *__restrict__ W0, const float *__restrict__ b0,
+                                                                           double *__restrict__ part)
+{
+    __shared__ __attribute__((aligned(16))) float Xs[T_BM][T_XLD];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int nw = (H + 31) >> 5;
+    const bool has0 = w < nw;
+    const int64_t n_tiles = (n_pairs + T_BM - 1) / T_BM;
+    const int cc = w * 32 + r;
+    const float bv = (has0 && cc < H) ? b0[cc] : 0.f;
+    double cnt = 0.0, mean = 0.0, m2 = 0.0;      // of column tid over this workgroup's tiles so far
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t e0 = tile * T_BM;
+        t_gather(Xs, hmat, H, pu, pv, n_pairs, e0, w, lane);
+        __syncthreads();
+        f32x16 acc[2];
+        t_matmul(acc, Xs, W0, H, w, has0, r, hh);
+        __syncthreads();  // every wave has finished reading X
+        if (has0) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) Xs[mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh][cc] = acc[mi][e] + bv;
+        }
+        __syncthreads();
+        if (tid < H) {
+            const int nt = n_pairs - e0 < T_BM ? (int)(n_pairs - e0) : T_BM;
+            double s = 0.0;
+            for (int row = 0; row < nt; ++row) s += (double)Xs[row][tid];
+            const double mt = s / nt;
+            double q = 0.0;
+            for (int row = 0; row < nt; ++row) {
+                const double d = (double)Xs[row][tid] - mt;
+                q += d * d;
+            }
+            t_chan(cnt, mean, m2, (double)nt, mt, q);
+        }
+        __syncthreads();
+    }
+    double *row = part + (int64_t)blockIdx.x * T_SROW;
+    if (tid < H) {
+        row[tid] = mean;
+        row[T_HMAX + tid] = m2;
+    }
+    if (tid == 0) row[2 * T_HMAX] = cnt;
+}
+
+// the workgroups' triples, merged in workgroup order: mean[c], var[c] = M2 / B (the biased variance)
+__global__ __launch_bounds__(T_HMAX) void mlp_decode_bn_merge_kernel(const double *__restrict__ part, int32_t S, int32_t H,
+                                                                     float *__restrict__ mean_out, float *__restrict__ var_out)
+{
+    const int c = threadIdx.x;
+    if (c >= H) return;
+    double cnt = 0.0, mean = 0.0, m2 = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double *row = part + (int64_t)s * T_SROW;
+        t_chan(cnt, mean, m2, row[2 * T_HMAX], row[c], row[T_HMAX + c]);
+    }
+    mean_out[c] = (float)mean;
+    var_out[c] = (float)(m2 / cnt);
+}
+
+// X tile <- rows e0.. of a [Bp, H] spill (the inverse of t_spill; the tile's 64 rows exist there); pad columns are zero
+__device__ __forceinline__ void t_unspill(float (*Xs)[T_XLD], const float *__restrict__ src, int H, int64_t e0, int w, int lane)
+{
+    const int h4 = H >> 2, hp4 = ((H + 31) & ~31) >> 2;
+    const float *__restrict__ base = src + e0 * H;       // (32-bit offsets inside the tile)
+    if (lane < hp4) {
+        v4f x[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = *reinterpret_cast<const v4f *>(base + (w * 8 + i) * H + 4 * (lane < h4 ? lane : 0));
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            *reinterpret_cast<v4f *>(&Xs[w * 8 + i][4 * lane]) = lane < h4 ? x[i] : (v4f){0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// grad_gamma partials: per tile x0 from its spill, zhat = (x0 W0^T + b0 - mu) / sigma on the MFMA loop, then per column
+// sum_rows dy zhat in float64 (lane (r, hh) holds column cc of 32 rows; the two halves meet in one exchange).  One row of
+// partials per workgroup.
+__global__ __launch_bounds__(T_THREADS, 4) void mlp_decode_bn_dgamma_kernel(int32_t H, int64_t n_pairs, const float *__restrict__ W0,
+                                                                            const float *__restrict__ b0,
+                                                                            const float *__restrict__ mean,
+                                                                            const float *__restrict__ var, float eps,
+                                                                            const float *__restrict__ A, const float *__restrict__ dZ,
+                                                                            double *__restrict__ part)
+{
+    __shared__ __attribute__((aligned(16))) float Xs[T_BM][T_XLD];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int nw = (H + 31) >> 5;
+    const bool has0 = w < nw;
+    const int64_t n_tiles = (n_pairs + T_BM - 1) / T_BM;
+    const int cc = w * 32 + r;
+    const bool okc = has0 && cc < H;
+    const int loff = (4 * hh * H + cc) * 4;  // byte offset of (row 4 hh, column cc) in a tile; the rest of a row offset is wave-uniform
+    double sum = 0.0;
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t e0 = tile * T_BM;
+        t_unspill(Xs, A, H, e0, w, lane);
+        __syncthreads();
+        f32x16 acc[2];
+        t_matmul(acc, Xs, W0, H, w, has0, r, hh);
+        const int nv = n_pairs - e0 < T_BM ? (int)(n_pairs - e0) : T_BM;      // rows of the tile that are edges
+        const double bm = okc ? (double)b0[cc] - (double)mean[cc] : 0.0;
+        const double isig = okc ? 1.0 / sqrt((double)var[cc] + (double)eps) : 0.0;
+        const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc((void *)(dZ + e0 * H), 0, T_BM * H * 4, 0x00020000);
+        if (has0) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int rr = mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                    const float dy = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dyr, loff, (mi * 32 + (e & 3) + 8 * (e >> 2)) * H * 4, 0));
+                    const float z = acc[mi][e];
+                    // (rows past the batch: dy is 0 in the spill; other columns: isig is 0.  The factor keeps the chain free of
+                    // branches -- as a select it compiles to 32 of them, each with its load inside)
+                    sum += (double)dy * (((double)z + bm) * isig) * (rr < nv ? 1.0 : 0.0);
+                }
+        }
+        __syncthreads();  // every wave has finished reading X
+    }
+    sum += __shfl_xor(sum, 32);              // (a + b on one half, b + a on the other: the same bits)
+    if (okc && hh == 0) part[(int64_t)blockIdx.x * T_HMAX + cc] = sum;
+}
+
+// grad_gamma[c] = the workgroups' partials in workgroup order; `out` also gets it (float32) when non-null
+__global__ __launch_bounds__(T_HMAX) void mlp_decode_bn_dgamma_sum_kernel(const double *__restrict__ part, int32_t S, int32_t H,
+                                                                          double *__restrict__ dgamma, float *__restrict__ out)
+{
+    const int c = threadIdx.x;
+    if (c >= H) return;
+    double s = 0.0;
+    for (int i = 0; i < S; ++i) s += part[(int64_t)i * T_HMAX + c];
+    dgamma[c] = s;                           // (the dz pass subtracts in float64: at small B its terms cancel almost wholly)
+    if (out) out[c] = (float)s;
+}
+
+__global__ __launch_bounds__(T_THREADS, 2) void mlp_decode_bn_dz_kernel(int32_t H, int64_t n_pairs, const float *__restrict__ W0,
+                                                                        const float *__restrict__ W0t, const float *__restrict__ b0,
+                                                                        const float *__restrict__ gamma,
+                                                                        const float *__restrict__ mean, const float *__restrict__ var,
+                                                                        float eps, const float *__restrict__ gsum,
+                                                                        const double *__restrict__ dgamma, const float *__restrict__ A,
+                                                                        float *__restrict__ dZ, float *__restrict__ dx0)
+{
+    __shared__ __attribute__((aligned(16))) float Xs[T_BM][T_XLD];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int nw = (H + 31) >> 5;
+    const bool has0 = w < nw;
+    const int64_t n_tiles = (n_pairs + T_BM - 1) / T_BM;
+    const int cc = w * 32 + r;
+    const bool okc = has0 && cc < H;
+    const int loff = (4 * hh * H + cc) * 4;  // byte offset of (row 4 hh, column cc) in a tile; the rest of a row offset is wave-uniform
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t e0 = tile * T_BM;
+        t_unspill(Xs, A, H, e0, w, lane);
+        __syncthreads();
+        f32x16 acc[2];
+        t_matmul(acc, Xs, W0, H, w, has0, r, hh);
+        const int nv = n_pairs - e0 < T_BM ? (int)(n_pairs - e0) : T_BM;      // rows of the tile that are edges
+        // this lane's column, in float64 and formed as the grad_gamma pass forms them: at small B dz is what a near-total
+        // cancellation leaves, and zhat has to be the zhat that grad_gamma summed
+        double sc = 0.0, isig = 0.0, bm = 0.0, gB = 0.0, dgB = 0.0;
+        if (okc) {
+            isig = 1.0 / sqrt((double)var[cc] + (double)eps);
+            sc = (double)gamma[cc] * isig;
+            bm = (double)b0[cc] - (double)mean[cc];
+            gB = (double)gsum[cc] / (double)n_pairs;
+            dgB = dgamma[cc] / (double)n_pairs;
+        }
+        // (the tile's rows of dy / dx0 through buffer descriptors: one 32-bit offset per element, not a 64-bit address)
+        const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc((void *)(dZ + e0 * H), 0, T_BM * H * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t dxr = __builtin_amdgcn_make_buffer_rsrc((void *)(dx0 + e0 * H), 0, T_BM * H * 4, 0x00020000);
+        if (has0) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int rr = mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                    // (no branch: a pad column's offset stays inside the tile or past its end, where the load gives 0)
+                    const float dy = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dyr, loff, (mi * 32 + (e & 3) + 8 * (e >> 2)) * H * 4, 0));
+                    const float z = acc[mi][e];
+                    // (other columns: sc is 0.  A factor, not a select: see the grad_gamma pass)
+                    acc[mi][e] = (float)(sc * ((double)dy - gB - (((double)z + bm) * isig) * dgB)) * (rr < nv ? 1.0f : 0.0f);
+                }
+        }
+        __syncthreads();  // every wave has finished reading X
+        if (has0) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) Xs[mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh][cc] = acc[mi][e];
+        }
+        __syncthreads();
+        t_spill(Xs, dZ, H, e0, w, lane);     // dz over dy: this workgroup alone reads and writes the tile's rows
+        t_matmul(acc, Xs, W0t, H, w, has0, r, hh);   // dx0[row][i] = sum_o dz[row][o] W0[o][i]
+        if (okc) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float o = acc[mi][e];          // (a copy: the bit cast wants an object, not a vector element)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), dxr, loff, (mi * 32 + (e & 3) + 8 * (e >> 2)) * H * 4, 0);
+                }
+        }
+        __syncthreads();
+    }
+}
+
+#define T_BN_DOMAIN(name)                                                                                                        \
+    EPS_REQUIRE(n_nodes >= 0, name ": negative size");                                                                            \
+    EPS_REQUIRE(hdim >= T_HMIN && hdim % 4 == 0 && hdim <= T_HMAX, name ": hdim=%d unsupported (need %%4==0, %d..%d)", hdim,      \
+                T_HMIN, T_HMAX);                                                                                                  \
+    EPS_REQUIRE(n_layers == 2, name ": n_layers=%d unsupported (Linear, BatchNorm, ReLU, Linear: exactly 2)", n_layers);          \
+    EPS_REQUIRE(n_pairs >= 2 && n_pairs < ((int64_t)1 << 30), name ": n_pairs=%lld unsupported (batch statistics need 2 .. 2^30 - 1 pairs)", \
+                (long long)n_pairs)
+
+static int64_t t_bn_backward_floats(int64_t n_pairs, int32_t hdim)
+{
+    return eps_mlp_decode_backward_workspace_bytes(n_pairs, hdim, 2) / 4 + 3 * T_HMAX;
+}
+
+extern "C" int64_t eps_mlp_decode_bn_workspace_bytes(int64_t n_pairs, int32_t hdim, int32_t n_layers)
+{
+    if (n_pairs < 2 || hdim < T_HMIN || hdim > T_HMAX || n_layers != 2) return 0;
+    const int64_t stats = (int64_t)T_MAX_WG * T_SROW * 8, bwd = t_bn_backward_floats(n_pairs, hdim) * 4;
+    return stats > bwd ? stats : bwd;
+}
+
+extern "C" int eps_mlp_decode_bn_stats(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u, const int32_t *v,
+                                       int64_t n_pairs, const float *const *w, const float *const *b, int32_t n_layers, float *mean,
+                                       float *var, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    T_BN_DOMAIN("eps_mlp_decode_bn_stats");
+    EPS_REQUIRE(h && u && v && w && b && mean && var && workspace, "eps_mlp_decode_bn_stats: null pointer");
+    EPS_REQUIRE(w[0] && b[0], "eps_mlp_decode_bn_stats: null weight/bias pointer at layer 0");
+    EPS_REQUIRE(n_nodes > 0, "eps_mlp_decode_bn_stats: pairs over an empty node set");
+    EPS_REQUIRE((uintptr_t)h % 16 == 0 && (uintptr_t)w[0] % 16 == 0 && (uintptr_t)workspace % 16 == 0,
+                "eps_mlp_decode_bn_stats: h, the weight and the workspace must be 16-byte aligned");
+    EPS_REQUIRE(workspace_bytes >= (int64_t)T_MAX_WG * T_SROW * 8, "eps_mlp_decode_bn_stats: workspace of %lld bytes, need %lld",
+                (long long)workspace_bytes, (long long)T_MAX_WG * T_SROW * 8);
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t n_tiles = t_tiles(n_pairs);
+    int64_t blocks = (int64_t)eps_num_cus() * 2;
+    if (blocks > T_MAX_WG) blocks = T_MAX_WG;
+    if (blocks > n_tiles) blocks = n_tiles;
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(mlp_decode_bn_stats_kernel, dim3((unsigned)blocks), dim3(T_THREADS), 0, st, h, hdim, u, v, n_pairs, w[0], b[0],
+                       part);
+    hipLaunchKernelGGL(mlp_decode_bn_merge_kernel, dim3(1), dim3(T_HMAX), 0, st, part, (int32_t)blocks, hdim, mean, var);
+    EPS_CHECK_LAUNCH("eps_mlp_decode_bn_stats");
+    return EPS_OK;
+}
+
+extern "C" int eps_mlp_decode_bn_backward(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u, const int32_t *v,
+                                          int64_t n_pairs, const float *const *w, const float *const *wt, const float *const *b,
+                                          int32_t n_layers, const float *const *wf, const float *const *bf, const float *gamma,
+                                          const float *mean, const float *var, float bn_eps, const uint32_t *keep, float keep_scale,
+                                          const float *grad_out, const int32_t *inc_order, const int64_t *inc_ptr,
+                                          float *const *grad_w, float *const *grad_b, float *grad_gamma, float *grad_beta,
+                                          float *grad_h, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    T_BN_DOMAIN("eps_mlp_decode_bn_backward");
+    const hipStream_t st = (hipStream_t)stream;
+    const int H = hdim, L = 2;
+    EPS_REQUIRE(h && u && v && w && wt && b && wf && bf && gamma && mean && var && grad_out && workspace,
+                "eps_mlp_decode_bn_backward: null pointer");
+    EPS_REQUIRE(n_nodes > 0, "eps_mlp_decode_bn_backward: pairs over an empty node set");
+    EPS_REQUIRE((uintptr_t)h % 16 == 0 && (uintptr_t)workspace % 16 == 0, "eps_mlp_decode_bn_backward: h and workspace must be 16-byte aligned");
+    EPS_REQUIRE(workspace_bytes >= t_bn_backward_floats(n_pairs, hdim) * 4, "eps_mlp_decode_bn_backward: workspace of %lld bytes, need %lld",
+                (long long)workspace_bytes, (long long)t_bn_backward_floats(n_pairs, hdim) * 4);
+    EPS_REQUIRE(!grad_h || (inc_order && inc_ptr && (uintptr_t)grad_h % 16 == 0),
+                "eps_mlp_decode_bn_backward: grad_h needs the sorted incidence list (inc_order, inc_ptr) and 16-byte alignment");
+    EPS_REQUIRE(bn_eps > 0.f, "eps_mlp_decode_bn_backward: eps=%g must be positive", (double)bn_eps);
+    TrainParams raw, prm;      // the layers as they are (W0 and its transpose for the dz pass); folded, for the pass that yields dy
+    if (int rc = t_params(raw, w, wt, b, n_layers, "eps_mlp_decode_bn_backward")) return rc;
+    const float *const wfold[2] = {wf[0], w[1]}, *const bfold[2] = {bf[0], b[1]};
+    if (int rc = t_params(prm, wfold, nullptr, bfold, n_layers, "eps_mlp_decode_bn_backward")) return rc;
+    if (!keep) keep_scale = 1.0f;
+
+    const int64_t n_tiles = t_tiles(n_pairs), bp = n_tiles * T_BM;
+    float *As = (float *)workspace;
+    float *dZs = As + bp * H;
+    float *dx0 = dZs + bp * H;
+    float *part = dx0 + bp * H;
+    float *dwp = part + (int64_t)T_MAX_WG * T_GROW;
+    float *gsum = dwp + (int64_t)T_DW_MAXS * H * H;
+    double *dgam = (double *)(gsum + T_HMAX);
+
+    int64_t blocks = eps_num_cus();
+    if (blocks > T_MAX_WG) blocks = T_MAX_WG;
+    if (blocks > n_tiles) blocks = n_tiles;
+    hipLaunchKernelGGL((mlp_decode_bwd_kernel<false>), dim3((unsigned)blocks), dim3(T_THREADS), 0, st, h, hdim, u, v, n_pairs, prm,
+                       n_layers, keep, keep_scale, 0, grad_out, As, dZs, dx0, part);
+    EPS_CHECK_LAUNCH("eps_mlp_decode_bn_backward");
+
+    auto sum_rows = [&](const float *src, int64_t stride, int S, int64_t n, float *dst) {
+        hipLaunchKernelGGL(mlp_decode_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, stride, (int32_t)S, n, dst);
+    };
+    int64_t chunk = 0;
+    const int S = t_dw_chunks(n_tiles, &chunk);
+    const int nt = (H + 127) / 128;
+    auto dw = [&](float *dst) {           // dst = dZs^T As
+        hipLaunchKernelGGL(mlp_decode_dw_kernel, dim3((unsigned)(nt * nt), (unsigned)S), dim3(256), 0, st, dZs, As, hdim, bp, chunk, dwp);
+        sum_rows(dwp, (int64_t)H * H, S, (int64_t)H * H, dst);
+    };
+    sum_rows(part, T_GROW, (int)blocks, H, gsum);                                  // g' = sum dy
+    if (grad_beta) sum_rows(part, T_GROW, (int)blocks, H, grad_beta);
+    if (grad_w && grad_w[1]) sum_rows(part + (L - 1) * T_HMAX, T_GROW, (int)blocks, H, grad_w[1]);
+    if (grad_b && grad_b[1]) sum_rows(part + T_MAXL * T_HMAX, T_GROW, (int)blocks, 1, grad_b[1]);
+    int64_t blocks2 = (int64_t)eps_num_cus() * 2;
+    if (blocks2 > T_MAX_WG) blocks2 = T_MAX_WG;
+    if (blocks2 > n_tiles) blocks2 = n_tiles;
+    double *dgp = (double *)dwp;             // [blocks2][T_HMAX] partials of grad gamma (the dW partials' room: 256 H^2 floats, free here)
+    hipLaunchKernelGGL(mlp_decode_bn_dgamma_kernel, dim3((unsigned)blocks2), dim3(T_THREADS), 0, st, hdim, n_pairs, raw.w[0], raw.b[0],
+                       mean, var, bn_eps, As, dZs, dgp);
+    hipLaunchKernelGGL(mlp_decode_bn_dgamma_sum_kernel, dim3(1), dim3(T_HMAX), 0, st, dgp, (int32_t)blocks2, hdim, dgam, grad_gamma);
+    // (193 registers per lane: one workgroup per CU, like the dy pass)
+    hipLaunchKernelGGL(mlp_decode_bn_dz_kernel, dim3((unsigned)blocks), dim3(T_THREADS), 0, st, hdim, n_pairs, raw.w[0], raw.wt[0],
+                       raw.b[0], gamma, mean, var, bn_eps, gsum, dgam, As, dZs, dx0);
+    EPS_CHECK_LAUNCH("eps_mlp_decode_bn_backward");
+    if (grad_w && grad_w[0]) dw(grad_w[0]);                                        // grad W0 = dz^T x0
+    if (grad_b && grad_b[0]) {                                                     // a bias in front of batch statistics: exactly 0
+        const hipError_t e = hipMemsetAsync(grad_b[0], 0, (size_t)H * 4, st);
+        EPS_REQUIRE(e == hipSuccess, "eps_mlp_decode_bn_backward: %s", hipGetErrorString(e));
+    }
+    if (grad_h) {
+        hipLaunchKernelGGL(mlp_decode_gradh_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, st, h, hdim, n_nodes, u, v,
+                           n_pairs, inc_order, inc_ptr, dx0, grad_h);
+    }
+    EPS_CHECK_LAUNCH("eps_mlp_decode_bn_backward");
     return EPS_OK;
 }
 

@@ -276,6 +276,40 @@ class _FusedDecode(torch.autograd.Function):
         return (gh, None, None, None, *(gw or [None] * L), *(gb or [None] * L))
 
 
+def fold_batch_statistics(weight, bias, gamma, beta, mean, var, eps: float):
+    """(W', b') such that x W'^T + b' == gamma (x W^T + b - mean) / sqrt(var + eps) + beta: ``fold_batchnorm`` on the statistics of
+    the batch at hand.  Formed in float64, returned in W's dtype; parameter-sized."""
+    f = torch.float64
+    s = gamma.to(f) / torch.sqrt(var.to(f) + eps)
+    return ((weight.to(f) * s[:, None]).to(weight.dtype).contiguous(),
+            (s * (bias.to(f) - mean.to(f)) + beta.to(f)).to(bias.dtype).contiguous())
+
+
+class _FusedDecodeBN(torch.autograd.Function):
+    """DEA_GNN_JK's two-layer training decode on csrc/mlp_decode_train.hip: ``apply(h, edges, keep, keep_scale, mean, var, eps,
+    W0, b0, gamma, beta, w1, b1)`` -> logits [B].  ``mean`` / ``var``: the batch statistics of the hidden pre-activation
+    (ops.mlp_decode_bn_stats), constants here: the backward carries the statistics' own dependence on h and W0 itself.  The
+    forward folds the BatchNorm into the hidden layer (``fold_batch_statistics``) and is
+    eps_mlp_decode_train on the folded layer; nothing but the inputs and that layer is saved."""
+
+    @staticmethod
+    def forward(ctx, h, edges, keep, keep_scale, mean, var, eps, w0, b0, gamma, beta, w1, b1):
+        h = h.contiguous()
+        w0, b0, gamma, beta, w1, b1 = (t.detach().contiguous() for t in (w0, b0, gamma, beta, w1, b1))
+        wf, bf = fold_batch_statistics(w0, b0, gamma, beta, mean, var, eps)
+        ctx.save_for_backward(h, edges, keep, mean, var, w0, b0, gamma, w1, b1, wf, bf)
+        ctx.keep_scale, ctx.eps = keep_scale, eps
+        return ops.mlp_decode_train(h, edges[0], edges[1], [wf, w1], [bf, b1], keep=keep, keep_scale=keep_scale, apply_sigmoid=False)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, edges, keep, mean, var, w0, b0, gamma, w1, b1, wf, bf = ctx.saved_tensors
+        gh, gw, gb, gg, gbeta = ops.mlp_decode_bn_backward(h, edges[0], edges[1], [w0, w1], [b0, b1], wf, bf, gamma, mean, var, ctx.eps,
+                                                           grad_out.contiguous(), keep=keep, keep_scale=ctx.keep_scale,
+                                                           want_h=ctx.needs_input_grad[0])
+        return (gh, None, None, None, None, None, None, gw[0], gb[0], gg, gbeta, gw[1], gb[1])
+
+
 def _check_precision(precision: str) -> None:
     if precision not in DECODE_PRECISIONS:
         raise ValueError(f"decode precision '{precision}': one of {', '.join(DECODE_PRECISIONS)}")
@@ -541,7 +575,11 @@ class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
 
     Training mode runs on torch autograd with the hops through the HIP SpMM.  Eval mode runs on the HIP kernels: per layer
     the hop buffer (TAGConv.hops) and one GEMM with the BatchNorm folded into its weights and ReLU in its epilogue; the
-    embeddings are cached like LinkGNN's; the decode is eps_mlp_decode (logits) with the decoder's BatchNorms folded in."""
+    embeddings are cached like LinkGNN's; the decode is eps_mlp_decode (logits) with the decoder's BatchNorms folded in.
+
+    ``fused_decode`` (off by default): the training branch decodes through ``decode_train`` (the fused HIP statistics pass,
+    forward and backward, BatchNorm on batch statistics included) instead of the torch ops; the GNN half stays on autograd."""
+    fused_decode = False
 
     def __init__(self, num_nodes, embed_dim, gnn_in_dim, gnn_hidden_dim, gnn_out_dim, gnn_num_layers, mlp_in_dim,
                  mlp_hidden_dim, mlp_out_dim=1, mlp_num_layers=2, dropout=0.5, gnn_batchnorm=False, mlp_batchnorm=False, K=2,
@@ -629,6 +667,38 @@ class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
             bs.append(b.contiguous())
         return ws, bs
 
+    def decode_train(self, h: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+        """The training decode over edges [2,B] on the fused kernels (eps_mlp_decode_bn_stats, eps_mlp_decode_train on the
+        folded layer, eps_mlp_decode_bn_backward) -> logits float32 [B], differentiable in ``h``, the two Linear layers and the
+        BatchNorm's weight and bias.  The BatchNorm's running statistics and ``num_batches_tracked`` are updated in place as
+        torch.nn.BatchNorm1d updates them.  Dropout masks: as ``LinkPredictor.decode_train`` draws them."""
+        hd, L, B = h.shape[1], len(self.lins), edges.shape[1]
+        if (h.dim() != 2 or L != 2 or not self.mlp_batchnorm or hd % 4 != 0 or not ops.TRAIN_MIN_HIDDEN <= hd <= ops.TRAIN_MAX_HIDDEN
+                or tuple(self.lins[0].weight.shape) != (hd, hd) or tuple(self.lins[1].weight.shape) != (1, hd)):
+            raise ValueError(f"fused BatchNorm training decode: width {hd} with layers {[tuple(lin.weight.shape) for lin in self.lins]}"
+                             f"{'' if self.mlp_batchnorm else ' without mlp_batchnorm'} is outside the kernel's domain (Linear(H, H), "
+                             f"BatchNorm, ReLU, Linear(H, 1): exactly two layers, H % 4 == 0, {ops.TRAIN_MIN_HIDDEN} <= H <= "
+                             f"{ops.TRAIN_MAX_HIDDEN}); leave fused_decode off for this model")
+        if B < 2:
+            raise ValueError(f"fused BatchNorm training decode: B={B} edges; batch statistics need at least 2")
+        heuristics.check_node_ids(edges, h.shape[0], "decode edges")   # the kernels gather h[u], h[v] unchecked
+        e = edges.to(device=h.device, dtype=torch.int32).contiguous()
+        bn, (lin0, lin1) = self.mlp_bns[0], self.lins
+        with torch.no_grad():
+            mean, var = ops.mlp_decode_bn_stats(h.detach().contiguous(), e[0], e[1], [lin0.weight.contiguous(), lin1.weight.contiguous()],
+                                                [lin0.bias.contiguous(), lin1.bias.contiguous()])
+            if bn.track_running_stats and bn.running_mean is not None:
+                bn.num_batches_tracked.add_(1)
+                m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+                bn.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+                bn.running_var.mul_(1.0 - m).add_(var, alpha=m * B / (B - 1))
+        keep, scale, p = None, 1.0, float(self.dropout)
+        if p > 0:
+            keep = ops.pack_mask(torch.rand(B, hd, device=h.device) >= p).unsqueeze(0)
+            scale = 1.0 / (1.0 - p) if p < 1 else 0.0
+        return _FusedDecodeBN.apply(h, e, keep, scale, mean, var, float(bn.eps), lin0.weight, lin0.bias, bn.weight, bn.bias,
+                                    lin1.weight, lin1.bias)
+
     def forward(self, x_feature, edge_label_index, adj_t):
         if not self.training:
             return self.decode(self.embeddings(x_feature, adj_t), edge_label_index)
@@ -641,6 +711,8 @@ class DEA_GNN_JK(_CachedEmbeddings, torch.nn.Module):
             out = F.dropout(F.relu(out), p=self.dropout, training=True)
             outs.append(out)
         out = self._jk(outs)
+        if self.fused_decode:
+            return self.decode_train(out, edge_label_index)
         out = out[edge_label_index[0]] * out[edge_label_index[1]]
         for i, lin in enumerate(self.lins[:-1]):
             out = lin(out)

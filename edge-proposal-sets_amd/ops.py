@@ -1232,6 +1232,77 @@ def mlp_decode_backward(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], 
     return gh, gw, gb
 
 
+def _bn_decode_args(who: str, h, u, v, weights, biases):
+    """The shared checks of the BatchNorm decode calls -> (n_nodes, hd, n_pairs).  The domain itself (two layers, the width,
+    at least two pairs) is the library's to refuse: EPS_EINVAL names the value."""
+    _chk(_F32, h=h); _chk(_I32, u=u, v=v)
+    if h.dim() != 2:
+        raise _lib.EpsError(f"{who}: h must be [N, H]")
+    n_nodes, hd = h.shape
+    _decode_layers(who, hd, weights, biases)
+    if v.numel() != u.numel():
+        raise _lib.EpsError(f"{who}: u and v differ in length")
+    return n_nodes, hd, u.numel()
+
+
+def _bn_workspace(n: int, hd: int, L: int, dev):
+    """(tensor that owns it, 16-byte aligned address, bytes) of eps_mlp_decode_bn_workspace_bytes (0 outside the domain)."""
+    ws_bytes = int(_lib.load().eps_mlp_decode_bn_workspace_bytes(n, hd, L))
+    ws = torch.empty((ws_bytes + 7) // 8 + 2, dtype=_I64, device=dev)
+    return ws, ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 16), ws_bytes
+
+
+def mlp_decode_bn_stats(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor]):
+    """The batch statistics of a two-layer BatchNorm decoder's hidden pre-activation z = (h[u] * h[v]) W0^T + b0
+    (eps_mlp_decode_bn_stats) -> (mean, var) float32 [H], var the BIASED variance over the E >= 2 edges.  ``weights`` /
+    ``biases``: the layers as they are, [W0, w1] / [b0, b1].  The same inputs give the same bits."""
+    dev = _need_gpu(h, u, v, *weights, *biases)
+    who = "mlp_decode_bn_stats"
+    n_nodes, hd, n = _bn_decode_args(who, h, u, v, weights, biases)
+    L = len(weights)
+    mean, var = torch.empty(hd, dtype=_F32, device=dev), torch.empty(hd, dtype=_F32, device=dev)
+    ws, ws_ptr, ws_bytes = _bn_workspace(n, hd, L, dev)
+    arr = lambda ts: (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in ts])   # noqa: E731
+    _call("eps_mlp_decode_bn_stats", dev, h, n_nodes, hd, u, v, n, arr(weights), arr(biases), L, mean, var, ws_ptr, ws_bytes)
+    return mean, var
+
+
+def mlp_decode_bn_backward(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],
+                           folded_w: torch.Tensor, folded_b: torch.Tensor, gamma: torch.Tensor, mean: torch.Tensor,
+                           var: torch.Tensor, eps: float, grad_out: torch.Tensor, keep: Optional[torch.Tensor] = None,
+                           keep_scale: float = 1.0, want_h=True):
+    """The gradients of the BatchNorm decode (eps_mlp_decode_bn_backward) given ``grad_out`` = dL/d(logits) float32 [E] ->
+    (grad_h [N, H] | None, [grad_W0, grad_w1], [grad_b0 (exact zeros), grad_b1], grad_gamma, grad_beta).  ``folded_w`` /
+    ``folded_b``: the folded hidden layer the forward ran on (``mlp_decode_train``); ``mean`` / ``var``: ``mlp_decode_bn_stats``.
+    The same inputs give the same bits; grad_h sums each node's incidences in the order of a stable sort of cat(u, v)."""
+    dev = _need_gpu(h, u, v, keep, grad_out, folded_w, folded_b, gamma, mean, var, *weights, *biases)
+    who = "mlp_decode_bn_backward"
+    n_nodes, hd, n = _bn_decode_args(who, h, u, v, weights, biases)
+    L = len(weights)
+    _chk(_F32, grad_out=grad_out, folded_w=folded_w, folded_b=folded_b, gamma=gamma, mean=mean, var=var)
+    if grad_out.numel() != n:
+        raise _lib.EpsError(f"{who}: u, v and grad_out differ in length")
+    if tuple(folded_w.shape) != (hd, hd) or any(t.numel() != hd for t in (folded_b, gamma, mean, var)):
+        raise _lib.EpsError(f"{who}: the folded layer must be [{hd}, {hd}] / [{hd}], gamma, mean and var [{hd}]")
+    _chk_keep(who, keep, L, n, hd)
+    wts = [w.t().contiguous() for w in weights[:-1]]
+    gw, gb = [torch.empty_like(w) for w in weights], [torch.empty_like(b) for b in biases]
+    ggamma, gbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    gh = torch.empty_like(h) if want_h else None
+    order = ptr = None
+    if want_h and n:
+        ids = torch.cat([u, v]).to(_I64)
+        order = torch.sort(ids, stable=True).indices.to(_I32)
+        ptr = torch.zeros(n_nodes + 1, dtype=_I64, device=dev)
+        torch.cumsum(torch.bincount(ids, minlength=n_nodes)[:n_nodes], 0, out=ptr[1:])
+    ws, ws_ptr, ws_bytes = _bn_workspace(n, hd, L, dev)
+    arr = lambda ts, k: (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in ts])   # noqa: E731
+    _call("eps_mlp_decode_bn_backward", dev, h, n_nodes, hd, u, v, n, arr(weights, L), arr(wts, L - 1), arr(biases, L), L,
+          arr([folded_w], 1), arr([folded_b], 1), gamma, mean, var, float(eps), keep, float(keep_scale), grad_out, order, ptr,
+          arr(gw, L), arr(gb, L), ggamma, gbeta, gh, ws_ptr, ws_bytes)
+    return gh, gw, gb, ggamma, gbeta
+
+
 SIGNATURES = _lib.SIGNATURES      # name -> (restype, argtypes) of every export: the table tests/test_abi.py holds to the header
 BF16_MAX_HIDDEN = 256             # csrc/mlp_decode_bf16.hip: hdim % 16 == 0 && hdim <= 256, 2 <= layers
 

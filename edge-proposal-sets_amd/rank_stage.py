@@ -56,6 +56,7 @@ def make_parser():
     parser.add_argument('--load_model', type=str, default="")
     parser.add_argument('--train_cosine', action="store_true", default=False)   # train mlpcos's embedding (see run())
     parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
+    parser.add_argument('--fused_decode_bn', action="store_true", default=False)   # dea: the same, BatchNorm on batch statistics included
     parser.add_argument('--no_incremental_graph', action="store_true", default=False)   # rebuild the graph from the edge list at every point
     return parser
 
@@ -202,7 +203,20 @@ def run(args):
         # (before any data is read)
         raise ValueError(f"--fused_decode trains the LinkPredictor decoder of --model gcn / sage through the fused HIP kernels; "
                          f"--model {args.model} has no such decoder (dea's decoder applies BatchNorm on batch statistics, which "
-                         f"needs a reduction across the kernel's edge tiles: not supported)")
+                         f"needs a reduction across the kernel's edge tiles: not supported by this flag; --fused_decode_bn trains "
+                         f"--model dea through the kernels that carry it)")
+    if getattr(args, 'fused_decode_bn', False):
+        # (before any data is read, after default_model_configs has filled the width in)
+        if getattr(args, 'fused_decode', False):
+            raise ValueError("--fused_decode_bn and --fused_decode exclude each other: the first trains --model dea, the second "
+                             "--model gcn / sage")
+        if args.model != 'dea':
+            raise ValueError(f"--fused_decode_bn trains the decoder of --model dea (Linear, BatchNorm, ReLU, Linear) through the fused "
+                             f"HIP kernels; --model {args.model} has no such decoder"
+                             f"{' (dea_512 is wider than the kernels go: H <= 256)' if args.model == 'dea_512' else ''}")
+        hc = args.hidden_channels
+        if hc is None or hc % 4 != 0 or not 32 <= hc <= 256:
+            raise ValueError(f"--fused_decode_bn: --hidden_channels {hc} is outside the kernels' domain (a multiple of 4 in 32..256)")
     if args.model == 'mlpcos' and not args.load_model and not getattr(args, 'train_cosine', False):
         # (before any data is generated.  Training mlpcos is opt-in: the bare command keeps the refusal it always had)
         raise NotImplementedError("rank.py --model mlpcos trains its embedding through the cosine scores: pass --train_cosine "
@@ -226,7 +240,7 @@ def run(args):
         raise ValueError("Model not specified")
     data = data.to(device)
     model = build_model(args, data, device)
-    if getattr(args, 'fused_decode', False):
+    if getattr(args, 'fused_decode', False) or getattr(args, 'fused_decode_bn', False):
         model.fused_decode = True
     print(f'using model {model}')
     evaluator, ks = evaluators[args.dataset], hits[args.dataset]

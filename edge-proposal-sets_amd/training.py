@@ -4,7 +4,8 @@ cosine common-neighbour models with an embedding (mlpcos: the gradient reaches e
 Outside the scored hot path but needed to produce the checkpoints filter.py consumes and to
 run rank.py with a parametrised model: torch autograd drives it, the GNN aggregate is the HIP SpMM (custom autograd
 Function in models.py), dense layers and the pairwise decode run on torch in training mode (the decode of gcn / sage runs on
-csrc/mlp_decode_train.hip instead when LinkGNN.fused_decode is set: rank.py --fused_decode).
+csrc/mlp_decode_train.hip instead when LinkGNN.fused_decode is set: rank.py --fused_decode; DEA_GNN_JK.fused_decode:
+rank.py --fused_decode_bn).
 """
 from __future__ import annotations
 

@@ -559,6 +559,40 @@ int eps_mlp_decode_backward(const float *h, int64_t n_nodes, int32_t hdim, const
                             float *const *grad_w, float *const *grad_b, float *grad_h, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ---- K6d: the training decode of DEA_GNN_JK: BatchNorm on batch statistics between Linear and ReLU -----
+ * Replaces, in training mode, the decoder of the reference's DEA_GNN_JK.forward (models.py:118-128: Hadamard -> Linear(H, H)
+ * -> BatchNorm1d on batch statistics -> ReLU -> dropout -> Linear(H, 1), a logit) and what autograd records for it
+ * (train_and_eval.py:66-71).  Per channel c over the n_pairs edges: z = x0 W0^T + b0, mu = mean(z), var = the BIASED
+ * variance, sigma = sqrt(var + eps), y = gamma (z - mu) / sigma + beta, a = relu(y) keep keep_scale, out = a . w1 + b1.
+ * Domain of all three calls: hdim % 4 == 0, 32 <= hdim <= 256, n_layers == 2, 2 <= n_pairs < 2^30; anything else is
+ * EPS_EINVAL (the message names hdim= / n_layers= / n_pairs=) before any launch (the workspace query returns 0).
+ * w, b: HOST arrays of n_layers device pointers to the layers AS THEY ARE (w[0] = W0 [hdim, hdim], w[1] = w1 [1, hdim]).
+ * eps_mlp_decode_bn_stats: mean, var float32 [hdim] of z over the batch (per-workgroup (count, mean, M2) triples in float64,
+ *   merged in workgroup order).
+ * The forward is eps_mlp_decode_train on the folded layer wf = diag(s) W0, bf = s b0 + beta - s mu, s = gamma / sigma,
+ *   with apply_sigmoid = 0.
+ * eps_mlp_decode_bn_backward: grad_out float32 [n_pairs] = dL/d(out).  wt[0]: W0 transposed; wf / bf: HOST arrays of
+ *   n_layers - 1 pointers to the folded layer the forward ran on (the backward follows ITS ReLU branch); mean / var: what
+ *   eps_mlp_decode_bn_stats returned.  Outputs, each nullable: grad_w[l] / grad_b[l] shaped like w[l] / b[l] (grad_b[0]
+ *   is written as exact zeros: a bias in front of batch statistics has no gradient), grad_gamma, grad_beta float32 [hdim],
+ *   grad_h float32 [n_nodes, hdim] with inc_order / inc_ptr and the incidence-order rule of eps_mlp_decode_backward.
+ * workspace: eps_mlp_decode_bn_workspace_bytes(...) bytes (serves either call), 16-byte aligned, contents arbitrary.
+ * No atomics; every summation order is a function of the shapes and the device's CU count: the same inputs give the same
+ * bits.  Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int64_t eps_mlp_decode_bn_workspace_bytes(int64_t n_pairs, int32_t hdim, int32_t n_layers);
+int eps_mlp_decode_bn_stats(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u,
+                            const int32_t *v, int64_t n_pairs, const float *const *w,
+                            const float *const *b, int32_t n_layers, float *mean, float *var,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+int eps_mlp_decode_bn_backward(const float *h, int64_t n_nodes, int32_t hdim, const int32_t *u,
+                               const int32_t *v, int64_t n_pairs, const float *const *w, const float *const *wt,
+                               const float *const *b, int32_t n_layers, const float *const *wf,
+                               const float *const *bf, const float *gamma, const float *mean, const float *var,
+                               float bn_eps, const uint32_t *keep, float keep_scale, const float *grad_out,
+                               const int32_t *inc_order, const int64_t *inc_ptr, float *const *grad_w,
+                               float *const *grad_b, float *grad_gamma, float *grad_beta, float *grad_h,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- top-K selection with the declared tie rule ------------------------------------------
  * Replaces `all_scores[:,2].sort(descending=True)` (filter.py:160-161) for the K rows rank.py
  * ever reads (rank.py:294).  Declared order: score descending, then `id` ascending (== a stable

@@ -8,6 +8,9 @@ chained with `&&` (a step that fails, faults or runs out of time ends the run; n
 
   ddi:    N = 4,267,   B = 262,144 edges, H = 256, L = 2      collab: N = 235,868, B = 65,536, H = 256, L = 3
   each with dropout 0.5 and 0.  A step = scores -> training's log loss -> backward into h and the decoder's parameters.
+  dea_ddi / dea_collab: the same batches through DEA_GNN_JK's decoder (Linear, BatchNorm on batch statistics, ReLU, dropout,
+  Linear; L = 2, logits, BCE with logits): DEA_GNN_JK.decode_train (eps_mlp_decode_bn_stats + eps_mlp_decode_train on the folded
+  layer + eps_mlp_decode_bn_backward, the running statistics' update included) against the torch ops of DEA_GNN_JK.forward.
   HIP events, median of --reps after --warmup.  Also reported: per tensor, the largest difference of the two routes' gradients at
   dropout 0 (at 0.5 they draw different masks), and whether two fused steps under one seed return the same bits.
 
@@ -25,26 +28,43 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = {"ddi": (4_267, 262_144, 256, 2), "collab": (235_868, 65_536, 256, 3)}
-STEPS = [f"{s}:{p}" for s in SHAPES for p in ("0.5", "0")]
+DEA_SHAPES = {"dea_ddi": (4_267, 262_144, 256, 2), "dea_collab": (235_868, 65_536, 256, 2)}
+STEPS = [f"{s}:{p}" for s in SHAPES for p in ("0.5", "0")] + ["dea_ddi:0.5", "dea_ddi:0", "dea_collab:0"]
 STEP_SECONDS = 240
 
 
 def run_step(a, dev):
     import torch
+    import torch.nn.functional as F
     from eps_amd import models
     shape, p = a.step.split(":")
-    n, B, H, L = SHAPES[shape]
+    dea = shape in DEA_SHAPES
+    n, B, H, L = (DEA_SHAPES if dea else SHAPES)[shape]
     torch.manual_seed(0)
-    lp = models.LinkPredictor(H, H, 1, L, float(p)).to(dev).train()
     h = torch.randn(n, H, device=dev).requires_grad_(True)
     edges = torch.randint(0, n, (2, B), device=dev)
-    params = [h] + list(lp.parameters())
+    if dea:
+        # (only the decoder runs here: one node's embedding, the TAG layers idle)
+        lp = models.DEA_GNN_JK(1, H, H, H, H, 3, H, H, 1, 2, float(p), True, True).to(dev).train()
+        named = [(k, t) for k, t in lp.named_parameters() if k.startswith(("lins.", "mlp_bns."))]
+        label = torch.cat([torch.ones(B // 2), torch.zeros(B - B // 2)]).to(dev)
+    else:
+        lp = models.LinkPredictor(H, H, 1, L, float(p)).to(dev).train()
+        named = list(lp.named_parameters())
+    params = [h] + [t for _, t in named]
+
+    def dea_torch():                # DEA_GNN_JK.forward's decoder
+        x = lp.mlp_bns[0](lp.lins[0](h[edges[0]] * h[edges[1]]))
+        return lp.lins[1](F.dropout(F.relu(x), p=lp.dropout, training=True)).squeeze(1)
 
     def step(fused):
         for t in params:
             t.grad = None
-        out = lp.decode_train(h, edges) if fused else lp(h[edges[0]], h[edges[1]]).squeeze(1)
-        loss = -torch.log(out[:B // 2] + 1e-8).mean() - torch.log(1 - out[B // 2:] + 1e-8).mean()
+        if dea:
+            loss = lp.loss(lp.decode_train(h, edges) if fused else dea_torch(), label)
+        else:
+            out = lp.decode_train(h, edges) if fused else lp(h[edges[0]], h[edges[1]]).squeeze(1)
+            loss = -torch.log(out[:B // 2] + 1e-8).mean() - torch.log(1 - out[B // 2:] + 1e-8).mean()
         loss.backward()
         return [t.grad for t in params]
 
@@ -65,7 +85,8 @@ def run_step(a, dev):
     res["torch_ms"], res["torch_min_ms"] = timed(False)
     res["fused_ms"], res["fused_min_ms"] = timed(True)
     res["fused_over_torch"] = round(res["fused_ms"] / res["torch_ms"], 3)
-    flop = B * (3 * 2 * H * H * (L - 1) + 6 * H)          # forward + dA + dW per hidden layer (the fused route adds one forward)
+    flop = B * (3 * 2 * H * H * (L - 1) + 6 * H)          # forward + dA + dW per hidden layer (the fused route adds one forward;
+                                                          # dea's adds four: statistics, dy, grad gamma, dz)
     res["model_gflop_per_step"] = round(flop / 1e9, 2)
     grads = []
     for _ in range(2):
@@ -74,8 +95,10 @@ def run_step(a, dev):
     res["fused_reproducible"] = all(torch.equal(x, y) for x, y in zip(*grads))
     if float(p) == 0:
         ref = step(False)
-        names = ["h"] + [k for k, _ in lp.named_parameters()]
-        rel = {k: float((x - y).abs().max() / y.abs().max().clamp(min=1e-30)) for k, x, y in zip(names, grads[0], ref)}
+        names = ["h"] + [k for k, _ in named]
+        # (dea's lins.0.bias sits in front of batch statistics: its true gradient is 0, the fused route writes 0, torch float noise)
+        rel = {k: float((x - y).abs().max() / y.abs().max().clamp(min=1e-30)) for k, x, y in zip(names, grads[0], ref)
+               if not (dea and k == "lins.0.bias")}
         res["rel_grad_diff_vs_torch"] = {k: float(f"{v:.3g}") for k, v in rel.items()}     # per tensor, of that tensor's max|grad|
     return res
 
