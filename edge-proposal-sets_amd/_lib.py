@@ -126,6 +126,11 @@ SIGNATURES = {
     "eps_katz_workspace_bytes": (_i64, [_i64]),
     "eps_katz_pair_scores": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_double, _c.c_double,
                                     _c.c_double, _vp, _vp, _vp]),
+    "eps_katz_columns_limits": (_int, [_c.POINTER(_i32), _c.POINTER(_i32)]),
+    "eps_katz_columns_workspace_bytes": (_i64, [_i64]),
+    "eps_katz_columns_chunk": (_i64, [_i64]),
+    "eps_katz_column_scores": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _c.c_double, _c.c_double,
+                                      _c.c_double, _i64, _i32, _vp, _i64, _vp, _vp]),
     "eps_cos_node_features": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "eps_edge_cosines": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "eps_cos_node_features_nrm": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),

@@ -23,7 +23,8 @@ import torch
 from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
-from .heuristics import cosine_graph, node_weight_table, pair_scores_streamed, sigmoid_raw_cut
+from .heuristics import (KATZ_BETA, cosine_graph, katz_steps_bound, node_weight_table, pair_scores_streamed, sigmoid_raw_cut,
+                         truncated_katz, truncated_katz_columns)
 from .models import DECODE_PRECISIONS, build_model, default_model_configs
 
 
@@ -153,6 +154,8 @@ def score_block(args, model, data, pairs: torch.Tensor, ra_graph=None) -> torch.
     if args.model == "resource_allocation":              # filter.py:127-142 (float64 math, FloatTensor out)
         w = node_weight_table(ra_graph, ops.W_RA, f64=True)
         return pair_scores_streamed(ra_graph, u, v, w, grouped=True)[2].to(torch.float32)
+    if args.model == "katz":                             # (CommonNeighborsPredictor('katz') returns None, as in the reference)
+        return truncated_katz(data.adj_t, pairs, beta=KATZ_BETA, device_out=True)
     return model(data.x, pairs, data.adj_t).reshape(-1)  # filter.py:116-121
 
 
@@ -280,6 +283,9 @@ COSINE_FUSED = True        # cosine filters: fused signed expansion (False: cand
 LAST_COSINE_CUTS = []      # the last fused cosine run, per column block: (v_lo, v_hi, raw threshold or None, "scored" / "cut" / "skipped")
 
 
+KATZ_COLUMNS = True         # the Katz filter: the column kernel (False: candidate lists + the pair kernel, for comparisons)
+
+
 def cosine_blocks(args, model, data, blocks, bar=None, fused: bool = True):
     """``scored_blocks`` of the cosine filters (models.py:556-575): candidates of the graph as it is, scores
     sigmoid(sum_w c[u,w] * c[v,w]) with c the stored cosines of ``heuristics.cosine_graph``.  The fused expansion walks
@@ -328,6 +334,25 @@ def cosine_blocks(args, model, data, blocks, bar=None, fused: bool = True):
         yield v_lo, v_hi, blk, blk.score
 
 
+def katz_blocks(args, data, blocks):
+    """``scored_blocks`` of the Katz filter: candidates of the graph as it is (list-only expansion), scores
+    beta*A + 2 beta^2 A^2 + beta^3 A^3 at every one of them from the column kernel (csrc/katz_columns.hip), on EVERY dataset --
+    the truncated series of test_katz's collab branch (train_and_eval.py:285-291); the exact inverse of its other branch is a
+    dense N x N object, and a filter needs an ordering of the 2-hop candidates only.  Blocks are [2,E] pair tensors, so the
+    streaming top-K, the per-node cut, column shards and the full sort take them as they take any other block."""
+    g = data.adj_t
+    print(f'Katz filter: truncated series, beta = {KATZ_BETA}; at most {katz_steps_bound(g):.3e} three-hop steps '
+          f'(sum over the candidates of deg(u), bounded from the two-hop path counts of the whole graph)')
+    for v_lo, v_hi in blocks:
+        pairs = candidates.expand_block(g, v_lo, v_hi)[0]
+        if pairs.shape[1] == 0:
+            yield v_lo, v_hi, pairs, None
+            continue
+        v = pairs[1].contiguous()
+        colptr = torch.searchsorted(v, torch.arange(v_lo, v_hi + 1, dtype=v.dtype, device=v.device)).to(torch.int64)
+        yield v_lo, v_hi, pairs, truncated_katz_columns(g, v_lo, v_hi, colptr, pairs[0], beta=KATZ_BETA, device_out=True)
+
+
 def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = None, bar=None):
     """(v_lo, v_hi, pairs, scores) per column block.  Heuristic filters whose scoring graph IS the candidate graph
     (AA: filter.py:122-126; CN 'simple': :116-121 with models.py:536-542) come out of the fused expansion already
@@ -338,6 +363,9 @@ def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = No
     blocks = [(max(lo, col_lo), min(hi, col_hi)) for lo, hi in candidates.column_blocks(g) if lo < col_hi and hi > col_lo]
     if args.model in COSINE_MODELS:
         yield from cosine_blocks(args, model, data, blocks, bar, fused=COSINE_FUSED and candidates.hip_expand_available(g))
+        return
+    if args.model == "katz" and KATZ_COLUMNS and candidates.hip_expand_available(g, scored=False):
+        yield from katz_blocks(args, data, blocks)
         return
     node_w = fused_node_weights(args, g, ra_graph) if candidates.hip_expand_available(g) else None
     if node_w is not None and not candidates.fused_scores_fit(g, node_w):
@@ -454,7 +482,7 @@ def run(args) -> str:
             print('dense common-neighbour product (A A^T on the f32 MFMA)')
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS and scan.scan_plausible(data.adj_t):
+    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) and scan.scan_plausible(data.adj_t):
         # (the hubs-first copy first: the symmetry check of scan_available then reads the COPY's reverse positions -- the table
         #  the scan needs anyway -- instead of building one for the graph as labelled, 3-5 ms on a ppa-sized graph)
         scan.scan_graph(data.adj_t, build=True)

@@ -8,6 +8,7 @@ types:
 * ``resource_allocation(adj_matrix, link_list, batch_size=32768)``  <- train_and_eval.py:195-216
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
+* ``truncated_katz_columns``                        <- the truncated series for a filter's column-major candidate blocks
 * ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
 * ``cosine_common_neighbors_raw(adj, x, edges)``     <- the same before the sigmoid, differentiable in x (training)
 
@@ -340,6 +341,42 @@ def truncated_katz(A, edge_index, beta: float = KATZ_BETA, iterations: int = 2, 
     gt, p_out, p_in = _katz_transpose(g)
     out = ops.katz_pair_scores(g.rowptr, g.col, g.val, gt.rowptr, gt.col, gt.val, p_out, p_in, g.n_rows, u, v, coeffs)
     return out if device_out else out.cpu()
+
+
+def truncated_katz_columns(A, v_lo: int, v_hi: int, colptr, cand_u, beta: float = KATZ_BETA, iterations: int = 2,
+                           device_out: bool = False) -> torch.Tensor:
+    """``truncated_katz`` for a FILTER's access pattern: float32[E] scores of the column-major candidates (cand_u[p], v) of the
+    columns [v_lo, v_hi) -- ``colptr`` [v_hi - v_lo + 1] gives every column's range, as ``candidates.expand_block`` lays a block
+    out.  One eps_katz_column_scores launch (csrc/katz_columns.hip): (A^2)[:, v] is built once per column and every candidate
+    costs one pass over its row.  Same score, bit for bit the same under any split into blocks; any u may be listed."""
+    coeffs = katz_coefficients(beta, iterations)
+    g = _as_graph(A)
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"truncated Katz needs a square adjacency, got {g.sparse_sizes()}")
+    colptr = torch.as_tensor(colptr).to(device=g.device, dtype=torch.int64).contiguous()
+    cand_u = torch.as_tensor(cand_u)
+    if cand_u.dtype != torch.int32:             # (ids that an int32 cannot hold stop here; ops checks the range of the rest)
+        check_node_ids(cand_u, g.n_rows, "candidate list")
+    cand_u = cand_u.to(device=g.device, dtype=torch.int32).contiguous()
+    gt, _, p_in = _katz_transpose(g)
+    out = ops.katz_column_scores(g.rowptr, g.col, g.val, gt.rowptr, gt.col, gt.val, p_in, g.n_rows, v_lo, v_hi, colptr, cand_u,
+                                 coeffs)
+    return out if device_out else out.cpu()
+
+
+def katz_column_steps(g: CSRGraph, cand_u: torch.Tensor) -> int:
+    """Three-hop steps of the column kernel on a candidate list: one table lookup per stored entry of every candidate's row,
+    sum over the candidates of deg(u).  (Plain tensor ops: also on CPU graphs.)"""
+    deg = g.rowptr[1:] - g.rowptr[:-1]
+    return int(deg[cand_u.to(torch.int64)].sum().item()) if cand_u.numel() else 0
+
+
+def katz_steps_bound(g: CSRGraph) -> int:
+    """Upper bound of ``katz_column_steps`` over ALL 2-hop non-edges of the graph without listing them: node u is the first
+    element of at most min(two-paths out of u, N - 1) candidates, each costing deg(u)."""
+    from .candidates import path_counts
+    deg = g.rowptr[1:] - g.rowptr[:-1]
+    return int((deg * torch.clamp(path_counts(g), max=max(g.n_rows - 1, 0))).sum().item()) if g.n_rows else 0
 
 
 def exact_katz_bytes(n: int) -> int:

@@ -219,6 +219,62 @@ def katz_pair_scores(rowptr, col, val, rowptr_t, col_t, val_t, paths_out, paths_
     return out
 
 
+def katz_columns_limits() -> Tuple[int, int]:
+    """(largest support bound min(paths_in[v], N) whose y2 table stays in LDS, smallest default number of candidates per work
+    unit -- ``katz_columns_chunk`` gives a list's own) of eps_katz_column_scores (host-only query)."""
+    cap, chunk = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.load().eps_katz_columns_limits(ctypes.byref(cap), ctypes.byref(chunk)), "eps_katz_columns_limits")
+    return cap.value, chunk.value
+
+
+def katz_columns_chunk(n_cand: int) -> int:
+    """Candidates per work unit eps_katz_column_scores takes by default for a list of ``n_cand`` candidates (host-only query)."""
+    return int(_lib.load().eps_katz_columns_chunk(int(n_cand)))
+
+
+def katz_column_scores(rowptr, col, val, rowptr_t, col_t, val_t, paths_in, n_nodes: int, v_lo: int, v_hi: int, colptr, cand_u,
+                       coeffs: Sequence[float], chunk: int = 0) -> torch.Tensor:
+    """-> float32[E]: c1*A[u,v] + c2*(A^2)[u,v] + c3*(A^3)[u,v] of the column-major candidates of columns [v_lo, v_hi)
+    (``colptr`` int64[v_hi - v_lo + 1], ``cand_u`` int32[E]; any u of the graph may be listed), with (A^2)[:, v] built once per
+    column (csrc/katz_columns.hip; float64 accumulate, one rounding).  ``(rowptr_t, col_t, val_t)`` is A's transpose (A's own
+    tensors when A is symmetric), ``paths_in`` = ``two_path_counts`` of A^T.  ``chunk``: candidates per work unit (0: the
+    kernel's default; the scores do not depend on it).  Node ids and the column pointers' ends are checked
+    here, on the host, before anything is launched."""
+    dev = _need_gpu(rowptr, col, val, rowptr_t, col_t, val_t, paths_in, colptr, cand_u)
+    _csr(rowptr, col, val); _csr(rowptr_t, col_t, val_t, "_t")
+    _chk(_I64, paths_in=paths_in, colptr=colptr); _chk(_I32, cand_u=cand_u)
+    v_lo, v_hi, n_nodes = int(v_lo), int(v_hi), int(n_nodes)
+    if rowptr.numel() != n_nodes + 1 or rowptr_t.numel() != n_nodes + 1 or paths_in.numel() != n_nodes:
+        raise _lib.EpsError(f"katz_column_scores: A, A^T and the two-path counts must all describe {n_nodes} nodes")
+    if not 0 <= v_lo <= v_hi <= n_nodes:
+        raise _lib.EpsError(f"katz_column_scores: columns [{v_lo}, {v_hi}) outside [0, {n_nodes}]")
+    if colptr.numel() != v_hi - v_lo + 1:
+        raise _lib.EpsError(f"katz_column_scores: colptr must hold {v_hi - v_lo + 1} entries, got {colptr.numel()}")
+    if (val is None) != (val_t is None):
+        raise _lib.EpsError("katz_column_scores: A and A^T must both carry values or both be unit-valued")
+    c = [float(x) for x in coeffs]
+    if len(c) != 3:
+        raise _lib.EpsError(f"katz_column_scores: expected three coefficients, got {len(c)}")
+    n = cand_u.numel()
+    out = torch.empty(n, dtype=_F32, device=dev)
+    if n == 0:
+        return out
+    # one host read: the ids' range, the column pointers' ends and order, the largest support bound of the block
+    lo, hi = torch.aminmax(cand_u)
+    facts = torch.stack([lo.to(_I64), hi.to(_I64), colptr[0], colptr[-1], (colptr[1:] - colptr[:-1]).min(),
+                         paths_in[v_lo:v_hi].max()]).tolist()
+    if facts[0] < 0 or facts[1] >= n_nodes:
+        raise _lib.EpsError(f"katz_column_scores: node ids must lie in [0, {n_nodes}), got [{facts[0]}, {facts[1]}]")
+    if facts[2] != 0 or facts[3] != n or facts[4] < 0:
+        raise _lib.EpsError(f"katz_column_scores: colptr must ascend from 0 to {n} (the candidates), got {facts[2]} .. {facts[3]}")
+    max_support = min(int(facts[5]), n_nodes)
+    ws_bytes = int(_lib.load().eps_katz_columns_workspace_bytes(max_support))
+    ws = _scratch("katz_columns", dev, (ws_bytes + 7) // 8, (ws_bytes + 7) // 8) if ws_bytes else None
+    _call("eps_katz_column_scores", dev, rowptr, col, val, rowptr_t, col_t, val_t, paths_in, n_nodes, v_lo, v_hi, colptr, cand_u,
+          n, c[0], c[1], c[2], max_support, int(chunk), ws, ws_bytes, out, timed=("katz_columns_kernel", n))
+    return out
+
+
 def expand_max_nodes() -> int:
     return int(_lib.load().eps_expand_max_nodes())
 

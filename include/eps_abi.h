@@ -747,6 +747,31 @@ int eps_katz_pair_scores(const int64_t *rowptr, const int32_t *col, const float 
                          int64_t n_nodes, const int32_t *u, const int32_t *v, int64_t n_pairs, double c1, double c2,
                          double c3, void *workspace, float *out, void *stream);
 
+/* ---- Truncated Katz over a block of columns (csrc/katz_columns.hip) -----------------------------
+ * The filter's form of the score above: every candidate of column v shares y2 = (A^2)[:, v], so it is built once per
+ * column (a keyed table, in LDS or in the workspace) and candidate u costs one pass over row u:
+ *   out[p] = c1*A[u,v] + c2*(A^2)[u,v] + c3*(A^3)[u,v]          (float64 accumulate, float32 result)
+ * for candidate p = (cand_u[p], v), v the column of [v_lo, v_hi) whose range colptr[v - v_lo] .. colptr[v - v_lo + 1]
+ * holds p (colptr: int64[v_hi - v_lo + 1], ascending from 0 to n_cand -- the column-major layout of the expansion).
+ * Any u in [0, n_nodes) may be listed: stored edges, u == v and pairs without a walk of length <= 3 (exactly 0.0) too.
+ * A, A^T as for eps_katz_pair_scores (val and val_t both NULL: unit-valued); paths_in = eps_two_path_counts(A^T).
+ * max_support >= min(paths_in[v], n_nodes) for every column of the block: it sizes the workspace (device, 8-byte aligned,
+ * contents arbitrary, eps_katz_columns_workspace_bytes(max_support) bytes -- 0 while every table fits LDS); a column
+ * beyond it, or a cand_u outside the graph, scores NaN.  A score depends on the graph, the coefficients and the pair alone:
+ * bitwise equal across launches, blocks and splits.  chunk: candidates per work unit, 0 for the default (a column with more
+ * is scored by several units, each building its table again; any value in [1, 2^20] gives the same bits -- for measurements
+ * and tests).  eps_katz_columns_limits (host only): the largest support bound whose table stays in LDS, and the smallest
+ * default chunk; eps_katz_columns_chunk (host only): the default chunk of a list of n_cand candidates (longer lists take
+ * larger units, which rebuild the tables of split columns less often). */
+int eps_katz_columns_limits(int32_t *lds_capacity, int32_t *chunk);
+int64_t eps_katz_columns_chunk(int64_t n_cand);
+int64_t eps_katz_columns_workspace_bytes(int64_t max_support);
+int eps_katz_column_scores(const int64_t *rowptr, const int32_t *col, const float *val, const int64_t *rowptr_t,
+                           const int32_t *col_t, const float *val_t, const int64_t *paths_in, int64_t n_nodes,
+                           int64_t v_lo, int64_t v_hi, const int64_t *colptr, const int32_t *cand_u, int64_t n_cand,
+                           double c1, double c2, double c3, int64_t max_support, int32_t chunk, void *workspace,
+                           int64_t workspace_bytes, float *out, void *stream);
+
 /* ---- Cosine-weighted common neighbours: the prologue (csrc/cosine_cn.hip) -------------------------------------------
  * Replaces the per-path cosines of models.py:556-575 ('simplecos' / 'mlpcos'): both factors of a path u - w - v depend
  * on one stored entry, so the score is the edge-valued common-neighbour sum over the graph whose values are
