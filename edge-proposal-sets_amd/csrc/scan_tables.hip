@@ -180,7 +180,8 @@ __global__ void sp_screen_weights_kernel(const int64_t *__restrict__ fixw, int64
         }
         const unsigned long long q = ((unsigned long long)f + ((1ull << down) - 1ull)) >> down;
         if (q > 0xFFFFFFFFull) atomicOr(bad, 2u);
-        fx32[i] = q ? (uint32_t)q : 1u;
+        const uint32_t low = (uint32_t)q;             // (a flagged quotient keeps its low word -- and a multiple of 2^32 is no 0 either)
+        fx32[i] = low ? low : 1u;
     }
 }
 
