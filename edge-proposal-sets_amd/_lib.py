@@ -142,6 +142,10 @@ SIGNATURES = {
     "eps_csr_merge_fill": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "eps_segment_topk_class_max": (_i64, [_i32]),
     "eps_segment_topk": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "eps_local_index_pairs": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "eps_local_index_columns_workspace_bytes": (_i64, [_i64]),
+    "eps_local_index_columns": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                       _i64, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

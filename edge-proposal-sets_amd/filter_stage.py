@@ -23,8 +23,8 @@ import torch
 from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
-from .heuristics import (KATZ_BETA, cosine_graph, katz_steps_bound, node_weight_table, pair_scores_streamed, sigmoid_raw_cut,
-                         truncated_katz, truncated_katz_columns)
+from .heuristics import (KATZ_BETA, LOCAL_INDICES, cosine_graph, katz_steps_bound, local_index_columns, node_weight_table,
+                         pair_scores_streamed, sigmoid_raw_cut, truncated_katz, truncated_katz_columns)
 from .models import DECODE_PRECISIONS, build_model, default_model_configs
 
 
@@ -353,11 +353,76 @@ def katz_blocks(args, data, blocks):
         yield v_lo, v_hi, pairs, truncated_katz_columns(g, v_lo, v_hi, colptr, pairs[0], beta=KATZ_BETA, device_out=True)
 
 
+LOCAL_INDEX_CUT = True      # local-index filters under --keep_top: the kernel's survivor lists (False: every block scored in full, for comparisons)
+LAST_LOCAL_INDEX_CUTS = []  # the last local-index run, per column block: (v_lo, v_hi, bar or None, "scored" / "cut")
+
+
+def _counted_block(g: CSRGraph, v_lo: int, v_hi: int, count_free: bool) -> candidates.ColumnBlock:
+    """The candidates of columns [v_lo, v_hi) with the number of common stored neighbours of every one in ``cn``: on graphs
+    without values the float32 unit-weight score of the list kernels (``ops.expand_unit``: that integer exactly, below 2^24
+    nodes), on graphs with values the int32 count of the fused expansion (``want_cn``; stored values play no part).
+    ``count_free``: the padded upper-bound layout (``candidates.segment_bounds``), no counting pass."""
+    if g.val is None and 0 < g.n_rows < 1 << 24 and g.nnz() < 1 << 30:
+        kw = {}
+        if count_free:
+            pre, pre_host = candidates.segment_bounds(g)
+            kw = dict(colptr_ub=(pre[v_lo:v_hi + 1] - pre[v_lo]).contiguous(), total_ub=int(pre_host[v_hi] - pre_host[v_lo]))
+        r = ops.expand_unit(g.rowptr, g.col, None, g.n_rows, v_lo, v_hi, scan.max_degree(g), scan.window_splits(g), want_score=True,
+                            want_v=False, col_order=candidates.heaviest_first(g, v_lo, v_hi), **kw)
+        if count_free and int(r.status.item()):
+            raise _lib.EpsError(f"local index filter: the one-pass list of columns [{v_lo}, {v_hi}) reported status {int(r.status.item())}")
+        return candidates.ColumnBlock(v_lo, r[0], r[1], r[4], None, counts=r.counts)
+    blk = candidates.expand_block_lazy(g, v_lo, v_hi, None, want_cn=True, count_free=count_free)
+    blk.score = None
+    return blk
+
+
+def local_index_blocks(args, data, blocks, bar=None):
+    """``scored_blocks`` of the degree-normalised local indices (``heuristics.LOCAL_INDICES``): candidates of the graph as it
+    is, each with its exact common-neighbour count out of the expansion, scored by the column kernel (csrc/local_index.hip).  A
+    degree-normalised score is no sum of per-neighbour weights, so there is no column bound for the threshold scan to screen
+    with: every candidate's score is formed.  Once the streaming top-K holds K proposals the kernel hands back only the
+    candidates above its bar (``ColumnBlock.survivors``; the count-free layout then costs nothing, nothing scans the block
+    afterwards); a block with more than CUT_CAPACITY of them is scored in full instead.  Graphs whose heaviest column outgrows
+    the fused expansion's scratch take list + pair-kernel counts, then the same kernel."""
+    g = data.adj_t
+    LAST_LOCAL_INDEX_CUTS.clear()
+    print(f'local index filter ({args.model}): expansion with common-neighbour counts + column kernel')
+    fused = candidates.hip_expand_available(g)
+    for v_lo, v_hi in blocks:
+        if not fused:
+            pairs, cn, _ = candidates.expand_block(g, v_lo, v_hi, want_cn=True)
+            if pairs.shape[1] == 0:
+                yield v_lo, v_hi, pairs, None
+                continue
+            v = pairs[1].contiguous()
+            colptr = torch.searchsorted(v, torch.arange(v_lo, v_hi + 1, dtype=v.dtype, device=v.device)).to(torch.int64)
+            blk = candidates.ColumnBlock(v_lo, colptr, pairs[0].to(torch.int32).contiguous(), cn, None)
+            yield v_lo, v_hi, pairs, local_index_columns(g, v_lo, v_hi, blk, args.model, check=False)
+            continue
+        thr = bar() if bar is not None and LOCAL_INDEX_CUT else None
+        blk = None
+        if thr is not None:
+            blk = _counted_block(g, v_lo, v_hi, count_free=True)
+            blk.survivors = local_index_columns(g, v_lo, v_hi, blk, args.model, bar=thr, capacity=CUT_CAPACITY, check=False)
+            if blk.survivors is None:
+                blk = None                           # more survivors than the list holds: score the block in full
+        if blk is None:
+            blk = _counted_block(g, v_lo, v_hi, count_free=False)
+            # (the list has just come out of the expansion: its ids and column pointers are the kernels' own)
+            blk.score = local_index_columns(g, v_lo, v_hi, blk, args.model, check=False)
+            LAST_LOCAL_INDEX_CUTS.append((v_lo, v_hi, thr, "scored"))
+        else:
+            LAST_LOCAL_INDEX_CUTS.append((v_lo, v_hi, thr, "cut"))
+        yield v_lo, v_hi, blk, blk.score
+
+
 def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = None, bar=None):
     """(v_lo, v_hi, pairs, scores) per column block.  Heuristic filters whose scoring graph IS the candidate graph
     (AA: filter.py:122-126; CN 'simple': :116-121 with models.py:536-542) come out of the fused expansion already
     scored; RA scores on the train-only graph (filter.py:130-141) and GNN filters decode the block's pairs; the cosine
-    filters score the cosine graph (``cosine_blocks``)."""
+    filters score the cosine graph (``cosine_blocks``); the local indices score (count, degrees) per candidate
+    (``local_index_blocks``)."""
     g = data.adj_t
     col_hi = g.n_rows if col_hi is None else col_hi
     blocks = [(max(lo, col_lo), min(hi, col_hi)) for lo, hi in candidates.column_blocks(g) if lo < col_hi and hi > col_lo]
@@ -366,6 +431,9 @@ def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = No
         return
     if args.model == "katz" and KATZ_COLUMNS and candidates.hip_expand_available(g, scored=False):
         yield from katz_blocks(args, data, blocks)
+        return
+    if args.model in LOCAL_INDICES and candidates.hip_expand_available(g, scored=False):
+        yield from local_index_blocks(args, data, blocks, bar)
         return
     node_w = fused_node_weights(args, g, ra_graph) if candidates.hip_expand_available(g) else None
     if node_w is not None and not candidates.fused_scores_fit(g, node_w):
@@ -482,7 +550,7 @@ def run(args) -> str:
             print('dense common-neighbour product (A A^T on the f32 MFMA)')
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) and scan.scan_plausible(data.adj_t):
+    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) + LOCAL_INDICES and scan.scan_plausible(data.adj_t):
         # (the hubs-first copy first: the symmetry check of scan_available then reads the COPY's reverse positions -- the table
         #  the scan needs anyway -- instead of building one for the graph as labelled, 3-5 ms on a ppa-sized graph)
         scan.scan_graph(data.adj_t, build=True)

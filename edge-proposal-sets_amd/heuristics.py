@@ -7,6 +7,8 @@ types:
 * ``AA(A, edge_index, batch_size=2000)``             <- adamic_utils.py:13-25
 * ``resource_allocation(adj_matrix, link_list, batch_size=32768)``  <- train_and_eval.py:195-216
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
+* ``local_index(adj, edges, index)``                 <- the degree-normalised local indices of Zhou, Lu, Zhang (``LOCAL_INDICES``)
+* ``local_index_columns``                            <- the same for a filter's column-major candidate blocks
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
 * ``truncated_katz_columns``                        <- the truncated series for a filter's column-major candidate blocks
 * ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
@@ -147,6 +149,38 @@ def common_neighbors(adj: CSRGraph, edges: torch.Tensor) -> torch.Tensor:
     u, v = _as_pairs(edges, g.device, g.n_rows)
     _, cn, _ = pair_scores_streamed(g, u, v, None, want_cn=True)
     return cn
+
+
+# ------------------------------------------------------------------------------------------- degree-normalised local indices
+# Zhou, Lu, Zhang, "Predicting missing links via local information" (the paper train_and_eval.py:197 cites for RA) compares ten
+# local indices; CN, AA and RA are 'simple', 'adamic_ogb' and 'resource_allocation', these are the other seven.  With c the number
+# of common STORED neighbours (stored values are ignored, also on collab) and a, b the numbers of stored entries of rows u, v:
+#   salton c/sqrt(ab)  jaccard c/(a+b-c)  sorensen 2c/(a+b)  hpi c/min(a,b)  hdi c/max(a,b)  lhn c/(ab)  pa ab;  0/0 -> 0.
+LOCAL_INDICES = tuple(ops.LOCAL_INDEX)
+
+
+def local_index(A, edge_index, index: str) -> torch.Tensor:
+    """The local index ``index`` (one of ``LOCAL_INDICES``) of the pairs ``edge_index`` [2,E]: same argument forms and the same
+    kind of tensor as ``common_neighbors`` (float32 on the adjacency's device).  The counts come from eps_pair_scores, the
+    scores from eps_local_index_pairs (float64 arithmetic on the integers, one rounding): score(u, v) == score(v, u) bit for
+    bit, and equal to what ``local_index_columns`` gives the same pair."""
+    if index not in ops.LOCAL_INDEX:
+        raise EpsError(f"local index '{index}': one of {', '.join(LOCAL_INDICES)}")
+    g = _as_graph(A)
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    cnt, _, _ = pair_scores_streamed(g, u, v, None, want_count=True, want_cn=False)
+    return ops.local_index_pairs(g.rowptr, g.n_rows, u, v, cnt, index)
+
+
+def local_index_columns(g: CSRGraph, v_lo: int, v_hi: int, block, index: str, bar=None, capacity: int = 0, check: bool = True):
+    """``local_index`` for a FILTER's access pattern: ``block`` is a ``candidates.ColumnBlock`` of the columns [v_lo, v_hi) whose
+    ``cn`` holds the common-neighbour count of every slot (int32, or the float32 unit-weight score of ``ops.expand_unit``);
+    padded blocks bring their ``counts``.  ``bar`` None -> float32 scores per slot; a bar -> ``(positions, scores)`` of the slots
+    that EXCEED it in ascending position (what ``ColumnBlock.survivors`` holds), or None when more than ``capacity`` do."""
+    if index not in ops.LOCAL_INDEX:
+        raise EpsError(f"local index '{index}': one of {', '.join(LOCAL_INDICES)}")
+    return ops.local_index_columns(g.rowptr, g.n_rows, v_lo, v_hi, block.colptr, block.cand_u, block.cn, index,
+                                   counts=block.counts, bar=bar, capacity=capacity, check=check)
 
 
 # ------------------------------------------------------------------------------------------- cosine common neighbours

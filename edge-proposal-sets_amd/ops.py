@@ -1448,6 +1448,109 @@ def segment_topk(colptr: torch.Tensor, score: torch.Tensor, k: int, counts: Opti
     return out
 
 
+LOCAL_INDEX = {"salton": 0, "jaccard": 1, "sorensen": 2, "hpi": 3, "hdi": 4, "lhn": 5, "pa": 6}     # csrc/local_index.hip: name -> code
+
+
+def _local_index_code(index) -> int:
+    if isinstance(index, str):
+        if index not in LOCAL_INDEX:
+            raise _lib.EpsError(f"local index '{index}': one of {', '.join(LOCAL_INDEX)}")
+        return LOCAL_INDEX[index]
+    return int(index)          # (the library refuses a code outside the table)
+
+
+def local_index_pairs(rowptr, n_nodes: int, u, v, cn, index) -> torch.Tensor:
+    """-> float32[E]: the local index ``index`` (a name of ``LOCAL_INDEX`` or its code) of the pairs (u[p], v[p]) whose numbers
+    of common stored neighbours are ``cn`` (int32: the ``count`` of ``pair_scores``); degrees are rowptr differences, float64
+    arithmetic, one rounding (eps_local_index_pairs).  Any pair may be listed; an id outside the graph scores NaN."""
+    dev = _need_gpu(rowptr, u, v, cn)
+    _chk(_I64, rowptr=rowptr); _chk(_I32, u=u, v=v, cn=cn)
+    n_nodes = int(n_nodes)
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"local_index_pairs: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    if u.numel() != v.numel() or u.numel() != cn.numel():
+        raise _lib.EpsError("local_index_pairs: u, v and cn differ in length")
+    out = torch.empty(u.numel(), dtype=_F32, device=dev)
+    _call("eps_local_index_pairs", dev, rowptr, n_nodes, u, v, cn, u.numel(), _local_index_code(index), out,
+          timed=("local_index_pairs_kernel", u.numel()))
+    return out
+
+
+def local_index_columns(rowptr, n_nodes: int, v_lo: int, v_hi: int, colptr, cand_u, cn, index, counts=None, bar=None,
+                        capacity: int = 0, out: Optional[torch.Tensor] = None, check: bool = True, stats: Optional[dict] = None):
+    """The local index ``index`` of a column-major candidate block (eps_local_index_columns): slot p of ``cand_u`` (int32) is the
+    pair (cand_u[p], v_lo + s) for the segment s = [colptr[s], colptr[s + 1]) that holds p -- with ``counts`` (int64 per
+    column) only [colptr[s], colptr[s] + counts[s]): the padded layout, whose other slots are neither read nor written.  ``cn``:
+    the common-neighbour counts per slot, int32 (``expand_candidates`` want_cn) or float32 holding the integer (the unit-weight
+    score of ``expand_unit``; n_nodes < 2^24).
+
+    ``bar`` None -> float32 scores per slot (into ``out`` when given; padding slots keep what they held).
+    ``bar`` (a float, or a 1-element float32 device tensor) -> ``(positions int64 ascending, scores)`` of the slots whose score
+    EXCEEDS it, or None when more than ``capacity`` do (score the block in full then); ``out`` is filled as well when given.
+    ``stats`` (a dict) receives ``n_surv``, the true number of such slots, either way.
+
+    ``check``: the ids of the live slots and the ends and order of ``colptr`` (and ``counts`` within the segments) are verified
+    here, on the host, before the launch (one read).  ``check=False`` is for lists that have just come out of the expansion
+    kernels: the kernel itself scores NaN for an id outside the graph and reads no slot beyond the list."""
+    dev = _need_gpu(rowptr, colptr, cand_u, cn, counts, out, bar if isinstance(bar, torch.Tensor) else None)
+    _chk(_I64, rowptr=rowptr, colptr=colptr, counts=counts); _chk(_I32, cand_u=cand_u); _chk(_F32, out=out)
+    if cn.dtype not in (_I32, _F32):
+        raise _lib.EpsError(f"local_index_columns: cn is int32 or float32, got {cn.dtype}")
+    v_lo, v_hi, n_nodes, capacity = int(v_lo), int(v_hi), int(n_nodes), int(capacity)
+    n_cols, n = v_hi - v_lo, cand_u.numel()
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"local_index_columns: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    if not 0 <= v_lo <= v_hi <= n_nodes:
+        raise _lib.EpsError(f"local_index_columns: columns [{v_lo}, {v_hi}) outside [0, {n_nodes}]")
+    if colptr.numel() != n_cols + 1 or (counts is not None and counts.numel() != n_cols):
+        raise _lib.EpsError(f"local_index_columns: colptr must hold {n_cols + 1} entries (counts {n_cols}), got {colptr.numel()}"
+                            + ("" if counts is None else f" ({counts.numel()})"))
+    if cn.numel() != n or (out is not None and out.numel() != n):
+        raise _lib.EpsError(f"local_index_columns: cn / out must hold one entry per slot of cand_u ({n})")
+    if check and n:
+        width = colptr[1:] - colptr[:-1]
+        facts = [colptr[0], colptr[-1], width.min()]
+        if counts is None:
+            lo, hi = torch.aminmax(cand_u)
+        else:
+            facts += [counts.min(), (width - counts).min()]
+            pos = torch.arange(n, dtype=_I64, device=dev)
+            seg = torch.searchsorted(colptr[1:].contiguous(), pos, right=True).clamp_(max=n_cols - 1)
+            live = cand_u[(pos - colptr[seg]) < counts[seg]]
+            lo, hi = torch.aminmax(live) if live.numel() else (cand_u.new_zeros(()), cand_u.new_zeros(()))
+        facts = torch.stack([x.to(_I64) for x in facts + [lo, hi]]).tolist()
+        if facts[0] != 0 or facts[1] != n or facts[2] < 0:
+            raise _lib.EpsError(f"local_index_columns: colptr must ascend from 0 to {n} (the slots), got {facts[0]} .. {facts[1]}")
+        if counts is not None and (facts[3] < 0 or facts[4] < 0):
+            raise _lib.EpsError("local_index_columns: counts must lie within the segments of colptr")
+        if facts[-2] < 0 or facts[-1] >= n_nodes:
+            raise _lib.EpsError(f"local_index_columns: node ids must lie in [0, {n_nodes}), got [{facts[-2]}, {facts[-1]}]")
+    code = _local_index_code(index)
+    cn_i, cn_f = (cn, None) if cn.dtype == _I32 else (None, cn)
+    if bar is None:
+        score = out if out is not None else torch.empty(n, dtype=_F32, device=dev)
+        _call("eps_local_index_columns", dev, rowptr, n_nodes, v_lo, v_hi, colptr, counts, cand_u, n, cn_i, cn_f, code, score,
+              None, 0, None, None, None, None, 0, timed=("local_index_columns_kernel", n))
+        return score
+    if not isinstance(bar, torch.Tensor):
+        bar = torch.tensor([float(bar)], dtype=_F32, device=dev)
+    _chk(_F32, bar=bar)
+    if bar.numel() != 1 or capacity < 0:
+        raise _lib.EpsError(f"local_index_columns: bar is one float32 and capacity >= 0, got {bar.numel()} entries, capacity {capacity}")
+    pos = torch.empty(capacity, dtype=_I64, device=dev)
+    val = torch.empty(capacity, dtype=_F32, device=dev)
+    n_surv = torch.zeros(1, dtype=_I64, device=dev)
+    ws_bytes = int(_lib.load().eps_local_index_columns_workspace_bytes(n))
+    ws = _scratch("local_index", dev, (ws_bytes + 7) // 8, (ws_bytes + 7) // 8) if ws_bytes else None
+    _call("eps_local_index_columns", dev, rowptr, n_nodes, v_lo, v_hi, colptr, counts, cand_u, n, cn_i, cn_f, code, out,
+          bar, capacity, pos, val, n_surv, ws, ws_bytes,
+          timed=("local_index_columns_kernel", n))
+    m = int(n_surv.item())
+    if stats is not None:
+        stats["n_surv"] = m
+    return None if m > capacity else (pos[:m], val[:m])
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

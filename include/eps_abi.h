@@ -866,6 +866,41 @@ int64_t eps_segment_topk_class_max(int32_t cls);
 int eps_segment_topk(const int64_t *colptr, const int64_t *counts_or_null, const float *score, int64_t n_seg, int64_t k,
                      const int64_t *outptr, const int32_t *order_or_null, int64_t *out_pos, void *stream);
 
+/* ---- Degree-normalised local indices (csrc/local_index.hip) -------------------------------------------------------------
+ * The local indices of Zhou, Lu and Zhang ("Predicting missing links via local information") beside CN, AA and RA.  With
+ * c = the number of common STORED neighbours of u and v (the pattern count: `count` of eps_pair_scores, `cn` of the
+ * expansions; stored values are ignored) and a = rowptr[u + 1] - rowptr[u], b = rowptr[v + 1] - rowptr[v]:
+ *   index 0 salton   c / sqrt(a b)      1 jaccard c / (a + b - c)     2 sorensen 2c / (a + b)     3 hpi c / min(a, b)
+ *         4 hdi      c / max(a, b)      5 lhn     c / (a b)           6 pa       a b
+ * A zero denominator scores 0.0.  float64 arithmetic on the integers, ONE rounding to float32: a score depends on
+ * (c, a, b, index) alone, so score(u, v) == score(v, u) bit for bit and no block, slice or launch shape changes it.  An id
+ * outside [0, n_nodes) scores NaN and touches nothing else.
+ *   eps_local_index_pairs: score[p] of the pairs (u[p], v[p]) with their counts cn[p] (int32), p < n_pairs; any pair may be
+ *       listed (stored edges, u == v, isolated nodes).
+ *   eps_local_index_columns: a column-major block of the filter stage.  Slot p of the n_slots slots of cand_u belongs to
+ *       column v = v_lo + s where segment s = [colptr[s], colptr[s + 1]) holds p (colptr int64[v_hi - v_lo + 1], ascending
+ *       from 0 to n_slots) -- or, with counts (int64[v_hi - v_lo]), [colptr[s], colptr[s] + counts[s]): the padded layout of a
+ *       count-free expansion, whose slots behind the counted entries are NEVER read and NEVER written.  The counts come as
+ *       cn_i32 (int32) or cn_f32 (float32 holding the integer, n_nodes < 2^24): exactly one of the two.
+ *       score_or_null (float32[n_slots]) receives every live slot's score.  bar_or_null (DEVICE float): the slots whose score
+ *       EXCEEDS *bar are reported in ascending position -- surv_pos[i] (int64), surv_score[i], i < min(*n_surv, capacity);
+ *       *n_surv (DEVICE int64) is the TRUE count, nothing is written past capacity (the caller then redoes the block with
+ *       score_or_null).  NaN never exceeds a bar.  Three launches -- survivors per fixed slice of the slot array, one exclusive
+ *       prefix, fill -- so the places do not depend on scheduling: no atomics, no workgroup waits on another.  workspace: with
+ *       a bar, eps_local_index_columns_workspace_bytes(n_slots) bytes, 8-byte aligned, contents arbitrary; else unused.
+ * EPS_EINVAL before any HIP call, the message naming the value: index outside [0, 7); both or neither count form; v_lo > v_hi
+ * or columns outside [0, n_nodes]; a negative n_nodes / n_slots / capacity / workspace_bytes; n_nodes >= 2^24 with cn_f32; a
+ * bar without n_surv (or without surv_pos / surv_score when capacity > 0); neither score nor bar; a workspace too small.
+ * Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_local_index_pairs(const int64_t *rowptr, int64_t n_nodes, const int32_t *u, const int32_t *v, const int32_t *cn,
+                          int64_t n_pairs, int32_t index, float *score, void *stream);
+int64_t eps_local_index_columns_workspace_bytes(int64_t n_slots);
+int eps_local_index_columns(const int64_t *rowptr, int64_t n_nodes, int64_t v_lo, int64_t v_hi, const int64_t *colptr,
+                            const int64_t *counts_or_null, const int32_t *cand_u, int64_t n_slots,
+                            const int32_t *cn_i32_or_null, const float *cn_f32_or_null, int32_t index, float *score_or_null,
+                            const float *bar_or_null, int64_t capacity, int64_t *surv_pos, float *surv_score,
+                            int64_t *n_surv, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
