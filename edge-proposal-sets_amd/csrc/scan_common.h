@@ -29,7 +29,11 @@ __device__ __forceinline__ int sp_wave_incl_scan(int x)
 // float(a * 2^-40) > threshold, i.e. a >= thr_fix (monotone: found by bisection); a screening sum s >= a / 2^(40 - shift),
 // so s >= floor(thr_fix / 2^(40 - shift)) holds for every such candidate.  Any bar <= 0 (or -inf): every candidate (1).
 // +inf / NaN: nothing passes (SP_FLAG: sums stay below 2^31).
-__device__ __forceinline__ uint32_t sp_bar_units(float thr, int shift)
+// ``up``: the quotient rounded UP instead -- s is a whole number, so s >= ceil(thr_fix / 2^(40 - shift)) holds for every such
+// candidate just as well, and then float(s * 2^-shift) >= float(thr_fix * 2^-40) > threshold: every reported screening score
+// exceeds the bar.  The launches over stored values take it (their list goes straight to the re-scoring); the unit-valued ones
+// keep the floor, which eps_scan_refine shares with them (a walked sum AT the bar in table units passes there).
+__device__ __forceinline__ uint32_t sp_bar_units(float thr, int shift, bool up = false)
 {
     auto above = [&](long long a) { return (float)((double)a * (1.0 / (double)(1ll << 40))) > thr; };
     if (!above(0x7fffffffffffffffll)) return SP_FLAG;
@@ -39,7 +43,7 @@ __device__ __forceinline__ uint32_t sp_bar_units(float thr, int shift)
         const long long mid = lo + ((hi - lo) >> 1);
         if (above(mid)) hi = mid; else lo = mid + 1;
     }
-    const unsigned long long q = (unsigned long long)lo >> (40 - shift);
+    const unsigned long long q = ((unsigned long long)lo + (up ? (1ull << (40 - shift)) - 1ull : 0ull)) >> (40 - shift);
     return q >= (unsigned long long)SP_FLAG ? SP_FLAG : (q ? (uint32_t)q : 1u);
 }
 #endif

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
     const __amdgpu_buffer_rsrc_t col_rs = __builtin_amdgcn_make_buffer_rsrc((void *)p.col, 0, p.col_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t val_rs = __builtin_amdgcn_make_buffer_rsrc((void *)(HV ? (const void *)p.val : (const void *)p.col), 0,
                                                                             p.col_bytes, 0x00020000);
-    const uint32_t thr32 = sp_bar_units(p.out->threshold, p.shift);
+    const uint32_t thr32 = sp_bar_units(p.out->threshold, p.shift, HV);      // (stored values: rounded up -- every survivor's score exceeds the bar)
     const uint32_t direct_ids = 2u * (uint32_t)slots;
     // Survivor slots are reserved in chunks (one global atomic each).  Without a bar every candidate of a piece survives: the
     // chunk holds a whole piece's yield.  With one, survivors are rare: a piece asks for room for 1024, and a survivor that

@@ -315,8 +315,12 @@ class Screen:
         exceeds its exact 2^-40 term by less than (2^d + 1) x 2^-shift: once for the round-up to 2^-shift, once for the d low
         bits a packed / 16-bit direct piece drops (d <= d_used).  A pair has at most max_deg paths -- and, when every node
         weighs at least w_min > 0, at most exact / w_min <= s / w_min of them, which is what keeps the bound tight under the
-        coarse weights (3.7 % of s on the ppa-like graph against 13230 x 2^-8 = 52 absolute).  Weighted graphs form a term from
-        two roundings (no dropped bits)."""
+        coarse weights (3.7 % of s on the ppa-like graph against 13230 x 2^-8 = 52 absolute).
+        Stored values (no dropped bits): a path's screening term is ceil(A[u,w] x rowf) + 1 with rowf inflated by 1 + 2^-20 and
+        three float32 roundings on the way, so it exceeds the exact term by up to 4 units AND by up to 2^-19 of the term
+        (_VAL_INFLATION).  The relative part adds up to less than 2^-19 s over the pair, and s stays below 2^31 units (screen_fits):
+        2^12 units cover it for every pair -- more than the 4 per path wherever rows are short and scores use the high bits of the
+        word (tests/test_gpu_weighted_values.py: without it the bound lay above the exact score by up to 8e-7 of it)."""
         a, b = self.lower_params(max_deg)
         return torch.maximum(s - a, s * b)
 
@@ -329,7 +333,10 @@ class Screen:
         b = 0.0
         if self.w_min > 0.0 and unit < self.w_min:
             b = 1.0 - 1.00001 * unit / self.w_min                                     # (w_min itself is exact to 2^-40)
-        return max_deg * unit, b
+        a = max_deg * unit
+        if self.val is not None:
+            a += (_VAL_INFLATION - 1.0) * 2.0 ** 31 * 2.0 ** -self.shift              # (the relative inflation of a sum below 2^31 units)
+        return a, b
 
 
 def _sum_bounds(g: CSRGraph, fx32: torch.Tensor):

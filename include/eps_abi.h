@@ -408,7 +408,8 @@ int eps_scan_plan(const int64_t *rowptr, const uint16_t *cuts, const uint32_t *w
  * multi-edge weights; val[e] must equal the value of e's mirror entry and be positive).  A path's term is
  * (A[u,w] * A[v,w]) * node_w[w] -- symmetric in (u, v), so the half scheme holds -- and its screening weight is formed per
  * path from the float values, rounded up.  node_w = the float32 node weights (no fx32 table); re-score with
- * eps_rescore_weighted. */
+ * eps_rescore_weighted.  The bar is taken rounded UP to a whole screening unit here (eps_scan_screen rounds it down, as
+ * eps_scan_refine does): every reported out->val exceeds out->threshold, and no candidate above it is lost. */
 int eps_scan_screen_weighted(const int64_t *rowptr, const int32_t *col, const float *val, const int32_t *revpos,
                              const float *node_w, const uint16_t *cuts, const uint32_t *wpaths, const int32_t *bounds,
                              int64_t n_nodes, int64_t nnz, const int32_t *columns, int64_t n_columns, int32_t shift,
