@@ -122,6 +122,17 @@ def check_per_node_args(args) -> None:
         raise ValueError(f"--keep_per_node {k}: the selection takes k < 2^31")
 
 
+NCN_MODELS = ('ncn', 'ncn_sage')
+
+
+def check_ncn_args(args) -> None:
+    """--model ncn / ncn_sage scores through the model's forward in one process: a sharded run is refused before the dataset is
+    read (the row-sharded embedding forward has not been tried with the common-neighbour sums on top)."""
+    import os
+    if args.model in NCN_MODELS and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError(f"--model {args.model} runs in one process: sharded filter runs are not supported for it")
+
+
 def per_node_positions(pairs, score: torch.Tensor, v_lo: int, v_hi: int, k: int) -> torch.Tensor:
     """Positions (ascending) of the candidates of one block of ``scored_blocks`` that the per-node cut keeps: for every column
     of [v_lo, v_hi) its k best in the declared order (``ops.segment_topk``).  A ``ColumnBlock`` brings its column pointers; an
@@ -490,6 +501,7 @@ def run(args) -> str:
     args = default_model_configs(args)
     check_per_node_args(args)
     check_decode_args(args)
+    check_ncn_args(args)
     print(args)
     Path("filtered_edges").mkdir(exist_ok=True)
     if not torch.cuda.is_available():

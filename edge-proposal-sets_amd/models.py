@@ -13,6 +13,9 @@ with the HIP SpMM as a custom autograd Function (forward and backward) and the d
 What differs from the reference on purpose: ``LinkGNN`` computes the node embeddings ``h`` ONCE per
 (parameters, x, adjacency) and reuses them for every scoring batch; the reference re-runs the whole
 GNN for each batch (models.py:505 called from filter.py:118).  Results are identical in eval mode.
+
+Beyond the reference: ``NCNPredictor`` / ``NCNLinkGNN`` (``--model ncn | ncn_sage``), Neural Common Neighbor on the
+common-neighbour lists of csrc/pair_cn_list.hip (``cn_embed_sum``).
 """
 from __future__ import annotations
 
@@ -485,6 +488,132 @@ class LinkGNN(_CachedEmbeddings, torch.nn.Module):
         return self.linkpred.decode(h, edges).unsqueeze(1)
 
 
+# ----------------------------------------------------------------------------------- Neural Common Neighbor
+CN_LIST_BUDGET = 1 << 26         # common neighbours listed per launch (4 bytes each, twice in training: the list and its transpose)
+
+
+class _CNEmbedSum(torch.autograd.Function):
+    """Z = C H for one list of pairs, C the [pairs x nodes] common-neighbour incidence (ops.pair_cn_list), and dH = C^T dZ: both
+    products are eps_spmm_csr without values, which adds sequentially in entry order -- Z[b] is the float32 sum of the rows h[w]
+    in ascending w, dH[w] that of dZ[b] in ascending b, bit for bit (fmaf(1, x, acc) is an exact add).  The transpose is built
+    in the backward, and only when h wants a gradient."""
+
+    @staticmethod
+    def forward(ctx, h, adj, u, v, count):
+        ptr, w = ops.pair_cn_list(adj.rowptr, adj.col, adj.n_rows, u, v, check=False, count=count)
+        ctx.lists, ctx.n = (ptr, w), h.shape[0]
+        return ops.spmm_csr(ptr, w, None, _pad4(h))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        ptr, w = ctx.lists
+        tptr, tb = ops.cn_list_transpose(ptr, w, ctx.n, check=False)
+        return ops.spmm_csr(tptr, tb, None, _pad4(grad_out)), None, None, None, None
+
+
+def cn_embed_sum(h: torch.Tensor, adj: CSRGraph, edges: torch.Tensor) -> torch.Tensor:
+    """-> float32 [B, H]: z_b = sum of h[w] over the common STORED neighbours w of the pair (edges[0, b], edges[1, b]) in ``adj``
+    (the pattern: stored values are not read), added in ascending w; differentiable in ``h`` (any width).  At most
+    CN_LIST_BUDGET common neighbours are listed at a time: a longer batch is cut on its cumulative counts, each piece with a
+    list of its own (a pair's sum does not depend on where the cuts fall; a single pair beyond the budget is a piece)."""
+    _check_rows(h, adj, "cn_embed_sum")
+    if adj.n_rows != adj.n_cols:
+        raise ValueError(f"cn_embed_sum: common neighbours need a square adjacency, got {adj.n_rows} x {adj.n_cols}")
+    heuristics.check_node_ids(edges, adj.n_rows, "cn_embed_sum edges")
+    e = edges.to(device=h.device, dtype=torch.int32)
+    u, v = e[0].contiguous(), e[1].contiguous()
+    b = u.numel()
+    if b == 0:
+        return h.new_zeros((0, h.shape[1]))
+    count = ops.pair_cn_list_count(adj.rowptr, adj.col, adj.n_rows, u, v, check=False)
+    cum = torch.cumsum(count, 0, dtype=torch.int64)
+    budget = int(CN_LIST_BUDGET)
+    if int(cum[-1].item()) <= budget:
+        return _CNEmbedSum.apply(h, adj, u, v, count)
+    cum, cuts, s, base = cum.cpu(), [0], 0, 0
+    while s < b:
+        # the longest run of pairs from s whose counts fit the budget -- at least one pair
+        s = max(s + 1, int(torch.searchsorted(cum, base + budget, right=True)))
+        cuts.append(s)
+        base = int(cum[s - 1])
+    return torch.cat([_CNEmbedSum.apply(h, adj, u[lo:hi], v[lo:hi], count[lo:hi]) for lo, hi in zip(cuts[:-1], cuts[1:])])
+
+
+class NCNPredictor(torch.nn.Module):
+    """The decoder of Neural Common Neighbor (Wang, Yang, Zhang): the pair's Hadamard product and the sum of its common
+    neighbours' embeddings each get a first layer,
+        t = relu(xij_lin(h_u * h_v)) + beta * relu(xcn_lin(z_cn)),
+    then dropout, relu(lin(t)) + dropout for each of lins[:-1], and sigmoid(lins[-1](t)).  ``lins`` holds num_layers - 1 layers
+    (num_layers >= 2); ``beta`` is a plain float.  The dense layers run on torch in training and in eval."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, beta=1.0):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError(f"NCNPredictor: num_layers {num_layers}: the two first layers and an output layer make at least 2")
+        self.xij_lin = torch.nn.Linear(in_channels, hidden_channels)
+        self.xcn_lin = torch.nn.Linear(in_channels, hidden_channels)
+        self.lins = torch.nn.ModuleList()
+        for _ in range(num_layers - 2):
+            self.lins.append(torch.nn.Linear(hidden_channels, hidden_channels))
+        self.lins.append(torch.nn.Linear(hidden_channels, out_channels))
+        self.dropout = dropout
+        self.beta = float(beta)
+
+    def reset_parameters(self):
+        self.xij_lin.reset_parameters()
+        self.xcn_lin.reset_parameters()
+        for lin in self.lins:
+            lin.reset_parameters()
+
+    def forward(self, x_i: torch.Tensor, x_j: torch.Tensor, z_cn: torch.Tensor) -> torch.Tensor:
+        drop = self.training and torch.is_grad_enabled()
+        t = F.relu(self.xij_lin(x_i * x_j)) + self.beta * F.relu(self.xcn_lin(z_cn))
+        t = F.dropout(t, p=self.dropout, training=drop)
+        for lin in self.lins[:-1]:
+            t = F.dropout(F.relu(lin(t)), p=self.dropout, training=drop)
+        return torch.sigmoid(self.lins[-1](t))
+
+
+NCN_EVAL_TILE = 1 << 15          # pairs per dense-layer call of NCNLinkGNN in eval: every call has this ONE shape
+NCN_EVAL_TILES_PER_LIST = 32     # ... and tiles per cn_embed_sum call (its host reads are per call: 2^20 pairs, 1 GiB of sums at H = 256)
+
+
+class NCNLinkGNN(LinkGNN):
+    """LinkGNN whose decoder also sees the pair's common neighbours: scores = linkpred(h_u, h_v, sum_{w in N(u) & N(v)} h_w), the
+    common neighbours being those of the ``adj`` passed in (no target-edge masking: v in N(u) puts neither u nor v into the
+    intersection).  Same state-dict prefixes, embedding-first input and eval-mode embedding cache as LinkGNN.
+
+    In eval the dense layers run on tiles of NCN_EVAL_TILE pairs, the last one padded: every GEMM then has one shape, so a
+    pair's score does not depend on the batch it arrives in -- the filter stage may cut its candidate blocks anywhere.  The list
+    of (u, v) equals that of (v, u) and h_u * h_v commutes, so score(u, v) == score(v, u) bit for bit."""
+
+    def forward(self, x, edges, adj):
+        if torch.is_grad_enabled() and self.training:
+            if x is None:
+                x = self.emb.weight
+            elif self.emb is not None:
+                x = torch.cat([self.emb.weight, x], dim=1)
+            h = self.gnn(x, adj)
+            return self.linkpred(h[edges[0]], h[edges[1]], cn_embed_sum(h, adj, edges))
+        with torch.no_grad():
+            h = self.embeddings(x, adj)
+            e = edges.to(device=h.device, dtype=torch.int64)     # (cn_embed_sum checks the ids before anything gathers with them)
+            n, tile = e.shape[1], int(NCN_EVAL_TILE)
+            out = torch.empty((n, self.linkpred.lins[-1].out_features), dtype=torch.float32, device=h.device)
+            for s0 in range(0, n, tile * NCN_EVAL_TILES_PER_LIST):
+                z_all = cn_embed_sum(h, adj, e[:, s0:s0 + tile * NCN_EVAL_TILES_PER_LIST])
+                for s in range(s0, s0 + z_all.shape[0], tile):
+                    u, v, z = e[0, s:s + tile], e[1, s:s + tile], z_all[s - s0:s - s0 + tile]
+                    xi, xj = h[u], h[v]
+                    if u.numel() < tile:
+                        pad = (0, 0, 0, tile - u.numel())
+                        xi, xj, z = F.pad(xi, pad), F.pad(xj, pad), F.pad(z, pad)
+                    out[s:s + tile] = self.linkpred(xi, xj, z)[:u.numel()]
+            return out
+
+
 # ----------------------------------------------------------------------------------- DEA_GNN_JK
 def fold_batchnorm(weight: torch.Tensor, bias: torch.Tensor, bn: torch.nn.BatchNorm1d):
     """(W', b') such that x W'^T + b' == bn(x W^T + b) with bn in eval mode (running statistics):
@@ -825,7 +954,8 @@ class CommonNeighborsPredictor(torch.nn.Module):
 # ----------------------------------------------------------------------------------- factory
 DECODE_MAX_HIDDEN = 256          # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 256
 _MODELS = ['sage', 'sage2', 'gcn', 'dea', 'dea_512', 'mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb',
-           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES]
+           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, 'ncn', 'ncn_sage']
+_NCN = {'ncn': 'gcn', 'ncn_sage': 'sage'}       # Neural Common Neighbor: name -> the encoder whose arguments and defaults it takes
 _HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES]
 
 
@@ -842,6 +972,13 @@ def build_model(args, data, device):
                              "them) or --use_learnable_embedding True")
     if args.model in ('dea', 'dea_512'):
         return _build_dea(args, data, device)
+    if args.model in _NCN:
+        # (before anything is allocated: ppa has no defaults, and the decoder's two first layers and its output layer make 2)
+        if args.hidden_channels is None:
+            raise UnsupportedModelConfig(f"--model {args.model} needs --hidden_channels (there is no "
+                                         f"{getattr(args, 'dataset', '')} default for it)")
+        if args.num_layers is None or args.num_layers < 2:
+            raise UnsupportedModelConfig(f"--model {args.model}: --num_layers {args.num_layers}: the decoder has at least 2 layers")
     emb = None
     if args.use_learnable_embedding:
         emb = torch.nn.Embedding(data.num_nodes, args.hidden_channels).to(device)
@@ -861,6 +998,11 @@ def build_model(args, data, device):
         linkpred = LinkPredictor(args.hidden_channels, args.hidden_channels, 1, args.num_layers,
                                  args.dropout).to(device)
         return LinkGNN(emb, gnn, linkpred)
+    if args.model in _NCN:
+        gnn_cls = SAGE if args.model == 'ncn_sage' else GCN
+        gnn = gnn_cls(input_dim, args.hidden_channels, args.hidden_channels, args.num_layers, args.dropout).to(device)
+        linkpred = NCNPredictor(args.hidden_channels, args.hidden_channels, 1, args.num_layers, args.dropout).to(device)
+        return NCNLinkGNN(emb, gnn, linkpred)
     if args.model in _HEURISTICS:
         return CommonNeighborsPredictor(emb, input_dim, args.hidden_channels, args.hidden_channels, args.num_layers,
                                         args.dropout, model_type=args.model).to(device)
@@ -895,12 +1037,13 @@ def _build_dea(args, data, device):
 
 
 # per-dataset defaults, one row per (dataset group, model group): restates the table of models.py:673-790
-_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage')
+_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage', 'ncn', 'ncn_sage')
 _KEYS = ["num_layers", "hidden_channels", "dropout", "batch_size", "lr", "epochs", "use_feature",
          "use_learnable_embedding"]
 
 
 def _defaults_for(dataset: str, model: str) -> dict:
+    model = _NCN.get(model, model)       # (ncn / ncn_sage: the row of their encoder)
     d = dict.fromkeys(_KEYS)
 
     def put(**kw):

@@ -1551,6 +1551,113 @@ def local_index_columns(rowptr, n_nodes: int, v_lo: int, v_hi: int, colptr, cand
     return None if m > capacity else (pos[:m], val[:m])
 
 
+def pair_cn_list_limits() -> Tuple[int, int]:
+    """(long-row entries staged in LDS per pass, ratio long / short from which a longer row is searched in place) of the
+    common-neighbour list kernel: the sizes at which it changes its path (host-only query)."""
+    cap, ratio = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.load().eps_pair_cn_list_limits(ctypes.byref(cap), ctypes.byref(ratio)), "eps_pair_cn_list_limits")
+    return cap.value, ratio.value
+
+
+def _cn_list_args(who: str, rowptr, col, n_nodes: int, u, v, check: bool) -> torch.device:
+    dev = _need_gpu(rowptr, col, u, v)
+    _csr(rowptr, col); _chk(_I32, u=u, v=v)
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"{who}: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    if u.dim() != 1 or u.shape != v.shape:
+        raise _lib.EpsError(f"{who}: u and v are two vectors of one length, got {tuple(u.shape)} and {tuple(v.shape)}")
+    if check and u.numel():
+        lo, hi = torch.stack([torch.minimum(u.min(), v.min()), torch.maximum(u.max(), v.max())]).tolist()
+        if lo < 0 or hi >= n_nodes:
+            raise _lib.EpsError(f"{who}: node ids must lie in [0, {n_nodes}), got [{lo}, {hi}]")
+    return dev
+
+
+def pair_cn_list_count(rowptr, col, n_nodes: int, u, v, check: bool = True) -> torch.Tensor:
+    """-> int32[B]: |N(u_b) & N(v_b)| on the stored pattern (eps_pair_cn_list_count): the counts ``pair_cn_list_fill``'s pointers
+    are the prefix of.  ``check=False``: a pair with an id outside the graph counts 0 (the kernel reads nothing for it)."""
+    n_nodes = int(n_nodes)
+    dev = _cn_list_args("pair_cn_list_count", rowptr, col, n_nodes, u, v, check)
+    count = torch.empty(u.numel(), dtype=_I32, device=dev)
+    if u.numel():
+        _call("eps_pair_cn_list_count", dev, rowptr, col, n_nodes, u, v, u.numel(), count, timed=("pair_cn_list_kernel<count>", u.numel()))
+    return count
+
+
+def pair_cn_list_fill(rowptr, col, n_nodes: int, u, v, ptr: torch.Tensor, out_w: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """Writes the common neighbours of pair b, ascending, to out_w[ptr[b] : ptr[b + 1]] (eps_pair_cn_list_fill) and returns
+    ``out_w``.  ``ptr`` (int64[B + 1]) is the exclusive prefix of ``pair_cn_list_count`` of the same pairs; with any other ``ptr``
+    nothing is stored at or past ptr[b + 1] or ptr[B], and the call raises EpsError (one read of the status word)."""
+    n_nodes = int(n_nodes)
+    dev = _cn_list_args("pair_cn_list_fill", rowptr, col, n_nodes, u, v, check)
+    _need_gpu(rowptr, ptr, out_w)
+    _chk(_I64, ptr=ptr); _chk(_I32, out_w=out_w)
+    if ptr.numel() != u.numel() + 1:
+        raise _lib.EpsError(f"pair_cn_list_fill: ptr must hold {u.numel() + 1} entries, got {ptr.numel()}")
+    if u.numel() == 0:
+        return out_w
+    m = int(ptr[-1].item())
+    if not 0 <= m <= out_w.numel() or m >= 1 << 31:
+        raise _lib.EpsError(f"pair_cn_list_fill: ptr ends at {m}: out_w holds {out_w.numel()} entries and a list fewer than 2^31")
+    status = torch.empty(1, dtype=_I32, device=dev)
+    _call("eps_pair_cn_list_fill", dev, rowptr, col, n_nodes, u, v, u.numel(), ptr, out_w, status, timed=("pair_cn_list_kernel<fill>", u.numel()))
+    if int(status.item()) != 0:
+        raise _lib.EpsError("pair_cn_list_fill: a segment of ptr is not as long as its pair's list of common neighbours (ptr is not "
+                            "the prefix of pair_cn_list_count of these pairs on this graph); nothing was stored outside the segments")
+    return out_w
+
+
+def pair_cn_list(rowptr, col, n_nodes: int, u, v, check: bool = True, count: Optional[torch.Tensor] = None):
+    """-> (ptr int64[B + 1], w int32[M]): the common STORED neighbours of every pair (u[b], v[b]) as CSR rows, w ascending per
+    pair -- so the lists of (u, v) and (v, u) are equal; stored values are ignored, u == v lists the whole row.  Count, prefix,
+    fill: two launches of one kernel and one read of M (which must stay below 2^31).  ``check``: the ids are verified on the host
+    first; ``check=False`` gives a pair with an id outside the graph an empty segment.  ``count``: the counts of exactly these
+    pairs when the caller has them already.  B == 0 and M == 0 launch nothing that dereferences a list."""
+    n_nodes = int(n_nodes)
+    if count is None:
+        count = pair_cn_list_count(rowptr, col, n_nodes, u, v, check)
+    else:
+        _cn_list_args("pair_cn_list", rowptr, col, n_nodes, u, v, check)
+        _chk(_I32, count=count)
+        if count.shape != u.shape:
+            raise _lib.EpsError("pair_cn_list: one count per pair")
+    dev = count.device
+    ptr = torch.zeros(u.numel() + 1, dtype=_I64, device=dev)
+    if u.numel():
+        torch.cumsum(count, 0, dtype=_I64, out=ptr[1:])
+    m = int(ptr[-1].item()) if u.numel() else 0
+    if m >= 1 << 31:
+        raise _lib.EpsError(f"pair_cn_list: {m} common neighbours in one list; a list holds fewer than 2^31 (split the pairs)")
+    w = torch.empty(m, dtype=_I32, device=dev)
+    if m:
+        pair_cn_list_fill(rowptr, col, n_nodes, u, v, ptr, w, check=False)
+    return ptr, w
+
+
+def cn_list_transpose(ptr: torch.Tensor, w: torch.Tensor, n_nodes: int, check: bool = True):
+    """-> (tptr int64[n_nodes + 1], tb int32[M]): the incidence of ``pair_cn_list`` by node -- the pairs that list w are
+    tb[tptr[w] : tptr[w + 1]], ascending in b (eps_cn_list_transpose: a stable radix sort, no atomics: a function of the input
+    alone).  ``check``: ptr ascends from 0 to M and every w lies in [0, n_nodes) (one read)."""
+    dev = _need_gpu(ptr, w)
+    _chk(_I64, ptr=ptr); _chk(_I32, w=w)
+    n_nodes, m, n_pairs = int(n_nodes), w.numel(), ptr.numel() - 1
+    if n_pairs < 0 or n_nodes < 0 or m >= 1 << 31:
+        raise _lib.EpsError(f"cn_list_transpose: ptr holds B + 1 entries, n_nodes >= 0 and M < 2^31 (got {ptr.numel()}, {n_nodes}, {m})")
+    if check and m:
+        facts = torch.stack([ptr[0], ptr[-1], (ptr[1:] - ptr[:-1]).min(), w.min().to(_I64), w.max().to(_I64)]).tolist()
+        if facts[0] != 0 or facts[1] != m or facts[2] < 0:
+            raise _lib.EpsError(f"cn_list_transpose: ptr must ascend from 0 to {m} (the entries of w), got {facts[0]} .. {facts[1]}")
+        if facts[3] < 0 or facts[4] >= n_nodes:
+            raise _lib.EpsError(f"cn_list_transpose: w must lie in [0, {n_nodes}), got [{facts[3]}, {facts[4]}]")
+    elif check and n_pairs >= 0 and ptr.numel() and int(ptr[-1].item()) != 0:
+        raise _lib.EpsError("cn_list_transpose: ptr names entries but w is empty")
+    tptr = torch.empty(n_nodes + 1, dtype=_I64, device=dev)
+    tb = torch.empty(m, dtype=_I32, device=dev)
+    ws, ws_ptr, ws_bytes = _aligned_ws(dev, int(_lib.load().eps_cn_list_transpose_workspace_bytes(m, n_nodes))) if m else (None, None, 0)
+    _call("eps_cn_list_transpose", dev, ptr, w, m, n_pairs, n_nodes, tptr, tb, ws_ptr, ws_bytes, timed=("cn_list_transpose", m))
+    return tptr, tb
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

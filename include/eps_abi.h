@@ -902,6 +902,37 @@ int eps_local_index_columns(const int64_t *rowptr, int64_t n_nodes, int64_t v_lo
                             const float *bar_or_null, int64_t capacity, int64_t *surv_pos, float *surv_score,
                             int64_t *n_surv, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Common-neighbour lists per pair, and their transpose (csrc/pair_cn_list.hip) --------------------------------------------
+ * What Neural Common Neighbor (Wang, Yang, Zhang) adds to a GNN link decoder: z_b = sum of h_w over w in N(u_b) & N(v_b).  The
+ * intersection kernels above only reduce over it; these hand it back as the CSR incidence C [n_pairs x n_rows] ("w is a common
+ * STORED neighbour of pair b": the pattern only, stored values are ignored), so that Z = C H and dH = C^T dZ are eps_spmm_csr
+ * with val == NULL -- sequential adds in entry order.  The graph: rowptr int64[n_rows + 1], col int32 strictly ascending per row.
+ *   eps_pair_cn_list_count: count[b] (int32) = |N(u_b) & N(v_b)|.  A pair with an id outside [0, n_rows) counts 0 and reads
+ *       nothing; u == v counts the whole row.
+ *   eps_pair_cn_list_fill:  ptr (int64[n_pairs + 1]) = the exclusive prefix of count (the caller's); the common neighbours of
+ *       pair b go to out_w[ptr[b] .. ptr[b + 1]), ASCENDING in w whichever row is the shorter one: the lists of (u, v) and (v, u)
+ *       are the same array.  Count and fill are one kernel template in two modes, so they agree on what a match is; and whatever
+ *       ptr holds, nothing is stored at or past ptr[b + 1], nor at or past ptr[n_pairs].  *status (DEVICE int32, cleared by the
+ *       call) becomes 1 when a segment's length is not its pair's count (it would overflow, or stays short): the list then means
+ *       nothing.  Plain stores only; the one atomic is the ticket that hands 64-pair chunks to the waves.
+ *   eps_pair_cn_list_limits (host only): the long-row entries staged in LDS per pass, and the ratio long / short from which a
+ *       long row beyond that capacity is searched in place -- the sizes at which the kernel changes its path.
+ *   eps_cn_list_transpose:  the same incidence by node.  m = ptr[n_pairs] (the caller knows it: it sized out_w); every out_w in
+ *       [0, n_rows).  tptr (int64[n_rows + 1]), tb (int32[m]): the pairs that list w are tb[tptr[w] .. tptr[w + 1]), ASCENDING in
+ *       b (a stable radix sort of (w, b) by w; tptr by search).  A function of the input alone: no atomics.  Whatever out_w
+ *       holds, every tb lies in [0, n_pairs) and every tptr in [0, m].  m == 0 clears tptr and reads nothing.  workspace:
+ *       eps_cn_list_transpose_workspace_bytes(m, n_rows) bytes, 256-byte aligned, contents arbitrary (m == 0: may be NULL).
+ * EPS_EINVAL before any launch: a negative size, n_rows / n_pairs / m >= 2^31, a null pointer that would be read or written.
+ * n_pairs == 0 launches nothing.  Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_pair_cn_list_limits(int32_t *cap, int32_t *inplace_ratio);
+int eps_pair_cn_list_count(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int32_t *u, const int32_t *v,
+                           int64_t n_pairs, int32_t *count, void *stream);
+int eps_pair_cn_list_fill(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int32_t *u, const int32_t *v,
+                          int64_t n_pairs, const int64_t *ptr, int32_t *out_w, int32_t *status, void *stream);
+int64_t eps_cn_list_transpose_workspace_bytes(int64_t m, int64_t n_rows);
+int eps_cn_list_transpose(const int64_t *ptr, const int32_t *out_w, int64_t m, int64_t n_pairs, int64_t n_rows, int64_t *tptr,
+                          int32_t *tb, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
