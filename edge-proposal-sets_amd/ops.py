@@ -104,6 +104,26 @@ def _csr(rowptr, col, val=None, sfx: str = "") -> None:
     _chk(_I64, **{"rowptr" + sfx: rowptr}); _chk(_I32, **{"col" + sfx: col}); _chk(_F32, **{"val" + sfx: val})
 
 
+def _chk_2d(who: str, **named) -> None:
+    """Every named tensor is a matrix (None passes).  Called BEFORE ``_need_gpu``, whose own refusal of a row-strided operand
+    that is not 2-D does not say which operand it was."""
+    for name, t in named.items():
+        if t is not None and t.dim() != 2:
+            raise _lib.EpsError(f"{who}: {name} must be 2-D, got {tuple(t.shape)}")
+
+
+def _chk_len(who: str, name: str, t: Optional[torch.Tensor], n: int, what: str) -> None:
+    """A vector operand holds exactly ``n`` entries (None passes): the kernels read ``n`` of them unchecked."""
+    if t is not None and t.numel() != n:
+        raise _lib.EpsError(f"{who}: {name} holds {t.numel()} entries, not {n} ({what})")
+
+
+def _chk_out(who: str, out: Optional[torch.Tensor], rows: int, cols: int) -> None:
+    """A caller's ``out`` has the result's shape (None passes): the kernels write rows x cols through its row stride."""
+    if out is not None and tuple(out.shape) != (rows, cols):
+        raise _lib.EpsError(f"{who}: out must be [{rows}, {cols}], got {tuple(out.shape)}")
+
+
 def device_info() -> Tuple[int, str]:
     lib = _lib.load()
     n = ctypes.c_int(0)
@@ -990,10 +1010,14 @@ def scan_screen(rowptr, col, revpos, fx32, cuts, bounds, n_nodes: int, columns: 
 
 
 def spmm_csr(rowptr, col, val, x: torch.Tensor, bias=None, relu=False, mean=False, out=None) -> torch.Tensor:
+    _chk_2d("spmm_csr", x=x, out=out)
     dev = _need_gpu(rowptr, col, val, x, bias, out, row_strided=(x, out))
     _csr(rowptr, col, val); _chk(_F32, x=x, bias=bias, out=out)
     n_rows = rowptr.numel() - 1
     f = x.shape[1]
+    _chk_len("spmm_csr", "val", val, col.numel(), "one value per stored entry of col")
+    _chk_len("spmm_csr", "bias", bias, f, "one per column of x")
+    _chk_out("spmm_csr", out, n_rows, f)
     if out is None:
         out = torch.empty((n_rows, f), dtype=_F32, device=dev)
     _call("eps_spmm_csr", dev, rowptr, col, val, n_rows, x, x.stride(0), f, bias, int(relu), int(mean), out, out.stride(0))
@@ -1098,6 +1122,7 @@ def cos_features_backward(rowptr, col, val, xhat: torch.Tensor, nrm: torch.Tenso
 def gcn_norm(rowptr, col, val) -> torch.Tensor:
     dev = _need_gpu(rowptr, col, val)
     _csr(rowptr, col, val)
+    _chk_len("gcn_norm", "val", val, col.numel(), "one value per stored entry of col")
     n_rows = rowptr.numel() - 1
     dis = torch.empty(n_rows, dtype=_F32, device=dev)
     out = torch.empty(col.numel(), dtype=_F32, device=dev)
@@ -1108,12 +1133,15 @@ def gcn_norm(rowptr, col, val) -> torch.Tensor:
 def gemm(a: torch.Tensor, b_nk: torch.Tensor, bias=None, relu=False, out=None, accumulate=False, lower_only=False) -> torch.Tensor:
     """C = act(a @ b_nk.T + bias (+ C)); b_nk is [N,K] (torch.nn.Linear layout).  ``lower_only``: the product is symmetric and
     only its 128 x 128 tiles on and below the diagonal are computed (the rest of ``out`` is left as it is)."""
+    _chk_2d("gemm", a=a, b=b_nk, out=out)
     dev = _need_gpu(a, b_nk, bias, out, row_strided=(a, b_nk, out))
     _chk(_F32, a=a, b=b_nk, bias=bias, out=out)
     m, k = a.shape
     n = b_nk.shape[0]
     if b_nk.shape[1] != k:
         raise _lib.EpsError(f"gemm: inner dims differ ({k} vs {b_nk.shape[1]})")
+    _chk_len("gemm", "bias", bias, n, "one per row of b")
+    _chk_out("gemm", out, m, n)
     if out is None:
         if accumulate:
             raise _lib.EpsError("gemm: accumulate needs out")
@@ -1167,14 +1195,11 @@ def mlp_decode(h: torch.Tensor, u, v, weights: Sequence[torch.Tensor], biases: S
                apply_sigmoid=True) -> torch.Tensor:
     dev = _need_gpu(h, u, v, *weights, *biases)
     _chk(_F32, h=h); _chk(_I32, u=u, v=v)
-    L = len(weights)
+    _chk_2d("mlp_decode", h=h)
+    if u.numel() != v.numel():
+        raise _lib.EpsError(f"mlp_decode: u and v differ in length ({u.numel()} vs {v.numel()})")
     hd = h.shape[1]
-    for i, (w, b) in enumerate(zip(weights, biases)):
-        _chk(_F32, **{f"w{i}": w, f"b{i}": b})
-        exp = (1 if i == L - 1 else hd, hd)
-        if tuple(w.shape) != exp:
-            raise _lib.EpsError(f"mlp_decode: layer {i} weight {tuple(w.shape)} != {exp} "
-                                f"(hidden width must equal the embedding width, last layer out=1)")
+    L = _decode_layers("mlp_decode", hd, weights, biases)
     n = u.numel()
     out = torch.empty(n, dtype=_F32, device=dev)
     wp = (ctypes.c_void_p * L)(*[w.data_ptr() for w in weights])

@@ -11,6 +11,7 @@ import scipy.sparse as ssp
 import torch
 
 import training_truth as tt
+from layer_truth import rows_graph as _rows_graph, symmetric_weights as _symmetric_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -100,33 +101,6 @@ U = 2.0 ** -24                                   # unit roundoff of float32: eve
 
 BOUNDARY_ROWS = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 2049, 4200]     # SP_FLIGHT = 32 rows, fetches of 64 entries, one hub
 WIDTHS = [1, 3, 58, 64, 256, 260, 314, 384]      # scalar kernel (1, 3, 58, 314), float4 kernel, and a second column pass (> 256)
-
-
-def _symmetric_weights(A, rng, lo=1, hi=4):
-    """Integer weights on a symmetric pattern, the same on both copies of an edge."""
-    up = ssp.triu(ssp.csr_matrix(A), 1).tocoo()
-    w = rng.integers(lo, hi + 1, up.nnz).astype(np.float64)
-    W = ssp.coo_matrix((w, (up.row, up.col)), shape=A.shape).tocsr()
-    return (W + W.T).tocsr()
-
-
-def _rows_graph(rng, lengths, n):
-    """Symmetric weighted graph in which node i < len(lengths) has EXACTLY lengths[i] stored entries: the special nodes'
-    neighbours are drawn from the other ('filler') nodes only, which are also joined among themselves
-    (like test_gpu_fuzz._graph_with_row_lengths, whose lengths are lower limits)."""
-    k = len(lengths)
-    rows, cols = [], []
-    for i, L in enumerate(lengths):
-        nb = rng.choice(np.arange(k, n), size=L, replace=False)
-        rows.append(np.full(L, i)); cols.append(nb)
-    extra = rng.integers(k, n, (2, 3 * n))
-    extra = extra[:, extra[0] != extra[1]]
-    r, c = np.concatenate(rows + [extra[0]]), np.concatenate(cols + [extra[1]])
-    P = ssp.coo_matrix((np.ones(len(r)), (r, c)), shape=(n, n)).tocsr()
-    P = ((P + P.T) > 0).astype(np.float64).tocsr()
-    A = _symmetric_weights(P, rng)
-    assert np.diff(A.indptr)[:k].tolist() == list(lengths)
-    return A
 
 
 def _spmm_graph(kind):
