@@ -151,6 +151,9 @@ SIGNATURES = {
     "eps_pair_cn_list_fill": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "eps_cn_list_transpose_workspace_bytes": (_i64, [_i64, _i64]),
     "eps_cn_list_transpose": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "eps_local_community_limits": (_int, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32)]),
+    "eps_local_community_degrees": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "eps_local_community_scores": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

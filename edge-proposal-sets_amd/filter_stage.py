@@ -23,8 +23,9 @@ import torch
 from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
-from .heuristics import (KATZ_BETA, LOCAL_INDICES, cosine_graph, katz_steps_bound, local_index_columns, node_weight_table,
-                         pair_scores_streamed, sigmoid_raw_cut, truncated_katz, truncated_katz_columns)
+from .heuristics import (KATZ_BETA, LOCAL_COMMUNITY_INDICES, LOCAL_INDICES, cosine_graph, katz_steps_bound, local_community_columns,
+                         local_community_pairs, local_index_columns, node_weight_table, pair_scores_streamed, sigmoid_raw_cut,
+                         truncated_katz, truncated_katz_columns)
 from .models import DECODE_PRECISIONS, build_model, default_model_configs
 
 
@@ -428,12 +429,39 @@ def local_index_blocks(args, data, blocks, bar=None):
         yield v_lo, v_hi, blk, blk.score
 
 
+def local_community_blocks(args, data, blocks):
+    """``scored_blocks`` of the local-community indices (``heuristics.LOCAL_COMMUNITY_INDICES``): candidates of the graph as it
+    is, each with its exact common-neighbour count out of the expansion (``_counted_block``).  The candidates with two or more
+    common neighbours are compacted, listed with their counts given (no counting launch: csrc/pair_cn_list.hip), their lists
+    run through the degree and the score kernels (csrc/local_community.hip) a budget of list entries at a time, and the scores
+    scattered back; the others get their closed form from the same device function (``heuristics.local_community_pairs``).
+    Every candidate's score is written: these scores are no sum of per-node weights, so there is no bound to screen with, and
+    a survivor-only path under the running bar is not built.  Graphs whose heaviest column outgrows the fused expansion's
+    scratch take list + pair-kernel counts, then the same kernels."""
+    g = data.adj_t
+    print(f'local-community filter ({args.model}): expansion with common-neighbour counts + list, degree and score kernels')
+    fused = candidates.hip_expand_available(g)
+    for v_lo, v_hi in blocks:
+        if not fused:
+            pairs, cn, _ = candidates.expand_block(g, v_lo, v_hi, want_cn=True)
+            if pairs.shape[1] == 0:
+                yield v_lo, v_hi, pairs, None
+                continue
+            yield v_lo, v_hi, pairs, local_community_pairs(g, pairs[0].to(torch.int32).contiguous(), pairs[1].to(torch.int32).contiguous(),
+                                                           cn.to(torch.int32), args.model)
+            continue
+        blk = _counted_block(g, v_lo, v_hi, count_free=False)
+        blk.score = local_community_columns(g, v_lo, v_hi, blk, args.model)
+        yield v_lo, v_hi, blk, blk.score
+
+
 def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = None, bar=None):
     """(v_lo, v_hi, pairs, scores) per column block.  Heuristic filters whose scoring graph IS the candidate graph
     (AA: filter.py:122-126; CN 'simple': :116-121 with models.py:536-542) come out of the fused expansion already
     scored; RA scores on the train-only graph (filter.py:130-141) and GNN filters decode the block's pairs; the cosine
     filters score the cosine graph (``cosine_blocks``); the local indices score (count, degrees) per candidate
-    (``local_index_blocks``)."""
+    (``local_index_blocks``), the local-community indices the links among every candidate's common neighbours
+    (``local_community_blocks``)."""
     g = data.adj_t
     col_hi = g.n_rows if col_hi is None else col_hi
     blocks = [(max(lo, col_lo), min(hi, col_hi)) for lo, hi in candidates.column_blocks(g) if lo < col_hi and hi > col_lo]
@@ -445,6 +473,9 @@ def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = No
         return
     if args.model in LOCAL_INDICES and candidates.hip_expand_available(g, scored=False):
         yield from local_index_blocks(args, data, blocks, bar)
+        return
+    if args.model in LOCAL_COMMUNITY_INDICES and candidates.hip_expand_available(g, scored=False):
+        yield from local_community_blocks(args, data, blocks)
         return
     node_w = fused_node_weights(args, g, ra_graph) if candidates.hip_expand_available(g) else None
     if node_w is not None and not candidates.fused_scores_fit(g, node_w):
@@ -562,7 +593,7 @@ def run(args) -> str:
             print('dense common-neighbour product (A A^T on the f32 MFMA)')
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) + LOCAL_INDICES and scan.scan_plausible(data.adj_t):
+    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) + LOCAL_INDICES + LOCAL_COMMUNITY_INDICES and scan.scan_plausible(data.adj_t):
         # (the hubs-first copy first: the symmetry check of scan_available then reads the COPY's reverse positions -- the table
         #  the scan needs anyway -- instead of building one for the graph as labelled, 3-5 ms on a ppa-sized graph)
         scan.scan_graph(data.adj_t, build=True)

@@ -9,6 +9,9 @@ types:
 * ``common_neighbors(adj, edges)``                   <- models.py:536-542 ('simple')
 * ``local_index(adj, edges, index)``                 <- the degree-normalised local indices of Zhou, Lu, Zhang (``LOCAL_INDICES``)
 * ``local_index_columns``                            <- the same for a filter's column-major candidate blocks
+* ``local_community(adj, edges, index)``             <- the local-community indices of Cannistraci, Alanis-Lobato, Ravasi
+                                                        (``LOCAL_COMMUNITY_INDICES``: car, cpa, caa, cra, cjc)
+* ``local_community_columns``                        <- the same for a filter's column-major candidate blocks
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
 * ``truncated_katz_columns``                        <- the truncated series for a filter's column-major candidate blocks
 * ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
@@ -181,6 +184,101 @@ def local_index_columns(g: CSRGraph, v_lo: int, v_hi: int, block, index: str, ba
         raise EpsError(f"local index '{index}': one of {', '.join(LOCAL_INDICES)}")
     return ops.local_index_columns(g.rowptr, g.n_rows, v_lo, v_hi, block.colptr, block.cand_u, block.cn, index,
                                    counts=block.counts, bar=bar, capacity=capacity, check=check)
+
+
+# ------------------------------------------------------------------------------------------- local-community indices
+# Cannistraci, Alanis-Lobato, Ravasi (Sci. Rep. 3:1613, 2013): a pair is scored by the links AMONG its common neighbours.  With L
+# the ascending list of the common STORED neighbours of u and v (stored values are ignored), c = |L|, a, b, d_w the stored
+# entries of rows u, v, w, gamma(w) = the members of L other than w stored in row w, G = sum gamma, CAR = c G / 2:
+#   car CAR   cpa ((a-c) + CAR)((b-c) + CAR)   caa sum gamma(w)/log2 d_w   cra sum gamma(w)/d_w   cjc CAR/(a+b-c), 0/0 -> 0.
+# Lists from csrc/pair_cn_list.hip, gamma and the scores from csrc/local_community.hip.
+LOCAL_COMMUNITY_INDICES = tuple(ops.LOCAL_COMMUNITY_INDEX)
+LOCAL_COMMUNITY_BUDGET = 1 << 26     # common neighbours listed per piece (4 bytes each for the list, 4 for gamma)
+
+
+def _budget_cuts(count: torch.Tensor, budget: int):
+    """[(lo, hi)]: the pairs cut on the prefix of ``count`` into the longest runs whose counts fit ``budget`` -- a single pair
+    beyond it is a run of its own (``models.cn_embed_sum`` cuts the same way)."""
+    b = count.numel()
+    cum = torch.cumsum(count, 0, dtype=torch.int64)
+    if b == 0 or int(cum[-1].item()) <= budget:
+        return [(0, b)]
+    cum, cuts, s, base = cum.cpu(), [0], 0, 0
+    while s < b:
+        s = max(s + 1, int(torch.searchsorted(cum, base + budget, right=True)))
+        cuts.append(s)
+        base = int(cum[s - 1])
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+def local_community_pairs(g: CSRGraph, u: torch.Tensor, v: torch.Tensor, count: torch.Tensor, index: str) -> torch.Tensor:
+    """float32 scores of the pairs (u[p], v[p]) (int32 device vectors, ids inside the graph) whose numbers of common stored
+    neighbours are ``count`` (int32).  Pairs with fewer than two are not listed: no link can lie among their common neighbours,
+    their closed form comes from the same device function.  The others are listed LOCAL_COMMUNITY_BUDGET entries at a time
+    (cut on the counts' prefix; a pair's score does not depend on where the cuts fall), then degrees, then scores."""
+    if index not in ops.LOCAL_COMMUNITY_INDEX:
+        raise EpsError(f"local-community index '{index}': one of {', '.join(LOCAL_COMMUNITY_INDICES)}")
+    out = torch.empty(u.numel(), dtype=torch.float32, device=u.device)
+    if u.numel() == 0:
+        return out
+    listed = count >= 2
+    pos, rest = torch.nonzero(listed).squeeze(1), torch.nonzero(~listed).squeeze(1)
+    if rest.numel():
+        ptr = torch.zeros(rest.numel() + 1, dtype=torch.int64, device=u.device)
+        torch.cumsum(count[rest], 0, dtype=torch.int64, out=ptr[1:])
+        out[rest] = ops.local_community_scores(g.rowptr, g.n_rows, u[rest], v[rest], ptr, None, None, index)
+    if pos.numel():
+        lu, lv, lc = u[pos], v[pos], count[pos]
+        for lo, hi in _budget_cuts(lc, int(LOCAL_COMMUNITY_BUDGET)):
+            pu, pv = lu[lo:hi], lv[lo:hi]
+            ptr, w = ops.pair_cn_list(g.rowptr, g.col, g.n_rows, pu, pv, check=False, count=lc[lo:hi])
+            gamma = ops.local_community_degrees(g.rowptr, g.col, g.n_rows, ptr, w, check=False)
+            out[pos[lo:hi]] = ops.local_community_scores(g.rowptr, g.n_rows, pu, pv, ptr, w, gamma, index, check=False)
+    return out
+
+
+def local_community(A, edge_index, index: str) -> torch.Tensor:
+    """The local-community index ``index`` (one of ``LOCAL_COMMUNITY_INDICES``) of the pairs ``edge_index`` [2,E]: same argument
+    forms and the same kind of tensor as ``local_index`` (float32 on the adjacency's device).  Counts from
+    eps_pair_cn_list_count, then ``local_community_pairs``: score(u, v) == score(v, u) bit for bit, and equal to what
+    ``local_community_columns`` gives the same pair."""
+    if index not in ops.LOCAL_COMMUNITY_INDEX:
+        raise EpsError(f"local-community index '{index}': one of {', '.join(LOCAL_COMMUNITY_INDICES)}")
+    g = _as_graph(A)
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    count = ops.pair_cn_list_count(g.rowptr, g.col, g.n_rows, u, v, check=False)
+    return local_community_pairs(g, u, v, count, index)
+
+
+def local_community_columns(g: CSRGraph, v_lo: int, v_hi: int, block, index: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``local_community`` for a FILTER's access pattern: ``block`` is a ``candidates.ColumnBlock`` of the columns [v_lo, v_hi)
+    whose ``cn`` holds the common-neighbour count of every slot (int32, or the float32 unit-weight score of
+    ``ops.expand_unit``).  -> float32 scores per slot, into ``out`` when given; the padding slots of a count-free block are not
+    written (-inf without ``out``)."""
+    n = block.cand_u.numel()
+    if out is not None and (out.dtype != torch.float32 or out.numel() != n):
+        raise EpsError(f"local_community_columns: out must hold one float32 per slot of the block ({n})")
+    if block.padded:
+        score = out if out is not None else torch.full((n,), float("-inf"), dtype=torch.float32, device=block.cand_u.device)
+        # the counted entries of every column, by the counts (what a padding slot holds is not defined for every expansion)
+        counts = block.counts.to(torch.int64)
+        first = torch.cumsum(counts, 0) - counts
+        seg = torch.repeat_interleave(torch.arange(counts.numel(), device=counts.device), counts)
+        pos = block.colptr[seg] + (torch.arange(seg.numel(), device=counts.device) - first[seg])
+        u, cn = block.cand_u[pos], block.cn[pos]
+        v = (seg + int(v_lo)).to(torch.int32)
+    else:
+        u, cn = block.cand_u, block.cn
+        cols = torch.arange(int(v_lo), int(v_hi), dtype=torch.int32, device=block.cand_u.device)
+        v = torch.repeat_interleave(cols, block.colptr[1:] - block.colptr[:-1], output_size=n)
+    got = local_community_pairs(g, u.contiguous(), v, cn.to(torch.int32), index)
+    if not block.padded and out is None:
+        return got
+    if block.padded:
+        score[pos] = got
+    else:
+        score = out.copy_(got)
+    return score
 
 
 # ------------------------------------------------------------------------------------------- cosine common neighbours

@@ -888,7 +888,7 @@ class CommonNeighborsPredictor(torch.nn.Module):
     def __init__(self, emb, in_channels, hidden_channels, out_channels, num_layers, dropout, model_type='weighted'):
         super().__init__()
         assert model_type in ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz',
-                              *heuristics.LOCAL_INDICES]
+                              *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]
         self.type = model_type
         if self.type == 'mlpcos':
             self.mlp = MLP(in_channels, hidden_channels, out_channels, num_layers, dropout)
@@ -935,6 +935,8 @@ class CommonNeighborsPredictor(torch.nn.Module):
             return heuristics.common_neighbors(adj, edges)                   # models.py:536-542
         if self.type in heuristics.LOCAL_INDICES:                            # (no parameters, no sigmoid: the index itself)
             return heuristics.local_index(adj, edges, self.type)
+        if self.type in heuristics.LOCAL_COMMUNITY_INDICES:                  # (likewise: car, cpa, caa, cra, cjc)
+            return heuristics.local_community(adj, edges, self.type)
         if self.type == 'adamic':
             # models.py:547-554: weight 1/log(rowsum(adj) + 1e-6) per common neighbour (edge values of the two
             # rows are NOT used: only the indices of the product), no inf guard, then sigmoid
@@ -954,9 +956,9 @@ class CommonNeighborsPredictor(torch.nn.Module):
 # ----------------------------------------------------------------------------------- factory
 DECODE_MAX_HIDDEN = 256          # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 256
 _MODELS = ['sage', 'sage2', 'gcn', 'dea', 'dea_512', 'mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb',
-           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, 'ncn', 'ncn_sage']
+           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage']
 _NCN = {'ncn': 'gcn', 'ncn_sage': 'sage'}       # Neural Common Neighbor: name -> the encoder whose arguments and defaults it takes
-_HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES]
+_HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]
 
 
 def build_model(args, data, device):
@@ -1059,7 +1061,7 @@ def _defaults_for(dataset: str, model: str) -> dict:
                     put(hidden_channels=512)
         if model in ('mlpcos', 'simplecos'):
             put(num_layers=2, hidden_channels=256, dropout=0.5, lr=0.005, epochs=200)
-        if model in ('simple', 'simplecos') + heuristics.LOCAL_INDICES:
+        if model in ('simple', 'simplecos') + heuristics.LOCAL_INDICES + heuristics.LOCAL_COMMUNITY_INDICES:
             put(batch_size=1024)
             if model == 'simplecos':
                 put(use_feature=True)
@@ -1096,7 +1098,7 @@ def default_model_configs(args):
     for attr in _KEYS:
         if getattr(args, attr) is None:
             setattr(args, attr, defaults[attr])
-    if args.model in ['adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz', "ensemble_gcn_sage", *heuristics.LOCAL_INDICES]:
+    if args.model in ['adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz', "ensemble_gcn_sage", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]:
         args.use_feature = False
         args.use_learnable_embedding = False
     if args.model == 'simplecos' and args.dataset != "email":

@@ -1683,6 +1683,106 @@ def cn_list_transpose(ptr: torch.Tensor, w: torch.Tensor, n_nodes: int, check: b
     return tptr, tb
 
 
+LOCAL_COMMUNITY_INDEX = {"car": 0, "cpa": 1, "caa": 2, "cra": 3, "cjc": 4}     # csrc/local_community.hip: name -> code
+
+
+def _local_community_code(index) -> int:
+    if isinstance(index, str):
+        if index not in LOCAL_COMMUNITY_INDEX:
+            raise _lib.EpsError(f"local-community index '{index}': one of {', '.join(LOCAL_COMMUNITY_INDEX)}")
+        return LOCAL_COMMUNITY_INDEX[index]
+    return int(index)          # (the library refuses a code outside the table)
+
+
+def local_community_limits() -> Tuple[int, int, int]:
+    """(list length up to which the ordered pairs of a list are dealt over the lanes, list entries staged in LDS per pass, ratio
+    row / staged entries from which a row is searched in place) of the local-community degree kernel: the sizes at which it
+    changes its path (host-only query)."""
+    short, cap, ratio = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.load().eps_local_community_limits(ctypes.byref(short), ctypes.byref(cap), ctypes.byref(ratio)),
+               "eps_local_community_limits")
+    return short.value, cap.value, ratio.value
+
+
+def _list_args(who: str, ptr, w, **same_length) -> int:
+    """The checks every consumer of a (ptr, w) list makes before a launch: ptr holds B + 1 entries, M < 2^31, and the arrays
+    named in ``same_length`` hold one entry per entry of w.  -> B."""
+    _chk(_I64, ptr=ptr); _chk(_I32, w=w)
+    if ptr.dim() != 1 or ptr.numel() < 1 or w.dim() != 1:
+        raise _lib.EpsError(f"{who}: ptr holds B + 1 entries and w is a vector, got {tuple(ptr.shape)} and {tuple(w.shape)}")
+    if w.numel() >= 1 << 31:
+        raise _lib.EpsError(f"{who}: {w.numel()} entries in one list; a list holds fewer than 2^31 (split the pairs)")
+    for name, t in same_length.items():
+        _chk_len(who, name, t, w.numel(), "one per entry of w")
+    return ptr.numel() - 1
+
+
+def local_community_degrees(rowptr, col, n_nodes: int, ptr, w, check: bool = True, out: Optional[torch.Tensor] = None,
+                            stats: Optional[dict] = None) -> torch.Tensor:
+    """-> int32[M]: gamma[i] = the number of stored entries of row w[i] that occur in the segment of ``ptr`` holding i, other than
+    w[i] itself (eps_local_community_degrees) -- for the lists of ``pair_cn_list`` the local-community degree of every common
+    neighbour; any strictly ascending segments of node ids are taken.  A segment that does not ascend, or holds an id outside
+    the graph, gets zeros (nothing is read for it) and raises EpsError -- with ``stats`` (a dict) given its ``status`` is stored
+    there instead.  ``check``: ptr ascends from 0 to M, verified on the host first (one read); ``check=False`` is for lists that
+    have just come out of the list kernel.  ``out``: an int32[M] tensor to write into."""
+    n_nodes = int(n_nodes)
+    _csr(rowptr, col); _chk(_I32, out=out)              # (dtypes and lengths first: they are refused the same on any device)
+    n_pairs = _list_args("local_community_degrees", ptr, w, out=out)
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"local_community_degrees: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    dev = _need_gpu(rowptr, col, ptr, w, out)
+    m = w.numel()
+    if check:
+        facts = torch.stack([ptr[0], ptr[-1], (ptr[1:] - ptr[:-1]).min() if n_pairs else ptr[0] * 0]).tolist()
+        if facts[0] != 0 or facts[1] != m or facts[2] < 0:
+            raise _lib.EpsError(f"local_community_degrees: ptr must ascend from 0 to {m} (the entries of w), got {facts[0]} .. {facts[1]}")
+    gamma = out if out is not None else torch.empty(m, dtype=_I32, device=dev)
+    if n_pairs == 0 or m == 0:
+        if stats is not None:
+            stats["status"] = 0
+        return gamma
+    status = torch.empty(1, dtype=_I32, device=dev)
+    _call("eps_local_community_degrees", dev, rowptr, col, n_nodes, ptr, w, n_pairs, gamma, status,
+          timed=("local_community_degrees_kernel", m))
+    if stats is not None:
+        stats["status"] = int(status.item())
+    elif check and int(status.item()) != 0:
+        raise _lib.EpsError("local_community_degrees: a segment does not ascend strictly or holds an id outside the graph (its "
+                            "entries got 0; nothing was read for them)")
+    return gamma
+
+
+def local_community_scores(rowptr, n_nodes: int, u, v, ptr, w, gamma, index, check: bool = True) -> torch.Tensor:
+    """-> float32[B]: the local-community index ``index`` (a name of ``LOCAL_COMMUNITY_INDEX`` or its code) of the pairs
+    (u[b], v[b]) whose common neighbours are w[ptr[b] : ptr[b + 1]] with the degrees ``gamma`` of ``local_community_degrees``
+    (eps_local_community_scores): float64 on the integers, the sums in a fixed association of the list positions, one rounding.
+    ``w`` and ``gamma`` both None: nothing is listed, ``ptr`` is the prefix of the counts alone and every pair gets its closed
+    form without links among its common neighbours (what the pairs with fewer than two have).  An id outside the graph scores
+    NaN.  ``check``: ptr ends at M, the entries of w, verified on the host first (one read; the kernel reads no entry at or
+    past ptr[B]); ``check=False`` is for lists that have just come out of the list kernel."""
+    n_nodes = int(n_nodes)
+    _chk(_I64, rowptr=rowptr, ptr=ptr); _chk(_I32, u=u, v=v, w=w, gamma=gamma)
+    if (w is None) != (gamma is None):
+        raise _lib.EpsError("local_community_scores: w and gamma come together (both None: closed forms)")
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"local_community_scores: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    if u.dim() != 1 or u.shape != v.shape:
+        raise _lib.EpsError(f"local_community_scores: u and v are two vectors of one length, got {tuple(u.shape)} and {tuple(v.shape)}")
+    if ptr.numel() != u.numel() + 1:
+        raise _lib.EpsError(f"local_community_scores: ptr must hold {u.numel() + 1} entries, got {ptr.numel()}")
+    if w is not None:
+        _list_args("local_community_scores", ptr, w, gamma=gamma)
+        if check and int(ptr[-1].item()) != w.numel():
+            raise _lib.EpsError(f"local_community_scores: ptr must end at {w.numel()} (the entries of w), got {int(ptr[-1].item())}")
+    code = _local_community_code(index)
+    dev = _need_gpu(rowptr, u, v, ptr, w, gamma)
+    out = torch.empty(u.numel(), dtype=_F32, device=dev)
+    if u.numel():
+        _call("eps_local_community_scores", dev, rowptr, n_nodes, u, v, ptr, w, gamma, u.numel(), code, out,
+              timed=("local_community_scores_kernel", u.numel()))
+    return out
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

@@ -933,6 +933,45 @@ int64_t eps_cn_list_transpose_workspace_bytes(int64_t m, int64_t n_rows);
 int eps_cn_list_transpose(const int64_t *ptr, const int32_t *out_w, int64_t m, int64_t n_pairs, int64_t n_rows, int64_t *tptr,
                           int32_t *tb, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Local-community indices (csrc/local_community.hip) ------------------------------------------------------------------------
+ * The local-community paradigm of Cannistraci, Alanis-Lobato and Ravasi (Sci. Rep. 3:1613, 2013): a pair is scored by the links
+ * AMONG its common neighbours.  For a pair (u, v): L = the ascending list of the common STORED neighbours of rows u and v (the
+ * lists above; stored values are ignored), c = |L|, a and b the stored entries of rows u and v, d_w those of row w,
+ *   gamma(w) = |{z in L : z != w, z stored in row w}| for w in L  (the local-community degree; a self loop never counts)
+ *   G = the sum of gamma over L, an integer (twice the links among the common neighbours on a symmetric pattern; symmetry is
+ *       not required), LCL = G / 2, exact in float64.
+ *   index 0 car  c LCL                                       1 cpa  ((a - c) + CAR) ((b - c) + CAR)
+ *         2 caa  sum over L of gamma(w) / log2(d_w)          3 cra  sum over L of gamma(w) / d_w
+ *         4 cjc  CAR / (a + b - c), 0.0 over a zero denominator
+ * A term with gamma(w) == 0 is skipped (d_w = 1 never divides by log2 1).  float64 arithmetic on the integers, ONE rounding to
+ * float32.  The two sums run over the list positions in a fixed association that depends on the list's length alone: blocks of
+ * 64 consecutive entries, inside a block the balanced pairwise tree x[i] + x[i ^ 1], then ^ 2, ^ 4 ... (places past the end
+ * hold 0.0), the blocks added first to last.  A score is therefore a function of (list, gamma, degrees, index): score(u, v) ==
+ * score(v, u) bit for bit, whatever launch, batch position or route formed it.  c < 2 gives G = 0: car, caa, cra, cjc are 0
+ * and cpa is (a - c)(b - c).
+ *   eps_local_community_degrees: ptr (int64[n_pairs + 1]) and w (int32[ptr[n_pairs]]) are ANY strictly ascending segments of
+ *       node ids (common-neighbour lists are the use; the kernel does not require it).  gamma[i] (int32) = the number of stored
+ *       entries of row w[i] that occur in the segment holding i, other than w[i] itself.  A segment that does not ascend
+ *       strictly, holds an id outside [0, n_rows), or whose bounds do not ascend inside [0, ptr[n_pairs]] sets *status (DEVICE
+ *       int32, cleared by the call) to 1; its entries get gamma 0 and no row is read for them; other segments are unaffected.
+ *       Nothing is read or stored at or past ptr[n_pairs].  Plain stores only; the one global atomic is the ticket that hands
+ *       chunks of up to 64 segments to the waves; the counts are integers, so no result depends on an order or a launch shape.
+ *   eps_local_community_limits (host only): the list length up to which the ordered pairs of a list are dealt over the lanes,
+ *       the list entries staged in LDS per pass, and the ratio row / staged entries from which a row is searched in place --
+ *       the sizes at which the kernel changes its path.
+ *   eps_local_community_scores: score[p] (float32) of the pairs (u[p], v[p]): c from ptr, a and b from rowptr, G and the sums
+ *       from (w, gamma, rowptr).  w == NULL and gamma == NULL together: nothing is listed, ptr carries the counts alone and
+ *       every pair gets its closed form with G = 0 (the pairs with c < 2 of a batch).  An id of u, v outside [0, n_rows) scores
+ *       NaN; an id of w outside it contributes no term and reads nothing.
+ * EPS_EINVAL before any launch: a negative size, n_rows >= 2^31, index outside [0, 5), a null pointer that would be read or
+ * written, w and gamma not both given or both NULL.  n_pairs == 0 launches nothing.  Additions: no existing call changes,
+ * EPS_ABI_VERSION stays. */
+int eps_local_community_limits(int32_t *short_max, int32_t *cap, int32_t *inplace_ratio);
+int eps_local_community_degrees(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *ptr, const int32_t *w,
+                                int64_t n_pairs, int32_t *gamma, int32_t *status, void *stream);
+int eps_local_community_scores(const int64_t *rowptr, int64_t n_rows, const int32_t *u, const int32_t *v, const int64_t *ptr,
+                               const int32_t *w, const int32_t *gamma, int64_t n_pairs, int32_t index, float *score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
