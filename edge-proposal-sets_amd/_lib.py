@@ -120,6 +120,10 @@ SIGNATURES = {
     "eps_radix_sort_by_u": (_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "eps_radix_sort_rows": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "eps_rescore_runs_dev": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "eps_rows_by_score_max_run": (_i32, []),
+    "eps_rows_by_score_window": (_i32, []),
+    "eps_rows_by_score_workspace_bytes": (_i64, [_i64]),
+    "eps_rows_by_score": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "eps_pack_keys": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "eps_unpack_keys": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "eps_two_path_counts": (_int, [_vp, _vp, _i64, _vp, _vp]),

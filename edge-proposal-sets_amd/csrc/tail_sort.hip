@@ -17,6 +17,7 @@
 //     output transform (the [2, K] proposal tensor rank.py reads + scores) are folded into the first and last phase;
 //   * the state block is left zeroed by the kernels that consume it (no memset launches).
 #include "eps_common.h"
+#include "score_buckets.h"
 #include <string.h>
 
 #define TS_T 1024               // threads per workgroup (16 waves)
@@ -26,35 +27,7 @@
 #define TS_MAXG 256             // workgroups of a sort at most (one per CU)
 #define TS_MAXPASS 16
 
-// ---- order-preserving score buckets --------------------------------------------------------------------------------------
-#define TS_MB 8                                   // mantissa bits of the bucket minifloat
-#define TS_BINS ((32 - TS_MB + 1) << TS_MB)       // 6400
-
-__device__ __forceinline__ uint32_t ts_ordered(float f)
-{
-    f = f + 0.0f;
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ts_unordered(uint32_t o)
-{
-    const uint32_t b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __builtin_bit_cast(float, b);
-}
-// bucket of a distance d >= 0 (in steps of the ordered bit pattern): d itself below 2^MB, else exponent | top MB mantissa bits
-__device__ __forceinline__ uint32_t ts_bucket(uint32_t d)
-{
-    if (d < (1u << TS_MB)) return d;
-    const int e = 31 - __clz((int)d);                       // >= MB
-    return ((uint32_t)(e - TS_MB + 1) << TS_MB) | ((d >> (e - TS_MB)) & ((1u << TS_MB) - 1u));
-}
-// smallest distance that falls into bucket b
-__device__ __forceinline__ uint32_t ts_bucket_floor(uint32_t b)
-{
-    if (b < (1u << TS_MB)) return b;
-    const uint32_t e1 = b >> TS_MB, m = b & ((1u << TS_MB) - 1u);
-    return ((1u << TS_MB) | m) << (e1 - 1u);
-}
+// ---- order-preserving score buckets (score_buckets.h: shared with rows_by_score.hip) --------------------------------------
 
 struct ts_sel_state {           // per (device, stream); zero at allocation, left zeroed by eps_score_pick_compact
     uint32_t hist[TS_BINS];

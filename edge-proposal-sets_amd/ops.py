@@ -1909,6 +1909,38 @@ def select_rows_pairs(sel_keys: torch.Tensor, sel_vals: torch.Tensor, k: int, id
     return _topk_rows(sel_keys, sel_vals, sel_keys.numel(), k, id_bits, perm, as_pairs=True)
 
 
+def rows_by_score_limits() -> Tuple[int, int]:
+    """(longest run of equal scores ``rows_by_score`` orders itself, sorted pairs per workgroup of its expansion)."""
+    lib = _lib.load()
+    return int(lib.eps_rows_by_score_max_run()), int(lib.eps_rows_by_score_window())
+
+
+def rows_by_score(keys_by_u: torch.Tensor, vals: torch.Tensor, bar: torch.Tensor, k2: int, k: int, id_bits: int = 32,
+                  perm: Optional[torch.Tensor] = None):
+    """The end of a one-rank step from ONE score sort of the re-scored pairs (eps_rows_by_score): ``keys_by_u`` / ``vals`` as
+    ``rescore_runs`` leaves them (u << 32 | v, any order), ``bar`` a 1-element float32 device tensor.  -> (pairs int64 [2, cap] as
+    (u; v), scores float32 [cap], sorted_keys, sorted_vals, n_sel, cut, flag) with cap = min(k, 2 len), all device tensors, no host
+    read: cut / n_sel are what ``score_hist`` + ``score_pick_compact`` give with above = base = bar and k = k2; the first n_sel
+    sorted pairs (v << 32 | u, score descending) are that selection; the first min(k, 2 n_sel) columns of ``pairs`` / ``scores`` are
+    its rows in the declared order -- unless ``flag`` (int64[1]) is 1: a run of equal scores was longer than
+    ``rows_by_score_limits()[0]`` and the rows are void (``select_rows_pairs`` on the selection orders them)."""
+    dev = _need_gpu(keys_by_u, vals, bar, perm)
+    _chk(_I64, keys_by_u=keys_by_u, perm=perm); _chk(_F32, vals=vals, bar=bar)
+    n, k = keys_by_u.numel(), int(k)
+    _chk_len("rows_by_score", "vals", vals, n, "one score per pair")
+    cap = min(k, 2 * n)
+    pairs = torch.empty((2, cap), dtype=_I64, device=dev)
+    scores = torch.empty(cap, dtype=_F32, device=dev)
+    sorted_k = torch.empty(n, dtype=_I64, device=dev)
+    sorted_v = torch.empty(n, dtype=_F32, device=dev)
+    cut = torch.empty(1, dtype=_F32, device=dev)
+    words = torch.empty(2, dtype=_I64, device=dev)               # n_sel, flag
+    _, wsp, wsb = _aligned_ws(dev, _lib.load().eps_rows_by_score_workspace_bytes(n))
+    _call("eps_rows_by_score", dev, keys_by_u, vals, n, bar, int(k2), k, int(id_bits), perm, sorted_k, sorted_v, cut, words.data_ptr(),
+          words.data_ptr() + 8, pairs, cap, scores, wsp, wsb, timed=("select_rows", n))
+    return pairs, scores, sorted_k, sorted_v, words[0:1], cut, words[1:2]
+
+
 def select_topk(keys: torch.Tensor, vals: torch.Tensor, k: int, id_bits: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
     """The k best DIRECTED rows (score descending, key ascending) of a list of unordered survivors of ``filter_scan``
     (key = v << 32 | u, u < v; no -1 slots): (keys int64, scores float32), sorted.  eps_select_topk_cut (radix select of the

@@ -864,7 +864,9 @@ def select_topk_torch(keys: torch.Tensor, vals: torch.Tensor, k: int) -> Tuple[t
 
 
 TAIL_DEVICE = True           # one rank, under a bar: the step's selections come from score-bucket histograms (csrc/tail_sort.hip)
-TAIL_SORT = "library"        # ... and its two orderings from the library sorts ("library": sizes from the host, two host reads per step) or
+TAIL_SORT = "score"          # ... and its two orderings from the library sorts ("library": sizes from the host, two host reads per step),
+                             # the same with cut and rows from ONE score sort of the re-scored pairs ("score": ops.rows_by_score; lists
+                             # with a run of equal scores too long for it, and Screen.exact ones, end as "library" does) or
                              # from the one-launch cooperative radix sorts with device-side sizes ("radix": one host read, but slower on
                              # MI355X -- see scan_topk)
 EXACT_SCREENING = True       # uniform weights whose screening sums are exact skip the re-scoring (Screen.exact; tests switch it off to compare)
@@ -1138,11 +1140,15 @@ def _device_tail(g: CSRGraph, screen: Screen, res: ops.Survivors, bar: torch.Ten
     """One rank under a bar: pre-filter, exact re-scoring (not for Screen.exact) and cut from score-bucket histograms
     (csrc/tail_sort.hip).  Threshold and cut are the lower edges of the buckets that hold the k2-th best screening / exact score
     (<= the exact order statistics: a few pairs more are re-scored and sorted, the K rows are the same; _Retry.verdict checks both).
-    -> (status table, selected keys, values, cut, pairs re-scored, rows).  TAIL_SORT = "library": library sorts, sized from the
-    host (host read 1: the pre-filter's count), rows = None -- faster on MI355X than "radix": a grid-wide hand-over inside a kernel
-    costs ~50 us there, a kernel boundary ~10 (profiles/r06/sort_probe.txt); "radix": cooperative sorts sized on the device, the
-    rows ordered here too, ONE host read.  Tied scores at the threshold beyond the room: the tail (not the launch) runs again."""
-    library = TAIL_SORT == "library"
+    -> (status table, selected keys, values, cut, pairs re-scored, rows, rows path).  TAIL_SORT = "library": library sorts, sized
+    from the host (host read 1: the pre-filter's count), rows = None -- faster on MI355X than "radix": a grid-wide hand-over inside a
+    kernel costs ~50 us there, a kernel boundary ~10 (profiles/r06/sort_probe.txt); "score": the same up to the re-scoring, then ONE
+    score sort of the re-scored pairs gives the cut, the selection (sorted) AND the rows (ops.rows_by_score), before the status read
+    -- unless the screen is exact or a run of equal scores was too long for it (a flag word behind the status row): rows = None,
+    rows path "library"; "radix": cooperative sorts sized on the device, the rows ordered here too, ONE host read.  Tied scores at
+    the threshold beyond the room: the tail (not the launch) runs again."""
+    library = TAIL_SORT != "radix"
+    by_score = TAIL_SORT == "score" and not screen.exact
     room = min(res.capacity, 2 * k2 + (1 << 16))
     while True:
         ops.score_hist(res.key, res.val, res.count_ptr, bar)
@@ -1164,16 +1170,23 @@ def _device_tail(g: CSRGraph, screen: Screen, res: ops.Survivors, bar: torch.Ten
         else:
             x_keys = ops.radix_sort_by_u(c_keys, n_valid, bits, RESCORE_V_BLOCK)
             x_vals = ops.rescore_runs_dev(g.rowptr, g.col, screen.fixw, g.n_rows, x_keys, n_valid)
+        if by_score:
+            r_pairs, r_scores, sel_k, sel_v, n_sel, cut, flag = ops.rows_by_score(x_keys, x_vals, bar, k2, k, bits, perm)
+            row = (res.rec[1:2], res.rec[4:5], n_sel, cut, res.status, pre_thr, res.walked_slots, bar)
+            st, (void,) = _unpack_status(_pack_status(*row, extra=(flag,)).tolist(), extra=1)               # the host read of the step
+            rows = None if void else (r_pairs, r_scores, min(k, 2 * st.n_sel))
+            return [st], sel_k, sel_v, cut, nv, rows, "library" if void else "score"
         ops.score_hist(x_keys, x_vals, count, bar, above=bar)
         sel_k, sel_v, n_sel, cut, _ = ops.score_pick_compact(x_keys, x_vals, count, bar, k2, above=bar, swap_halves=not screen.exact,
                                                              room=sel_room)
         row = (res.rec[1:2], res.rec[4:5], n_sel, cut, res.status, pre_thr, res.walked_slots, bar)
         if library:
-            return [_unpack_status(_pack_status(*row).tolist())], sel_k, sel_v, cut, 0 if screen.exact else nv, None   # the host read of the step
+            return ([_unpack_status(_pack_status(*row).tolist())], sel_k, sel_v, cut, 0 if screen.exact else nv, None,     # the host read of the step
+                    "library")
         r_pairs, r_scores, n_rows = ops.radix_sort_rows(sel_k, sel_v, n_sel, k, bits, perm)
         st, (nv, n_out) = _unpack_status(_pack_status(*row, extra=(n_valid, n_rows)).tolist(), extra=2)      # the host read
         if nv <= room:
-            return [st], sel_k, sel_v, cut, 0 if screen.exact else nv, (r_pairs, r_scores, n_out)
+            return [st], sel_k, sel_v, cut, 0 if screen.exact else nv, (r_pairs, r_scores, n_out), "radix"
         room = min(res.capacity, nv)
 
 
@@ -1329,8 +1342,8 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
     under a bar with skipped heads) -> one rank under a bar: the device tail (_device_tail); else the pre-filter and exact
     re-scoring of this rank's list (_prefilter) and the job-wide cut with the status table (_cut_from_histograms, _cut_from_scores,
     _cut_local) -> the verdict on the status table (_Retry.verdict), which VERIFIES the step -- else the launch repeats with what was
-    learnt -> the rows (_ordered_rows) and the stats (_step_stats).  Host reads per step on one rank: two (the pre-filter's count,
-    the status table); TAIL_SORT = "radix": one."""
+    learnt -> the rows (_ordered_rows, unless the tail ordered them already) and the stats (_step_stats; ``rows_path``: which
+    ordering gave the rows).  Host reads per step on one rank: two (the pre-filter's count, the status table); TAIL_SORT = "radix": one."""
     if relabel and scan_plausible(g):
         scan_graph(g, build=True)        # (first: the symmetry check below then reads the copy's table, the one the scan needs)
     if not scan_available(g):
@@ -1382,11 +1395,12 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
                       capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap, sketch=ht is not None and sketch_for(ht.budget))
         state.launches += 1
         rows = deal = None
+        rows_path = "library"
         if screen is not None:
             params = screen.lower_params(max_degree(g), None if ht is None else ht.d_used) + (4e-6,)
         if (TAIL_DEVICE and not _sharded(world) and screen is not None and g.val is None and bar is not None and not state.rescore_all
                 and k2 + (1 << 16) < (1 << 30)):
-            table, sel_k, sel_v, cut, n_rescored, rows = _device_tail(g, screen, res, bar, k, k2, params, bits, perm)
+            table, sel_k, sel_v, cut, n_rescored, rows, rows_path = _device_tail(g, screen, res, bar, k, k2, params, bits, perm)
         else:
             keys, vals, pre_thr, room = res.key, res.val, None, 0
             if screen is not None:
@@ -1420,4 +1434,5 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
                             _ordered_rows(sel_k, sel_v, [t.n_sel for t in table], deal, k, bits, perm, rank, world, rows_on))
     if stats is not None:
         _step_stats(stats, g, screen, fixw, table, ht, capacity, state, n_rescored, shard, bar, rank, world)
+        stats["rows_path"] = rows_path                        # which ordering gave the rows: "score", "library" or "radix" (_device_tail)
     return pairs, scores

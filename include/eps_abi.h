@@ -727,6 +727,27 @@ int eps_radix_sort_rows(const int64_t *sel_keys, const float *sel_vals, int64_t 
                         int64_t *n_rows_out_or_null, void *workspace, int64_t workspace_bytes, void *state, void *stream);
 int eps_rescore_runs_dev(const int64_t *rowptr, const int32_t *col, const int64_t *fixw, int64_t n_nodes, const int64_t *keys,
                          int64_t n_max, const int64_t *n_dev, float *out, void *stream);
+/* ---- the K rows from one score sort of the re-scored pairs (csrc/rows_by_score.hip) ----------------------------------------------
+ * The end of a one-rank step in one call, nothing read back: keys_by_u / vals are the n re-scored pairs as eps_rescore_runs leaves
+ * them (u << 32 | v in the scanned graph's labels, any order).
+ *   sorted_keys / sorted_vals (n entries): the list sorted by score, descending (order among equal scores unspecified), keys as
+ *          v << 32 | u -- the first *n_sel of them are the selection eps_select_topk_rows[_pairs] takes;
+ *   *cut, *n_sel (DEVICE): what eps_score_hist + eps_score_pick_compact give for this list with above = base = bar and k = k2 (live:
+ *          score > *bar and > -inf; *cut = lower edge of the bucket of the k2-th best live score, -inf with fewer; *n_sel = live
+ *          entries >= *cut) -- the same bits;
+ *   out_pairs / out_vals: the first min(k, 2 *n_sel) rows of the declared order (score descending, then (v, u) ascending in the
+ *          caller's labels: ids go through perm_or_null first) as out_pairs[i] = u, out_pairs[pairs_ld + i] = v, out_vals[i];
+ *          pairs_ld >= min(k, 2 n).  Rows of equal score are ordered inside the kernel in runs of up to eps_rows_by_score_max_run()
+ *          pairs; a longer run sets *flag (DEVICE int64: 0 / 1) and the rows of that call are void -- order sorted_keys[:*n_sel]
+ *          with eps_select_topk_rows_pairs instead.  eps_rows_by_score_window(): sorted pairs per workgroup of that kernel.
+ *          id_bits (1..32) is what the caller would hand eps_select_topk_rows_pairs: ids are compared as whole 32-bit words here.
+ * workspace: eps_rows_by_score_workspace_bytes(n) bytes, 256-byte aligned. */
+int32_t eps_rows_by_score_max_run(void);
+int32_t eps_rows_by_score_window(void);
+int64_t eps_rows_by_score_workspace_bytes(int64_t n);
+int eps_rows_by_score(const int64_t *keys_by_u, const float *vals, int64_t n, const float *bar, int64_t k2, int64_t k, int32_t id_bits,
+                      const int64_t *perm_or_null, int64_t *sorted_keys, float *sorted_vals, float *cut, int64_t *n_sel, int64_t *flag,
+                      int64_t *out_pairs, int64_t pairs_ld, float *out_vals, void *workspace, int64_t workspace_bytes, void *stream);
 int eps_pack_keys(const float *score, const int64_t *ids_or_null, int64_t id_base, int64_t n,
                   int64_t *keys, void *stream);
 int eps_unpack_keys(const int64_t *keys, int64_t n, float *score_or_null, int64_t *id_or_null,
