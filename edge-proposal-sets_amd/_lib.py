@@ -158,6 +158,11 @@ SIGNATURES = {
     "eps_local_community_limits": (_int, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32)]),
     "eps_local_community_degrees": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "eps_local_community_scores": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "eps_sketch_limits": (_int, [_c.POINTER(_i32), _c.POINTER(_i32)]),
+    "eps_sketch_own": (_int, [_i64, _i64, _vp, _vp, _vp]),
+    "eps_sketch_propagate_workspace_bytes": (_i64, [_i64]),
+    "eps_sketch_propagate": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]),
+    "eps_sketch_pair_stats": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _i64, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

@@ -62,6 +62,8 @@ def make_parser():
                              'pair and the rows follow the declared tie rule; only MEMBERSHIP can differ from the fp32 run: a pair '
                              'whose bf16 rank falls beyond the kept ones is lost.  Single-process runs only.  Default fp32: the bare '
                              'command is unchanged')
+    parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2],
+                        help='--model buddy: hops of the subgraph sketches and of the node-feature propagation (default 2)')
     parser.add_argument('--decode_guard', type=float, default=None, metavar='G',
                         help=f'with --decode_precision bf16: the screening pass keeps ceil(G * ceil(K/2)) pairs, G >= 1 '
                              f'(default {DECODE_GUARD_DEFAULT:g}: see DESIGN 4.5d)')
@@ -124,13 +126,15 @@ def check_per_node_args(args) -> None:
 
 
 NCN_MODELS = ('ncn', 'ncn_sage')
+ONE_PROCESS_MODELS = NCN_MODELS + ('buddy',)
 
 
 def check_ncn_args(args) -> None:
-    """--model ncn / ncn_sage scores through the model's forward in one process: a sharded run is refused before the dataset is
-    read (the row-sharded embedding forward has not been tried with the common-neighbour sums on top)."""
+    """--model ncn / ncn_sage / buddy scores through the model's forward in one process: a sharded run is refused before the
+    dataset is read (the row-sharded embedding forward has not been tried with the common-neighbour sums or the sketch features
+    on top)."""
     import os
-    if args.model in NCN_MODELS and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if args.model in ONE_PROCESS_MODELS and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError(f"--model {args.model} runs in one process: sharded filter runs are not supported for it")
 
 

@@ -272,6 +272,36 @@ class CSRGraph:
                                           self.n_cols)
         return self._cache["tag"]
 
+    def sketches(self, hops: int = 2):
+        """(hll uint8 [hops, N, 256], mh uint32 [hops, N, 128], card float64 [hops, N]): the HyperLogLog and MinHash sketches of
+        every node's neighbourhoods S_1 = N(v) and S_2 = S_1 with the S_1 of its neighbours (hop k at index k - 1; the stored
+        pattern of a square graph, values are not read), and the cardinality estimates of those rows (csrc/sketch.hip,
+        heuristics.sketch_cardinality).  Own sketches -> hop 1 (the union over the row) -> hop 2 (the same from hop 1, keeping
+        the node's own row); the own table is let go once hop 1 stands.  Cached per graph."""
+        hops = int(hops)
+        if hops not in (1, 2):
+            raise ValueError(f"sketches: hops {hops}: 1 or 2")
+        key = ("sketch", hops)
+        if key not in self._cache:
+            from . import heuristics, ops
+            if self.n_rows != self.n_cols:
+                raise ValueError(f"sketches: neighbourhoods need a square adjacency, got {self.n_rows} x {self.n_cols}")
+            n = self.n_rows
+            hll = torch.empty((hops, n, ops.SKETCH_REGS), dtype=torch.uint8, device=self.device)
+            mh = torch.empty((hops, n, ops.SKETCH_WORDS), dtype=torch.uint32, device=self.device)
+            own = ops.sketch_own(0, n, self.device)
+            ops.sketch_propagate(self.rowptr, self.col, n, own[0], own[1], keep_own=False, out=(hll[0], mh[0]))
+            del own
+            if hops == 2:
+                ops.sketch_propagate(self.rowptr, self.col, n, hll[0], mh[0], keep_own=True, check=False, out=(hll[1], mh[1]))
+            # a row's own statistics are those of the pair (v, v): the max of a row with itself
+            ids = torch.arange(n, dtype=torch.int32, device=self.device)
+            s, z, _ = ops.sketch_pair_stats(hll, mh, n, ids, ids, check=False)
+            d = torch.arange(hops, device=self.device)
+            card = heuristics.sketch_cardinality(s[:, d, d], z[:, d, d]).t().contiguous()
+            self._cache[key] = (hll, mh, card)
+        return self._cache[key]
+
     def with_edges(self, extra_edges: torch.Tensor, dataset_is_collab: bool) -> "CSRGraph":
         """``add_edges`` for a graph that is resident already.  ``self`` must be the symmetrised graph of the base edge list
         ALONE -- what ``add_edges(dataset, edge_index, edge_weight, <no edges>, N)`` returns; the result equals

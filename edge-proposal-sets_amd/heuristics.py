@@ -281,6 +281,73 @@ def local_community_columns(g: CSRGraph, v_lo: int, v_hi: int, block, index: str
     return score
 
 
+# ------------------------------------------------------------------------------------------- subgraph sketches
+SKETCH_CHUNK = 1 << 22            # pairs per eps_sketch_pair_stats call of the helpers below (their float64 temporaries are per call)
+
+
+def sketch_cardinality(S: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+    """The HyperLogLog estimate (float64, any shape) from the integer statistics of a 256-register row: S = the sum of
+    2^(33 - M_r), Z = the registers that are 0.  E = alpha m^2 2^33 / S with m = 256, alpha = 0.7213 / (1 + 1.079 / m); when
+    E <= 2.5 m and Z > 0, linear counting m ln(m / Z) instead.  The empty set (Z = 256) gives 0."""
+    m = 256.0
+    alpha = 0.7213 / (1.0 + 1.079 / m)
+    e = (alpha * m * m * 8589934592.0) / S.to(torch.float64)
+    lin = m * torch.log(m / Z.clamp(min=1).to(torch.float64))
+    return torch.where((e <= 2.5 * m) & (Z > 0), lin, e)
+
+
+def sketch_intersections(S: torch.Tensor, Z: torch.Tensor, match: torch.Tensor) -> torch.Tensor:
+    """I = (match / 128) E (float64): the estimated size of the intersection of two sketched sets from the statistics of their
+    union row (``sketch_cardinality``) and the count of equal MinHash words."""
+    return (match.to(torch.float64) / 128.0) * sketch_cardinality(S, Z)
+
+
+def sketch_feature_formulas(I: torch.Tensor, cu: torch.Tensor, cv: torch.Tensor) -> torch.Tensor:
+    """The structural features of BUDDY from the intersections I (float64 [B, K, K]) and the two endpoints' cardinalities
+    (float64 [K, B] each) -> float32 [B, 5] (K = 2) or [B, 2] (K = 1): log1p(clamp_min(., 0)) of
+        a11 = I11                                       nodes at distance (1, 1)
+        a12 = (I12 - I11) + (I21 - I11)                 ... (1, 2) and (2, 1)
+        a22 = (I22 - (I12 + I21)) + I11                 ... (2, 2)
+        b1  = (C1(u) - I12) + (C1(v) - I21)             within one hop of one endpoint only
+        b2  = (((C2(u) - C1(u)) - I22) + I12) + (((C2(v) - C1(v)) - I22) + I21)
+    (K = 1: I11 and (C1(u) - I11) + (C1(v) - I11)), each in exactly this association: swapping u and v gives the same bits."""
+    k = I.shape[1]
+    i11 = I[:, 0, 0]
+    if k == 1:
+        f = torch.stack([i11, (cu[0] - i11) + (cv[0] - i11)], 1)
+    else:
+        i12, i21, i22 = I[:, 0, 1], I[:, 1, 0], I[:, 1, 1]
+        f = torch.stack([i11,
+                         (i12 - i11) + (i21 - i11),
+                         (i22 - (i12 + i21)) + i11,
+                         (cu[0] - i12) + (cv[0] - i21),
+                         (((cu[1] - cu[0]) - i22) + i12) + (((cv[1] - cv[0]) - i22) + i21)], 1)
+    return torch.log1p(f.clamp_min(0.0)).to(torch.float32)
+
+
+def _sketch_pieces(A, edge_index, hops: int):
+    g = _as_graph(A)
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    hll, mh, card = g.sketches(hops)
+    for lo in range(0, max(u.numel(), 1), SKETCH_CHUNK):
+        pu, pv = u[lo:lo + SKETCH_CHUNK], v[lo:lo + SKETCH_CHUNK]
+        yield sketch_intersections(*ops.sketch_pair_stats(hll, mh, g.n_rows, pu, pv, check=False)), card, pu, pv
+
+
+def sketch_pair_counts(A, edge_index, hops: int = 2) -> torch.Tensor:
+    """-> float64 [E, hops, hops] on the adjacency's device: I[b, i - 1, j - 1] estimates |S_i(u_b) & S_j(v_b)| from the graph's
+    sketches (``CSRGraph.sketches``; csrc/sketch.hip) -- I[:, 0, 0] estimates the common-neighbour count.  Same argument forms
+    as ``local_index``.  I(u, v)[i, j] == I(v, u)[j, i] bit for bit."""
+    return torch.cat([I for I, _, _, _ in _sketch_pieces(A, edge_index, hops)])
+
+
+@torch.no_grad()
+def sketch_features(A, edge_index, hops: int = 2) -> torch.Tensor:
+    """-> float32 [E, 5] (hops 2) or [E, 2] (hops 1): the structural features ``sketch_feature_formulas`` of the pairs
+    ``edge_index`` [2,E] from the graph's sketches.  A constant of the graph: it carries no gradient."""
+    return torch.cat([sketch_feature_formulas(I, card[:, pu.long()], card[:, pv.long()]) for I, card, pu, pv in _sketch_pieces(A, edge_index, hops)])
+
+
 # ------------------------------------------------------------------------------------------- cosine common neighbours
 def cosine_graph(adj: CSRGraph, x: torch.Tensor) -> CSRGraph:
     """The graph whose value at stored entry (u, w) is cos(x'_u, x'_w), x' = x + (adj @ x) / (rowsum(adj) + 1e-6)

@@ -15,7 +15,8 @@ What differs from the reference on purpose: ``LinkGNN`` computes the node embedd
 GNN for each batch (models.py:505 called from filter.py:118).  Results are identical in eval mode.
 
 Beyond the reference: ``NCNPredictor`` / ``NCNLinkGNN`` (``--model ncn | ncn_sage``), Neural Common Neighbor on the
-common-neighbour lists of csrc/pair_cn_list.hip (``cn_embed_sum``).
+common-neighbour lists of csrc/pair_cn_list.hip (``cn_embed_sum``); ``BuddyPredictor`` / ``BuddyLinkModel`` (``--model buddy``),
+BUDDY on the subgraph sketches of csrc/sketch.hip (``heuristics.sketch_features``).
 """
 from __future__ import annotations
 
@@ -614,6 +615,114 @@ class NCNLinkGNN(LinkGNN):
             return out
 
 
+# ----------------------------------------------------------------------------------- BUDDY (subgraph sketches)
+SKETCH_FEATURES = {1: 2, 2: 5}   # hops -> structural features per pair (heuristics.sketch_feature_formulas)
+
+
+class BuddyPredictor(torch.nn.Module):
+    """The decoder of BUDDY (Chamberlain et al., ICLR 2023) in the mould of ``NCNPredictor``: the pair's Hadamard product and its
+    structural features from the subgraph sketches each get a first layer,
+        t = relu(xij_lin(h_u * h_v)) + relu(xs_lin(F(u, v))),
+    then dropout, relu(lin(t)) + dropout for each of lins[:-1], and sigmoid(lins[-1](t)).  ``lins`` holds num_layers - 1 layers
+    (num_layers >= 2).  The dense layers run on torch in training and in eval."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, num_features=5):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError(f"BuddyPredictor: num_layers {num_layers}: the two first layers and an output layer make at least 2")
+        self.xij_lin = torch.nn.Linear(in_channels, hidden_channels)
+        self.xs_lin = torch.nn.Linear(num_features, hidden_channels)
+        self.lins = torch.nn.ModuleList()
+        for _ in range(num_layers - 2):
+            self.lins.append(torch.nn.Linear(hidden_channels, hidden_channels))
+        self.lins.append(torch.nn.Linear(hidden_channels, out_channels))
+        self.dropout = dropout
+
+    def reset_parameters(self):
+        self.xij_lin.reset_parameters()
+        self.xs_lin.reset_parameters()
+        for lin in self.lins:
+            lin.reset_parameters()
+
+    def forward(self, x_i: torch.Tensor, x_j: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+        drop = self.training and torch.is_grad_enabled()
+        t = F.relu(self.xij_lin(x_i * x_j)) + F.relu(self.xs_lin(f))
+        t = F.dropout(t, p=self.dropout, training=drop)
+        for lin in self.lins[:-1]:
+            t = F.dropout(F.relu(lin(t)), p=self.dropout, training=drop)
+        return torch.sigmoid(self.lins[-1](t))
+
+
+class BuddyLinkModel(_CachedEmbeddings, torch.nn.Module):
+    """BUDDY: node side h = feat_lin(dropout([xin || A^ xin || ... || A^hops xin])) with A^ = ``adj.gcn_normalized()`` and xin =
+    [emb.weight || x] (embedding first, as in LinkGNN) -- fixed propagation, one Linear((hops + 1) in_dim, hidden); pair side
+    the structural features of ``heuristics.sketch_features`` (estimated from the graph's HyperLogLog / MinHash sketches at a
+    cost that depends on no degree; constants of the graph, no gradient); decoder ``BuddyPredictor``.  The sketches are those of
+    the ``adj`` passed in (no target-edge masking).  NOT a LinkGNN: the filter scores it block by block through ``forward``.
+
+    Eval: ``h`` is cached per (parameters, x, adjacency) like LinkGNN's, the sketches per adjacency on the graph; the dense
+    layers run on tiles of NCN_EVAL_TILE pairs, the last one padded, so a pair's score does not depend on the batch it arrives
+    in.  The features of (u, v) and (v, u) are the same bits and h_u * h_v commutes: score(u, v) == score(v, u) bit for bit."""
+
+    def __init__(self, emb, in_dim, hidden, num_layers, dropout, hops=2):
+        super().__init__()
+        if hops not in SKETCH_FEATURES:
+            raise ValueError(f"BuddyLinkModel: hops {hops}: 1 or 2")
+        self.emb = emb
+        self.hops = int(hops)
+        self.dropout = dropout
+        self.feat_lin = torch.nn.Linear((self.hops + 1) * in_dim, hidden)
+        self.linkpred = BuddyPredictor(hidden, hidden, 1, num_layers, dropout, SKETCH_FEATURES[self.hops])
+        self._h_key = None
+        self._h = None
+
+    def reset_parameters(self):
+        self.feat_lin.reset_parameters()
+        self.linkpred.reset_parameters()
+        if self.emb is not None:
+            self.emb.reset_parameters()
+        self._h_key = None
+
+    _node_input = LinkGNN._node_input
+
+    def _node_forward(self, xin, adj):
+        gn = adj.gcn_normalized()
+        xs = [xin.contiguous()]
+        for _ in range(self.hops):
+            xs.append(ops.spmm_csr(gn.rowptr, gn.col, gn.val, xs[-1]))
+        return ops.gemm(_pad4(torch.cat(xs, 1)), self.feat_lin.weight.detach().contiguous(), bias=self.feat_lin.bias.detach())
+
+    def forward(self, x, edges, adj):
+        if torch.is_grad_enabled() and self.training:
+            if x is None:
+                x = self.emb.weight
+            elif self.emb is not None:
+                x = torch.cat([self.emb.weight, x], dim=1)
+            _check_rows(x, adj, "BuddyLinkModel")
+            _check_trainable(adj, "BuddyLinkModel", values=True)
+            gn = adj.gcn_normalized()
+            xs = [x]
+            for _ in range(self.hops):
+                xs.append(_SpMM.apply(xs[-1], gn, False))
+            h = self.feat_lin(F.dropout(torch.cat(xs, 1), p=self.dropout, training=True))
+            f = heuristics.sketch_features(adj, edges, self.hops)
+            return self.linkpred(h[edges[0]], h[edges[1]], f)
+        with torch.no_grad():
+            h = self.embeddings(x, adj)
+            f_all = heuristics.sketch_features(adj, edges, self.hops)     # (once per call: it checks the ids before anything gathers with them)
+            e = edges.to(device=h.device, dtype=torch.int64)
+            n, tile = e.shape[1], int(NCN_EVAL_TILE)
+            out = torch.empty((n, self.linkpred.lins[-1].out_features), dtype=torch.float32, device=h.device)
+            for s in range(0, n, tile):
+                u, v = e[0, s:s + tile], e[1, s:s + tile]
+                xi, xj, f = h[u], h[v], f_all[s:s + tile]
+                if u.numel() < tile:
+                    pad = (0, 0, 0, tile - u.numel())
+                    xi, xj, f = F.pad(xi, pad), F.pad(xj, pad), F.pad(f, pad)
+                out[s:s + tile] = self.linkpred(xi, xj, f)[:u.numel()]
+            return out
+
+
 # ----------------------------------------------------------------------------------- DEA_GNN_JK
 def fold_batchnorm(weight: torch.Tensor, bias: torch.Tensor, bn: torch.nn.BatchNorm1d):
     """(W', b') such that x W'^T + b' == bn(x W^T + b) with bn in eval mode (running statistics):
@@ -956,8 +1065,9 @@ class CommonNeighborsPredictor(torch.nn.Module):
 # ----------------------------------------------------------------------------------- factory
 DECODE_MAX_HIDDEN = 256          # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 256
 _MODELS = ['sage', 'sage2', 'gcn', 'dea', 'dea_512', 'mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb',
-           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage']
+           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage', 'buddy']
 _NCN = {'ncn': 'gcn', 'ncn_sage': 'sage'}       # Neural Common Neighbor: name -> the encoder whose arguments and defaults it takes
+_ENCODER_ROW = {**_NCN, 'buddy': 'gcn'}         # models beyond the reference: name -> the row of the defaults table they take
 _HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]
 
 
@@ -974,7 +1084,7 @@ def build_model(args, data, device):
                              "them) or --use_learnable_embedding True")
     if args.model in ('dea', 'dea_512'):
         return _build_dea(args, data, device)
-    if args.model in _NCN:
+    if args.model in _ENCODER_ROW:
         # (before anything is allocated: ppa has no defaults, and the decoder's two first layers and its output layer make 2)
         if args.hidden_channels is None:
             raise UnsupportedModelConfig(f"--model {args.model} needs --hidden_channels (there is no "
@@ -1005,6 +1115,12 @@ def build_model(args, data, device):
         gnn = gnn_cls(input_dim, args.hidden_channels, args.hidden_channels, args.num_layers, args.dropout).to(device)
         linkpred = NCNPredictor(args.hidden_channels, args.hidden_channels, 1, args.num_layers, args.dropout).to(device)
         return NCNLinkGNN(emb, gnn, linkpred)
+    if args.model == 'buddy':
+        if input_dim == 0:
+            raise UnsupportedModelConfig("--model buddy needs node features: pass --use_feature True (on a dataset that has them) or "
+                                         "--use_learnable_embedding True")
+        return BuddyLinkModel(emb, input_dim, args.hidden_channels, args.num_layers, args.dropout,
+                              hops=int(getattr(args, "sketch_hops", 2) or 2)).to(device)
     if args.model in _HEURISTICS:
         return CommonNeighborsPredictor(emb, input_dim, args.hidden_channels, args.hidden_channels, args.num_layers,
                                         args.dropout, model_type=args.model).to(device)
@@ -1039,13 +1155,13 @@ def _build_dea(args, data, device):
 
 
 # per-dataset defaults, one row per (dataset group, model group): restates the table of models.py:673-790
-_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage', 'ncn', 'ncn_sage')
+_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage', 'ncn', 'ncn_sage', 'buddy')
 _KEYS = ["num_layers", "hidden_channels", "dropout", "batch_size", "lr", "epochs", "use_feature",
          "use_learnable_embedding"]
 
 
 def _defaults_for(dataset: str, model: str) -> dict:
-    model = _NCN.get(model, model)       # (ncn / ncn_sage: the row of their encoder)
+    model = _ENCODER_ROW.get(model, model)       # (ncn / ncn_sage / buddy: the row of their encoder)
     d = dict.fromkeys(_KEYS)
 
     def put(**kw):

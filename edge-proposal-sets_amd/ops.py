@@ -1783,6 +1783,101 @@ def local_community_scores(rowptr, n_nodes: int, u, v, ptr, w, gamma, index, che
     return out
 
 
+SKETCH_REGS, SKETCH_WORDS = 256, 128     # csrc/sketch.hip: HyperLogLog registers (bytes) and MinHash words (uint32) per sketch
+_U8, _U32 = torch.uint8, torch.uint32
+
+
+def sketch_limits() -> Tuple[int, int]:
+    """(row length above which ``sketch_propagate`` reduces a row piecewise on several waves, pairs per wave of
+    ``sketch_pair_stats``): the sizes at which the sketch kernels change their path (host-only query)."""
+    chunk, ppw = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.load().eps_sketch_limits(ctypes.byref(chunk), ctypes.byref(ppw)), "eps_sketch_limits")
+    return chunk.value, ppw.value
+
+
+def sketch_own(first_id: int, n: int, device):
+    """-> (hll uint8 [n, 256], mh uint32 [n, 128]): the own sketches of the ids first_id .. first_id + n - 1 (eps_sketch_own)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.EpsError("edge-proposal-sets_amd ops run on the MI355X only: sketch_own got a CPU device (there is no CPU fallback)")
+    first_id, n = int(first_id), int(n)
+    if n < 0 or first_id < 0 or first_id + n > 1 << 31:
+        raise _lib.EpsError(f"sketch_own: ids must lie in [0, 2^31), got [{first_id}, {first_id + n})")
+    hll = torch.empty((n, SKETCH_REGS), dtype=_U8, device=dev)
+    mh = torch.empty((n, SKETCH_WORDS), dtype=_U32, device=dev)
+    if n:
+        _call("eps_sketch_own", hll.device, first_id, n, hll, mh, timed=("sketch_own_kernel", n))
+    return hll, mh
+
+
+def _sketch_tables(who: str, hll, mh, lead: Tuple[int, ...]) -> None:
+    _chk(_U8, hll=hll); _chk(_U32, mh=mh)
+    if tuple(hll.shape) != (*lead, SKETCH_REGS) or tuple(mh.shape) != (*lead, SKETCH_WORDS):
+        raise _lib.EpsError(f"{who}: hll must be {[*lead, SKETCH_REGS]} and mh {[*lead, SKETCH_WORDS]}, got {list(hll.shape)} and {list(mh.shape)}")
+
+
+def sketch_propagate(rowptr, col, n: int, hll_in, mh_in, keep_own: bool, check: bool = True, out=None):
+    """-> (hll uint8 [n, 256], mh uint32 [n, 128]): out[v] = the union of in[w] over the stored entries w of row v of the square
+    graph (byte-wise max of the registers, word-wise min of the words), with ``keep_own`` also of in[v] (eps_sketch_propagate).
+    ``check``: every entry of col lies in [0, n) (one read); ``check=False``: an entry outside is skipped by the kernel.
+    ``out``: (hll, mh) tensors of the result's shapes to write into (slices of a [K, n, .] table); they must not be the inputs."""
+    n = int(n)
+    dev = _need_gpu(rowptr, col, hll_in, mh_in, *(out or ()))
+    _csr(rowptr, col)
+    _sketch_tables("sketch_propagate", hll_in, mh_in, (n,))
+    if rowptr.numel() != n + 1:
+        raise _lib.EpsError(f"sketch_propagate: rowptr must hold {n + 1} entries, got {rowptr.numel()}")
+    nnz = col.numel()
+    if check and nnz:
+        lo, hi, end = torch.stack([col.min().to(_I64), col.max().to(_I64), rowptr[-1]]).tolist()
+        if lo < 0 or hi >= n or end != nnz:
+            raise _lib.EpsError(f"sketch_propagate: col must hold rowptr[-1] = {end} entries in [0, {n}), got {nnz} in [{lo}, {hi}]")
+    if out is not None:
+        hll, mh = out
+        _sketch_tables("sketch_propagate (out)", hll, mh, (n,))
+    else:
+        hll = torch.empty((n, SKETCH_REGS), dtype=_U8, device=dev)
+        mh = torch.empty((n, SKETCH_WORDS), dtype=_U32, device=dev)
+    if n == 0:
+        return hll, mh
+    ws_bytes = int(_lib.load().eps_sketch_propagate_workspace_bytes(nnz))
+    ws = torch.empty(ws_bytes + 256, dtype=_U8, device=dev) if nnz else None
+    ws_ptr = ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256) if nnz else None
+    _call("eps_sketch_propagate", dev, rowptr, col, n, nnz, hll_in, mh_in, hll, mh, 1 if keep_own else 0, ws_ptr, ws_bytes,
+          timed=("sketch_propagate", nnz))
+    return hll, mh
+
+
+def sketch_pair_stats(hll, mh, n: int, u, v, check: bool = True):
+    """-> (S int64, Z int32, match int32), each [B, K, K]: for hll uint8 [K, n, 256] and mh uint32 [K, n, 128] (hop k at index
+    k - 1) and M = the byte-wise max of hll[i][u_b] and hll[j][v_b]: S = the sum of 2^(33 - M_r), Z = the registers with M_r == 0,
+    match = the equal words of mh[i][u_b] and mh[j][v_b] (eps_sketch_pair_stats: one packed int64 per slot, unpacked here).
+    ``check``: the ids are verified on the host first; ``check=False`` gives a pair with an id outside [0, n) -1 in every slot of
+    all three."""
+    n = int(n)
+    dev = _need_gpu(hll, mh, u, v)
+    _chk(_I32, u=u, v=v)
+    if hll.dim() != 3 or hll.shape[0] not in (1, 2):
+        raise _lib.EpsError(f"sketch_pair_stats: hll must be [K, n, {SKETCH_REGS}] with K 1 or 2, got {list(hll.shape)}")
+    k = int(hll.shape[0])
+    _sketch_tables("sketch_pair_stats", hll, mh, (k, n))
+    if u.dim() != 1 or u.shape != v.shape:
+        raise _lib.EpsError(f"sketch_pair_stats: u and v are two vectors of one length, got {tuple(u.shape)} and {tuple(v.shape)}")
+    b = u.numel()
+    if check and b:
+        lo, hi = torch.stack([torch.minimum(u.min(), v.min()), torch.maximum(u.max(), v.max())]).tolist()
+        if lo < 0 or hi >= n:
+            raise _lib.EpsError(f"sketch_pair_stats: node ids must lie in [0, {n}), got [{lo}, {hi}]")
+    stat = torch.empty((b, k, k), dtype=_I64, device=dev)
+    if b:
+        _call("eps_sketch_pair_stats", dev, hll, mh, k, n, u, v, b, stat, timed=("sketch_pair_stats_kernel", b))
+    bad = stat < 0
+    s = torch.where(bad, stat, stat & ((1 << 42) - 1))
+    z = torch.where(bad, stat, (stat >> 42) & 511).to(_I32)
+    match = torch.where(bad, stat, (stat >> 51) & 255).to(_I32)
+    return s, z, match
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

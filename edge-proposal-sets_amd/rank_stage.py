@@ -57,6 +57,7 @@ def make_parser():
     parser.add_argument('--train_cosine', action="store_true", default=False)   # train mlpcos's embedding (see run())
     parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
     parser.add_argument('--fused_decode_bn', action="store_true", default=False)   # dea: the same, BatchNorm on batch statistics included
+    parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2])   # buddy: hops of the sketches and of the feature propagation
     parser.add_argument('--no_incremental_graph', action="store_true", default=False)   # rebuild the graph from the edge list at every point
     return parser
 

@@ -993,6 +993,40 @@ int eps_local_community_degrees(const int64_t *rowptr, const int32_t *col, int64
 int eps_local_community_scores(const int64_t *rowptr, int64_t n_rows, const int32_t *u, const int32_t *v, const int64_t *ptr,
                                const int32_t *w, const int32_t *gamma, int64_t n_pairs, int32_t index, float *score, void *stream);
 
+/* ---- Subgraph sketches (csrc/sketch.hip) ----------------------------------------------------------------------------------------
+ * ELPH / BUDDY (Chamberlain et al., "Graph Neural Networks for Link Prediction with Subgraph Sketching", ICLR 2023): every node
+ * carries a HyperLogLog sketch (256 one-byte registers) and a MinHash sketch (128 uint32 words) of its k-hop neighbourhoods, and a
+ * pair's structural counts are estimated from those rows at a cost that depends on no degree.  All arithmetic here is integer.
+ *   mix64(x) = the splitmix64 finaliser: z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *              z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31   (mod 2^64)
+ *   own sketch of id x: h = mix64(x), register h >> 56 holds rank = clz32((h >> 24) & 0xFFFFFFFF) + 1 (33 for a zero word), the
+ *              other 255 hold 0; word j = the low 32 bits of mix64(x ^ (j + 1) << 32).
+ *   the empty set: registers 0, words 0xFFFFFFFF.  Union: byte-wise max of the registers, word-wise min of the words.
+ * Tables: hll uint8 [., n, 256], mh uint32 [., n, 128], 16-byte aligned.
+ *   eps_sketch_limits (host only): the row length above which eps_sketch_propagate reduces a row piecewise on several waves, and
+ *       the pairs one wave of eps_sketch_pair_stats handles.
+ *   eps_sketch_own: rows 0 .. n - 1 of hll / mh = the own sketches of the ids first_id .. first_id + n - 1 (ids below 2^31).
+ *   eps_sketch_propagate: out[v] = the union of in[w] over the stored entries w of row v (rowptr int64[n_rows + 1], col int32[nnz],
+ *       a square graph: the pattern only), and with keep_own != 0 also of in[v].  A row without entries gives the empty sketch
+ *       (in[v] under keep_own).  An entry outside [0, n_rows) is skipped and reads nothing; row bounds are clamped to [0, nnz].
+ *       No atomics: a function of the sets alone.  workspace: eps_sketch_propagate_workspace_bytes(nnz) bytes, 256-byte aligned,
+ *       contents arbitrary (the partial unions of the rows longer than the limit; nnz == 0: may be NULL).
+ *   eps_sketch_pair_stats: hll [K, n_rows, 256], mh [K, n_rows, 128], hop k at index k - 1.  stat int64 [n_pairs, K, K]: for
+ *       (i, j) and M = the byte-wise max of hll[i][u] and hll[j][v],
+ *         bits 0..41  S = sum over the registers of 2^(33 - M_r)   (a register above 33 adds nothing)
+ *         bits 42..50 Z = #{r : M_r == 0}        bits 51..58 = #{t : mh[i][u][t] == mh[j][v][t]}
+ *       A pair with an id outside [0, n_rows) gets -1 in all its slots and reads nothing.  Every slot of stat is written.
+ * EPS_EINVAL before any HIP call: a null pointer, K outside {1, 2}, a negative size, first_id + n > 2^31, n_rows > 2^31, a
+ * misaligned table, hll_out / mh_out overlapping their inputs.  Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_sketch_limits(int32_t *row_chunk, int32_t *pairs_per_wave);
+int eps_sketch_own(int64_t first_id, int64_t n, uint8_t *hll, uint32_t *mh, void *stream);
+int64_t eps_sketch_propagate_workspace_bytes(int64_t nnz);
+int eps_sketch_propagate(const int64_t *rowptr, const int32_t *col, int64_t n_rows, int64_t nnz, const uint8_t *hll_in,
+                         const uint32_t *mh_in, uint8_t *hll_out, uint32_t *mh_out, int keep_own, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int eps_sketch_pair_stats(const uint8_t *hll, const uint32_t *mh, int K, int64_t n_rows, const int32_t *u, const int32_t *v,
+                          int64_t n_pairs, int64_t *stat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

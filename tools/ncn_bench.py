@@ -21,75 +21,24 @@ import argparse
 import json
 import os
 import shlex
-import statistics
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from bench_helpers import default_args, rate, stand_in, timed, train_batch, train_step  # noqa: E402
 
 STEP_SECONDS = {"lists_ddi": 300, "lists_collab": 300, "train_ddi": 420, "train_collab": 420, "eval_ddi": 420}
-
-
-def timed(fn, reps, warmup):
-    import torch
-    ts = []
-    for i in range(warmup + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append(e0.elapsed_time(e1))
-    return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3)}
-
-
-def _rate(rec, n_bytes):
-    rec["GB_per_s"] = round(n_bytes / (rec["median_ms"] * 1e-3) / 1e9, 1)
-    return rec
-
-
-def _data(dataset, scale, dev):
-    import torch
-    from eps_amd import datasets
-    from eps_amd.graph import add_edges
-    os.environ["EPS_SYNTH_SCALE"] = str(scale)
-    ei, ew, split_edge, data = datasets.get_data(argparse.Namespace(dataset=dataset, synthetic=True, use_feature=dataset == "collab"))
-    data = data.to(dev)
-    data.adj_t = add_edges(dataset, ei.to(dev), ew.to(dev), torch.zeros((2, 0), dtype=torch.long, device=dev), data.num_nodes)
-    data.full_adj_t = data.adj_t
-    return split_edge, data
-
-
-def _batch(dataset, split_edge, data, batch_size, dev):
-    """The pairs of one step of training.train: a batch of positives in both directions, then as many negatives."""
-    import torch
-    from eps_amd import training
-    from eps_amd.rank_helpers import to_undirected
-    torch.manual_seed(7)
-    pos = split_edge['train']['edge'].to(dev)
-    pos_edge = to_undirected(pos[torch.randperm(pos.size(0), device=dev)[:batch_size]].t())
-    if dataset == "collab":
-        neg_edge = torch.randint(0, data.num_nodes, pos_edge.size(), dtype=torch.long, device=dev)
-    else:
-        row, col, _ = data.adj_t.coo()
-        neg_edge = training.negative_sampling(torch.stack([col, row]), data.num_nodes, pos_edge.size(1))
-    return pos_edge, neg_edge
-
-
-def _args(dataset, model):
-    from eps_amd import models
-    keys = ["num_layers", "hidden_channels", "dropout", "batch_size", "lr", "epochs", "use_feature", "use_learnable_embedding"]
-    return models.default_model_configs(argparse.Namespace(dataset=dataset, model=model, **{k: None for k in keys}))
 
 
 def step_lists(a, dev, dataset):
     import torch
     from eps_amd import ops
-    split_edge, data = _data(dataset, a.scale, dev)
+    split_edge, data = stand_in(dataset, a.scale, dev)
     g = data.adj_t
-    pos_edge, neg_edge = _batch(dataset, split_edge, data, _args(dataset, "ncn").batch_size, dev)
+    pos_edge, neg_edge = train_batch(dataset, split_edge, data, default_args(dataset, "ncn").batch_size, dev)
     e = torch.cat([pos_edge, neg_edge], 1).to(torch.int32)
     u, v = e[0].contiguous(), e[1].contiguous()
     b, n, H = u.numel(), g.n_rows, a.hidden
@@ -100,46 +49,34 @@ def step_lists(a, dev, dataset):
     m = w.numel()
     out = {"step": f"lists_{dataset}", "scale": a.scale, "nodes": n, "entries": g.nnz(), "pairs": b, "matches": m, "hidden": H,
            "row_bytes": row_bytes}
-    out["count"] = _rate(timed(lambda: ops.pair_cn_list_count(g.rowptr, g.col, n, u, v, check=False), a.reps, a.warmup), row_bytes + 28 * b)
-    out["fill"] = _rate(timed(lambda: ops.pair_cn_list_fill(g.rowptr, g.col, n, u, v, ptr, w, check=False), a.reps, a.warmup),
-                        row_bytes + 4 * m + 40 * b)
+    out["count"] = rate(timed(lambda: ops.pair_cn_list_count(g.rowptr, g.col, n, u, v, check=False), a.reps, a.warmup), row_bytes + 28 * b)
+    out["fill"] = rate(timed(lambda: ops.pair_cn_list_fill(g.rowptr, g.col, n, u, v, ptr, w, check=False), a.reps, a.warmup),
+                       row_bytes + 4 * m + 40 * b)
     out["transpose"] = timed(lambda: ops.cn_list_transpose(ptr, w, n, check=False), a.reps, a.warmup)
     out["transpose"]["matches_per_s"] = round(m / (out["transpose"]["median_ms"] * 1e-3), 1)
     tptr, tb = ops.cn_list_transpose(ptr, w, n, check=False)
     h = torch.randn(n, H, device=dev)
     dz = torch.randn(b, H, device=dev)
-    out["spmm_fwd"] = _rate(timed(lambda: ops.spmm_csr(ptr, w, None, h), a.reps, a.warmup), 4 * H * m)
-    out["spmm_bwd"] = _rate(timed(lambda: ops.spmm_csr(tptr, tb, None, dz), a.reps, a.warmup), 4 * H * m)
+    out["spmm_fwd"] = rate(timed(lambda: ops.spmm_csr(ptr, w, None, h), a.reps, a.warmup), 4 * H * m)
+    out["spmm_bwd"] = rate(timed(lambda: ops.spmm_csr(tptr, tb, None, dz), a.reps, a.warmup), 4 * H * m)
     return out
-
-
-def _train_step(model, data, pos_edge, neg_edge, opt):
-    import torch
-    opt.zero_grad()
-    out = model(data.x, torch.cat([pos_edge, neg_edge], 1), data.adj_t).squeeze()
-    k = pos_edge.size(1)
-    loss = -torch.log(out[:k] + 1e-8).mean() - torch.log(1 - out[k:] + 1e-8).mean()
-    loss.backward()
-    torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
-    opt.step()
-    return loss
 
 
 def step_train(a, dev, dataset):
     import torch
     from eps_amd import models
-    split_edge, data = _data(dataset, a.scale, dev)
+    split_edge, data = stand_in(dataset, a.scale, dev)
     out = {"step": f"train_{dataset}", "scale": a.scale, "nodes": data.num_nodes, "entries": data.adj_t.nnz(), "models": {}}
     for name in ("ncn", "gcn"):
-        args = _args(dataset, name)
+        args = default_args(dataset, name)
         torch.manual_seed(1)
         model = models.build_model(args, data, dev)
         model.train()
         opt = torch.optim.Adam(model.parameters(), lr=args.lr)
-        pos_edge, neg_edge = _batch(dataset, split_edge, data, args.batch_size, dev)
-        rec = timed(lambda: _train_step(model, data, pos_edge, neg_edge, opt), a.reps, a.warmup)
+        pos_edge, neg_edge = train_batch(dataset, split_edge, data, args.batch_size, dev)
+        rec = timed(lambda: train_step(model, data, pos_edge, neg_edge, opt), a.reps, a.warmup)
         rec.update(pairs=2 * pos_edge.size(1), hidden=args.hidden_channels, layers=args.num_layers,
-                   loss=round(float(_train_step(model, data, pos_edge, neg_edge, opt)), 4))
+                   loss=round(float(train_step(model, data, pos_edge, neg_edge, opt)), 4))
         out["models"][name] = rec
     return out
 
@@ -147,12 +84,12 @@ def step_train(a, dev, dataset):
 def step_eval(a, dev, dataset):
     import torch
     from eps_amd import evaluate, models
-    split_edge, data = _data(dataset, a.scale, dev)
+    split_edge, data = stand_in(dataset, a.scale, dev)
     out = {"step": f"eval_{dataset}", "scale": a.scale, "nodes": data.num_nodes, "entries": data.adj_t.nnz(),
            "pairs": sum(int(split_edge[k][f].size(0)) for k, f in (("eval_train", "edge"), ("valid", "edge"), ("valid", "edge_neg"),
                                                                     ("test", "edge"), ("test", "edge_neg"))), "models": {}}
     for name in ("ncn", "gcn"):
-        args = _args(dataset, name)
+        args = default_args(dataset, name)
         torch.manual_seed(1)
         model = models.build_model(args, data, dev)
         run = lambda: evaluate.test(model, data, split_edge, evaluate.evaluators[dataset], args.batch_size, args, dev)  # noqa: E731
