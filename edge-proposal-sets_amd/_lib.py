@@ -163,6 +163,9 @@ SIGNATURES = {
     "eps_sketch_propagate_workspace_bytes": (_i64, [_i64]),
     "eps_sketch_propagate": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]),
     "eps_sketch_pair_stats": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "eps_pair_scores_limits": (_int, [_c.POINTER(_i32)] * 6),
+    "eps_pair_scores_grouped_limits": (_int, [_c.POINTER(_i32)] * 4),
+    "eps_rescore_limits": (_int, [_c.POINTER(_i32)] * 3),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

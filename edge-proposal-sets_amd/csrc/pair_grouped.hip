@@ -8,7 +8,7 @@
 // graph).  A workgroup takes a 4096-pair chunk, turns N(v) of the chunk's column into an LDS
 // BITMAP over node ids once, and every pair (u, v) of the chunk then costs one coalesced read
 // of row u plus one ds_read + bit test per element -- no staging of row v per pair, no log
-// factor.  Node-id spaces that do not fit the LDS bitmap (N > 2^20) hash into it (w & mask) and
+// factor.  Node-id spaces that do not fit the LDS bitmap (N > 2^20; see the launch for the last sweep below it) hash into it (w & mask) and
 // every positive is verified by a binary search in row v (exactness kept; the same search
 // yields the position of w in row v, which weighted graphs need for A[v,w]).  Pairs of the chunk
 // whose v differs from the chunk's first v (run boundaries; rare in sorted lists) take an
@@ -21,6 +21,7 @@
 #define PG_QCAP 512             // per-wave hit queue entries (2 KiB)
 #define PG_MAX_WORDS (1 << 15)  // 2^20 bits = 128 KiB
 #define PG_RING 4               // pairs whose row loads are kept in flight per wave
+#define PG_LDS_BYTES 163840     // LDS of a workgroup (160 KiB)
 
 // Bitmap test of one row u against the chunk's column v with the weights gathered INLINE (a dependent
 // global load per hit): used for weighted graphs, float64 weights, hashed bitmaps and oversized pairs.
@@ -332,13 +333,17 @@ static int launch_pair_scores_grouped(const int64_t *rowptr, const int32_t *col,
     // bitmap: exact (one bit per node id) when it fits 2^20 bits, hashed (w & mask) + verified otherwise
     int64_t words = (n_nodes + 31) / 32;
     words = (words + PG_THREADS * 4 - 1) / (PG_THREADS * 4) * (PG_THREADS * 4);  // whole uint4 sweeps
-    const bool exact = words <= PG_MAX_WORDS;
+    // (an exact bitmap needs the per-wave hit queues and the kernel's few static words beside it in a workgroup's 160 KiB: a
+    //  bitmap of PG_MAX_WORDS itself -- the id spaces of the last sweep below 2^20 -- leaves no room for them and could not be
+    //  launched at all; it goes through the hashed variant, whose w & mask is then w itself)
+    const size_t queues = (size_t)PG_WAVES * PG_QCAP * 4;
+    const bool exact = words <= PG_MAX_WORDS && (size_t)words * 4 + queues + 256 <= PG_LDS_BYTES;
     if (!exact) words = PG_MAX_WORDS;
     const uint32_t mask = (uint32_t)(words * 32 - 1);
     // the per-wave hit queues exist only for the deferred-gather (exact bitmap) variants
-    const size_t lds = (size_t)words * 4 + (exact ? (size_t)PG_WAVES * PG_QCAP * 4 : 0);
+    const size_t lds = (size_t)words * 4 + (exact ? queues : 0);
     const int64_t n_chunks = (n_pairs + PG_CHUNK - 1) / PG_CHUNK;
-    int per_cu = (int)(163840 / (lds + 256));
+    int per_cu = (int)(PG_LDS_BYTES / (lds + 256));
     if (per_cu > 4) per_cu = 4;
     if (per_cu < 1) per_cu = 1;
     int64_t blocks = (int64_t)eps_num_cus() * per_cu;
@@ -371,6 +376,15 @@ static int launch_pair_scores_grouped(const int64_t *rowptr, const int32_t *col,
     }
 #undef PG_LAUNCH
     EPS_CHECK_LAUNCH("eps_pair_scores_grouped");
+    return EPS_OK;
+}
+
+extern "C" int eps_pair_scores_grouped_limits(int32_t *chunk, int32_t *queue, int32_t *bitmap_bits, int32_t *ring)
+{
+    if (chunk) *chunk = PG_CHUNK;
+    if (queue) *queue = PG_QCAP;
+    if (bitmap_bits) *bitmap_bits = PG_MAX_WORDS * 32;
+    if (ring) *ring = PG_RING;
     return EPS_OK;
 }
 

@@ -406,6 +406,18 @@ static int launch_pair_scores(const int64_t *rowptr, const int32_t *col, const f
     return EPS_OK;
 }
 
+extern "C" int eps_pair_scores_limits(int32_t *small_max, int32_t *cap, int32_t *queue, int32_t *inplace_ratio, int32_t *ticket,
+                                      int32_t *cls_stride)
+{
+    if (small_max) *small_max = PI_SMALL;
+    if (cap) *cap = PI_CAP;
+    if (queue) *queue = PI_QCAP;
+    if (inplace_ratio) *inplace_ratio = PI_INPLACE_RATIO;
+    if (ticket) *ticket = PI_TICKET;
+    if (cls_stride) *cls_stride = PI_CLS_STRIDE;
+    return EPS_OK;
+}
+
 extern "C" int eps_pair_scores(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w,
                                int64_t n_nodes, const int32_t *u, const int32_t *v, int64_t n_pairs,
                                int32_t *count, float *cn, float *wsum, void *stream)

@@ -310,6 +310,14 @@ static int rescore_runs_launch(const int64_t *rowptr, const int32_t *col, const 
     return EPS_OK;
 }
 
+extern "C" int eps_rescore_limits(int32_t *window_bits, int32_t *short_max, int32_t *chunk)
+{
+    if (window_bits) *window_bits = RS_BITS;
+    if (short_max) *short_max = RS_SHORT;
+    if (chunk) *chunk = RS_CHUNK;
+    return EPS_OK;
+}
+
 extern "C" int eps_rescore_runs(const int64_t *rowptr, const int32_t *col, const int64_t *fixw, int64_t n_nodes,
                                 const int64_t *keys, int64_t n, float *out, void *stream)
 {

@@ -1584,6 +1584,29 @@ def pair_cn_list_limits() -> Tuple[int, int]:
     return cap.value, ratio.value
 
 
+def _limits(name: str, k: int) -> Tuple[int, ...]:
+    out = [ctypes.c_int32(0) for _ in range(k)]
+    _lib.check(getattr(_lib.load(), name)(*[ctypes.byref(x) for x in out]), name)
+    return tuple(x.value for x in out)
+
+
+def pair_scores_limits() -> Tuple[int, int, int, int, int, int]:
+    """(PI_SMALL, PI_CAP, PI_QCAP, PI_INPLACE_RATIO, PI_TICKET, PI_CLS_STRIDE) of the generic pair-score kernel: the sizes at
+    which it changes its path (include/eps_abi.h; host-only query)."""
+    return _limits("eps_pair_scores_limits", 6)
+
+
+def pair_scores_grouped_limits() -> Tuple[int, int, int, int]:
+    """(PG_CHUNK, PG_QCAP, the exact bitmap's bits, PG_RING) of the column-run pair-score kernel (host-only query)."""
+    return _limits("eps_pair_scores_grouped_limits", 4)
+
+
+def rescore_limits() -> Tuple[int, int, int]:
+    """(RS_BITS, RS_SHORT, RS_CHUNK) of eps_rescore_runs: ids per bitmap window, the longest short row, pairs per chunk
+    (host-only query)."""
+    return _limits("eps_rescore_limits", 3)
+
+
 def _cn_list_args(who: str, rowptr, col, n_nodes: int, u, v, check: bool) -> torch.device:
     dev = _need_gpu(rowptr, col, u, v)
     _csr(rowptr, col); _chk(_I32, u=u, v=v)

@@ -1027,6 +1027,27 @@ int eps_sketch_propagate(const int64_t *rowptr, const int32_t *col, int64_t n_ro
 int eps_sketch_pair_stats(const uint8_t *hll, const uint32_t *mh, int K, int64_t n_rows, const int32_t *u, const int32_t *v,
                           int64_t n_pairs, int64_t *stat, void *stream);
 
+/* ---- The sizes at which the pair-score and re-scoring kernels change their path (host only) --------------------------------------
+ * Each call returns the `#define`s of its unit, so that tests place rows, lists and id spaces ON the switch points and follow
+ * a retuned constant; a NULL pointer skips that value.  Nothing is launched.
+ *   eps_pair_scores_limits (csrc/pair_intersect.hip): small_max = the longer row of a pair up to which the pair is scored by
+ *       sixteen lanes, four pairs a wave (unit values, float32 weights); cap = long-row entries staged in LDS per pass; queue =
+ *       the slots of a wave's queue of deferred weight gathers (flushed before a 64-entry slice when more than queue - 64 are
+ *       taken); inplace_ratio = long / short from which a row beyond cap is searched in place; ticket = consecutive 64-pair
+ *       chunks per ticket of the launch that scores the longer pairs; cls_stride = every cls_stride-th 64-pair chunk is sampled
+ *       by the classifier that picks the launch shape on the device (split when at least 60 % of the sampled pairs are small).
+ *   eps_pair_scores_grouped_limits (csrc/pair_grouped.hip): chunk = pairs per workgroup chunk; queue = the slots of a wave's hit
+ *       queue (flushed before a 256-entry unit when more than queue - 256 are taken); bitmap_bits = the bits of the LDS bitmap: an id
+ *       space beyond it is hashed into it and every positive verified (so is one whose exact bitmap would leave no room for the
+ *       queues beside it: the last sweep of ids below bitmap_bits); ring = rows a wave keeps in flight.
+ *   eps_rescore_limits (csrc/rescore.hip): window_bits = ids per bitmap window of eps_rescore_runs; short_max = the row length of
+ *       u up to which a pair goes to the short-row launch; chunk = pairs per workgroup chunk.
+ * Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_pair_scores_limits(int32_t *small_max, int32_t *cap, int32_t *queue, int32_t *inplace_ratio, int32_t *ticket,
+                           int32_t *cls_stride);
+int eps_pair_scores_grouped_limits(int32_t *chunk, int32_t *queue, int32_t *bitmap_bits, int32_t *ring);
+int eps_rescore_limits(int32_t *window_bits, int32_t *short_max, int32_t *chunk);
+
 #ifdef __cplusplus
 }
 #endif

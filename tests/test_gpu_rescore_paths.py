@@ -7,7 +7,10 @@ over the set bits -- and rescore_runs_kernel sets and clears one LDS bitmap of N
 are where those two can go wrong (sparse masks, a lone short pair in lane 0 / lane 63, partial last windows, more than one
 window per wave, a row of exactly 512 / 513 entries, many long runs inside one 256-pair chunk, a long row after a longer one).
 The production lists are sorted by (block of v, u, v): u goes up AND down between neighbouring runs, so the lists of long runs
-here do too; all the others are sorted ascending."""
+here do too; all the others are sorted ascending.
+
+The second half of the file runs the same comparison where the kernel's loop over id windows of RS_BITS ids takes more than one
+trip: a world of 2 RS_BITS + 77 nodes (three windows), and the small world declared as RS_BITS and as RS_BITS + 1 nodes."""
 import numpy as np
 import pytest
 import torch
@@ -132,3 +135,111 @@ def test_rescore_runs_dev_stops_at_device_count(eps, dev, world, case):
     eps.ops._call("eps_rescore_runs_dev", dev, w["rowptr"], w["col"], w["fixw"], N, keys, keys.numel(), n_dev, out)
     assert _same_bits(out[:count], w["ref"][case][:count])
     assert bool((out[count:] == SENTINEL).all())
+
+
+# ---------------------------------------------------------------------------------------------------------- several id windows
+# rescore_runs_kernel walks the id space in windows of RS_BITS ids, setting and clearing the bitmap of N(u) per window.  The world
+# above fits one window; the one below has n = 2 RS_BITS + 77 nodes -- three windows, almost every node isolated -- and is held to
+# the same host sums, bit for bit.  Every size comes from ops.rescore_limits().
+LA, LB = 10, 11                               # long rows: LA has entries in every window, LB none in the second one
+WIDE_CASES = ["long_runs", "A_then_B_stale_bits", "B_then_A", "mixed_with_short", "last_window_only"]
+
+
+def _wide_graph(rng, bits, short):
+    n = 2 * bits + 77
+    edge_ids = [bits - 1, bits, bits + 1, 2 * bits - 1, 2 * bits, n - 1]
+    w0, w1, w2 = np.arange(100, 3000), np.arange(bits + 100, bits + 3000), np.arange(2 * bits + 1, n - 1)
+    apart = np.arange(3000, 4000)                                                   # ids no long row holds
+    rows = {LA: np.concatenate([rng.choice(w0, short // 2 + 40, replace=False), rng.choice(w1, short // 2 + 40, replace=False),
+                                rng.choice(w2, 20, replace=False), edge_ids]),
+            LB: np.concatenate([rng.choice(w0, short + 9, replace=False), rng.choice(w2, 20, replace=False), [bits - 1, 2 * bits, n - 1]])}
+    in_a = rows[LA]
+    a1 = in_a[(in_a >= bits) & (in_a < 2 * bits)]
+    v_all = np.arange(5000, 5100)                                                   # rows with entries in every window, half of them LA's
+    for i in v_all:
+        rows[i] = np.concatenate([rng.choice(w0, 12), rng.choice(in_a[in_a < bits], 6), rng.choice(w1, 8), rng.choice(a1, 8),
+                                  rng.choice(w2, 6), rng.choice(edge_ids, 2)])
+    v_last = np.arange(5100, 5140)                                                  # common neighbours with LA / LB in the last window only
+    for i in v_last:
+        rows[i] = np.concatenate([rng.choice(apart, 20), rng.choice(w2, 10), [2 * bits] if i % 2 else [n - 1]])
+    rows[5140] = np.array(edge_ids)                                                 # exactly the ids on the window edges
+    rows[5141] = np.concatenate([rng.choice(w1, short, replace=False), edge_ids])                  # a third long row, as v and as u
+    src = np.concatenate([np.full(len(c), r, np.int64) for r, c in rows.items()])
+    flat = np.unique(src * n + np.concatenate(list(rows.values())).astype(np.int64))
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(flat // n, minlength=n), out=rowptr[1:])
+    col = (flat % n).astype(np.int32)
+    deg = np.diff(rowptr)
+    assert deg[LA] > short and deg[LB] > short and deg[5141] > short and deg[v_all].max() <= short
+    row = lambda r: col[rowptr[r]:rowptr[r + 1]]                                     # noqa: E731
+    assert set(edge_ids) <= set(row(LA).tolist()) and not ((row(LB) >= bits) & (row(LB) < 2 * bits)).any()
+    assert all(((row(v) >= bits) & (row(v) < 2 * bits) & np.isin(row(v), row(LA))).any() for v in v_all)   # what a stale bit would count
+    assert all((np.intersect1d(row(v), row(LA)) >= 2 * bits).all() and len(np.intersect1d(row(v), row(LA))) for v in v_last)
+    return n, rowptr, col, dict(v_all=v_all, v_last=v_last, edges=5140, third=5141)
+
+
+def _wide_lists(rng, g, chunk):
+    v_all, v_last = g["v_all"], g["v_last"]
+    every_v = np.concatenate([v_all, v_last, [g["edges"], g["third"], LA, LB]])
+    lists = {"long_runs": _keys(np.repeat([LA, LB, g["third"]], len(every_v)), np.tile(every_v, 3))}
+    # one 256-pair chunk: the run of LA (bits in the second window), then the run of LB (none there) on rows v that DO have entries there
+    k = chunk // 2 - 8
+    lists["A_then_B_stale_bits"] = _keys(np.repeat([LA, LB], k), np.tile(rng.choice(v_all, k), 2))
+    assert lists["A_then_B_stale_bits"].size < chunk and LA < LB
+    lists["B_then_A"] = _keys(np.repeat([LB, LA], k), np.tile(rng.choice(v_all, k), 2), ascending=False)
+    u = np.concatenate([rng.choice(v_all, 150), np.full(60, LA), rng.choice(v_last, 40), np.full(60, g["third"]), [g["edges"]] * 10])
+    lists["mixed_with_short"] = _keys(u, rng.choice(every_v, u.size))
+    lists["last_window_only"] = _keys(np.repeat([LA, LB], len(v_last)), np.tile(v_last, 2))
+    assert set(lists) == set(WIDE_CASES)
+    return lists
+
+
+@pytest.fixture(scope="module")
+def limits(eps):
+    bits, short, chunk = eps.ops.rescore_limits()
+    assert short == HUB_LEN[D] and short + 1 == HUB_LEN[A]          # the small world's rows of exactly RS_SHORT / RS_SHORT + 1 entries
+    return bits, short, chunk
+
+
+@pytest.fixture(scope="module")
+def wide_world(dev, limits):
+    bits, short, chunk = limits
+    rng = np.random.default_rng(20240612)
+    n, rowptr, col, g = _wide_graph(rng, bits, short)
+    fixw = rng.integers(1, 1 << 41, n, dtype=np.int64)
+    lists = _wide_lists(rng, g, chunk)
+    ref = {name: _reference(rowptr, col, fixw, k) for name, k in lists.items()}
+    assert all(r.any() for r in ref.values()) and (ref["last_window_only"] > 0).all()
+    t = lambda a: torch.from_numpy(a).to(dev)                                       # noqa: E731
+    return {"n": n, "rowptr": t(rowptr), "col": t(col), "fixw": t(fixw), "keys": {k: t(v) for k, v in lists.items()}, "ref": ref}
+
+
+@pytest.mark.parametrize("case", WIDE_CASES)
+def test_rescore_runs_over_three_id_windows(eps, dev, wide_world, limits, case):
+    w = wide_world
+    assert w["n"] == 2 * limits[0] + 77
+    keys = w["keys"][case]
+    got = eps.ops.rescore_runs(w["rowptr"], w["col"], w["fixw"], w["n"], keys)
+    assert _same_bits(got, w["ref"][case])
+    # the device count below the list's length: the head is the reference's, nothing beyond it is written
+    count = keys.numel() * 2 // 3
+    n_dev = torch.tensor([count], dtype=torch.int64, device=dev)
+    out = torch.full((keys.numel(),), SENTINEL, dtype=torch.float32, device=dev)
+    eps.ops._call("eps_rescore_runs_dev", dev, w["rowptr"], w["col"], w["fixw"], w["n"], keys, keys.numel(), n_dev, out)
+    assert _same_bits(out[:count], w["ref"][case][:count]) and bool((out[count:] == SENTINEL).all())
+    assert _same_bits(eps.ops.rescore_runs_dev(w["rowptr"], w["col"], w["fixw"], w["n"], keys, n_dev)[:count], w["ref"][case][:count])
+
+
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("case", ["all_long", "interleaved", "many_long_runs", "A_then_B"])
+def test_rescore_runs_at_the_window_switch(eps, dev, world, limits, case, extra):
+    """The small world again as a graph of exactly RS_BITS nodes (one window) and of RS_BITS + 1 (a second window of one id): the
+    nodes beyond N are isolated, the sums are the same."""
+    w = world
+    n = limits[0] + extra
+    nnz = w["col"].numel()
+    rowptr = torch.cat([w["rowptr"], torch.full((n - N,), nnz, dtype=torch.int64, device=dev)])
+    fixw = torch.cat([w["fixw"], torch.ones(n - N, dtype=torch.int64, device=dev)])
+    assert rowptr.numel() == n + 1 and fixw.numel() == n
+    got = eps.ops.rescore_runs(rowptr, w["col"], fixw, n, w["keys"][case])
+    assert _same_bits(got, w["ref"][case])
