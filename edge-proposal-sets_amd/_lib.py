@@ -166,6 +166,9 @@ SIGNATURES = {
     "eps_pair_scores_limits": (_int, [_c.POINTER(_i32)] * 6),
     "eps_pair_scores_grouped_limits": (_int, [_c.POINTER(_i32)] * 4),
     "eps_rescore_limits": (_int, [_c.POINTER(_i32)] * 3),
+    "eps_ppr_push_limits": (_int, [_i64, _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64)]),
+    "eps_ppr_push": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

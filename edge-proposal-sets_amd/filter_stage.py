@@ -23,9 +23,9 @@ import torch
 from . import _lib, candidates, ops, proposals, scan
 from .datasets import get_data
 from .graph import CSRGraph, add_edges
-from .heuristics import (KATZ_BETA, LOCAL_COMMUNITY_INDICES, LOCAL_INDICES, cosine_graph, katz_steps_bound, local_community_columns,
-                         local_community_pairs, local_index_columns, node_weight_table, pair_scores_streamed, sigmoid_raw_cut,
-                         truncated_katz, truncated_katz_columns)
+from .heuristics import (KATZ_BETA, LOCAL_COMMUNITY_INDICES, LOCAL_INDICES, PPR_ALPHA, PPR_EPS, cosine_graph, katz_steps_bound,
+                         local_community_columns, local_community_pairs, local_index_columns, node_weight_table, pair_scores_streamed,
+                         ppr_columns, sigmoid_raw_cut, truncated_katz, truncated_katz_columns)
 from .models import DECODE_PRECISIONS, build_model, default_model_configs
 
 
@@ -64,6 +64,10 @@ def make_parser():
                              'command is unchanged')
     parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2],
                         help='--model buddy: hops of the subgraph sketches and of the node-feature propagation (default 2)')
+    parser.add_argument('--ppr_alpha', type=float, default=PPR_ALPHA,
+                        help=f'--model ppr: the teleport probability, rounded to a 16-bit fraction in (0, 1/2] (default {PPR_ALPHA})')
+    parser.add_argument('--ppr_eps', type=float, default=PPR_EPS,
+                        help=f'--model ppr: a node pushes while its residual is at least eps times its degree (default {PPR_EPS})')
     parser.add_argument('--decode_guard', type=float, default=None, metavar='G',
                         help=f'with --decode_precision bf16: the screening pass keeps ceil(G * ceil(K/2)) pairs, G >= 1 '
                              f'(default {DECODE_GUARD_DEFAULT:g}: see DESIGN 4.5d)')
@@ -369,6 +373,31 @@ def katz_blocks(args, data, blocks):
         yield v_lo, v_hi, pairs, truncated_katz_columns(g, v_lo, v_hi, colptr, pairs[0], beta=KATZ_BETA, device_out=True)
 
 
+PPR_COLUMNS = True          # the PPR filter on a symmetric graph: one push per column (False: candidate lists + the pair entry, for comparisons)
+
+
+def ppr_blocks(model, data, blocks):
+    """``scored_blocks`` of the personalized-PageRank filter: candidates of the graph as it is (list-only expansion), then the
+    block's column pointers, then the COLUMN entry (``heuristics.ppr_columns``: one fixed-point push per column v, csrc/ppr_push.hip,
+    read at the column's candidates and scaled by (d(u) + d(v)) / d(u)).  Blocks are [2,E] pair tensors, so the streaming top-K,
+    the per-node cut, column shards and the full sort take them as they take Katz's.  Graphs that do not take this route (a
+    pattern that is not symmetric) are scored by the generic list + ``score_block`` route through the PAIR entry
+    (``heuristics.ppr``: pi_u(v) + pi_v(u) from two pushes); the two routes estimate the same quantity and differ within
+    |column - pair| < eps' d(v) plus the float32 rounding, eps' = ceil(eps 2^48) / 2^48 -- they are not bitwise equal."""
+    g = data.adj_t
+    alpha, eps = model.ppr_alpha, model.ppr_eps          # (what build_model took from --ppr_alpha / --ppr_eps: the pair entry's too)
+    print(f'PPR filter: alpha = {alpha}, eps = {eps}; one push per column, stored values ignored')
+    for v_lo, v_hi in blocks:
+        pairs = candidates.expand_block(g, v_lo, v_hi)[0]
+        if pairs.shape[1] == 0:
+            yield v_lo, v_hi, pairs, None
+            continue
+        v = pairs[1].contiguous()
+        colptr = torch.searchsorted(v, torch.arange(v_lo, v_hi + 1, dtype=v.dtype, device=v.device)).to(torch.int64)
+        # (the list has just come out of the expansion: its ids and column pointers are the kernels' own)
+        yield v_lo, v_hi, pairs, ppr_columns(g, v_lo, v_hi, colptr, pairs[0], alpha=alpha, eps=eps, device_out=True, check=False)
+
+
 LOCAL_INDEX_CUT = True      # local-index filters under --keep_top: the kernel's survivor lists (False: every block scored in full, for comparisons)
 LAST_LOCAL_INDEX_CUTS = []  # the last local-index run, per column block: (v_lo, v_hi, bar or None, "scored" / "cut")
 
@@ -474,6 +503,9 @@ def scored_blocks(args, model, data, ra_graph, col_lo: int = 0, col_hi: int = No
         return
     if args.model == "katz" and KATZ_COLUMNS and candidates.hip_expand_available(g, scored=False):
         yield from katz_blocks(args, data, blocks)
+        return
+    if args.model == "ppr" and PPR_COLUMNS and candidates.hip_expand_available(g, scored=False) and scan.is_symmetric(g):
+        yield from ppr_blocks(model, data, blocks)
         return
     if args.model in LOCAL_INDICES and candidates.hip_expand_available(g, scored=False):
         yield from local_index_blocks(args, data, blocks, bar)
@@ -597,7 +629,7 @@ def run(args) -> str:
             print('dense common-neighbour product (A A^T on the f32 MFMA)')
             print(f'using {n_seen} edges; scored in {dt:.2f} s ({n_seen / max(dt, 1e-9):.3e} candidate edges/s incl. generation)')
             return _save(args, spec, sorted_edge_path, num_sorted_edge, run_id, rank, world, rows)
-    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz",) + LOCAL_INDICES + LOCAL_COMMUNITY_INDICES and scan.scan_plausible(data.adj_t):
+    if 0 < keep <= scan.MAX_K and args.model not in COSINE_MODELS + ("katz", "ppr") + LOCAL_INDICES + LOCAL_COMMUNITY_INDICES and scan.scan_plausible(data.adj_t):
         # (the hubs-first copy first: the symmetry check of scan_available then reads the COPY's reverse positions -- the table
         #  the scan needs anyway -- instead of building one for the graph as labelled, 3-5 ms on a ppa-sized graph)
         scan.scan_graph(data.adj_t, build=True)

@@ -14,6 +14,8 @@ types:
 * ``local_community_columns``                        <- the same for a filter's column-major candidate blocks
 * ``truncated_katz`` / ``exact_katz``                <- the two branches of test_katz, train_and_eval.py:272-343
 * ``truncated_katz_columns``                        <- the truncated series for a filter's column-major candidate blocks
+* ``ppr`` / ``ppr_columns`` / ``ppr_mass``           <- personalized PageRank by a fixed-point forward push (pair entry, a filter's
+                                                        column entry, the integer mass per directed request)
 * ``cosine_common_neighbors(adj, x, edges)``         <- models.py:556-575 ('simplecos' / 'mlpcos')
 * ``cosine_common_neighbors_raw(adj, x, edges)``     <- the same before the sigmoid, differentiable in x (training)
 
@@ -634,4 +636,148 @@ def exact_katz(A, edge_index, beta: float = KATZ_BETA, device_out: bool = False)
     u, v = _as_pairs(edge_index, g.device, g.n_rows)
     h = _katz_inverse(g, beta)
     out = h[u.long(), v.long()]
+    return out if device_out else out.cpu()
+
+
+# ------------------------------------------------------------------------------------------ personalized PageRank
+# The forward push of Andersen, Chung and Lang in integers and synchronous rounds (csrc/ppr_push.hip, include/eps_abi.h): mass in
+# units of 2^-48, alpha = a16 / 65536, a node u pushes while r[u] >= T d(u) with T = ceil(eps * 2^48).  The walk is on the stored
+# PATTERN (stored values are ignored, also on collab, as 'simple' and 'adamic' ignore them).  With eps' = T / 2^48 and pi_s the
+# exact PPR vector at the effective alpha, on a symmetric pattern and a source that was not capped: 0 <= pi_s(x) - p_s(x) < eps' d(x).
+PPR_ALPHA = 0.15                  # common practice (PPRGo, HeaRT), not a measurement
+PPR_EPS = 1e-4                    # likewise
+PPR_MAX_ROUNDS = 1024             # bounds the kernel's loop by an argument (the golden graphs need at most 86 rounds): not a tuning knob
+PPR_SOURCE_CHUNK = 1 << 16        # sources per eps_ppr_push call of ppr_mass ...
+PPR_QUERY_CHUNK = 1 << 24         # ... and query nodes (8 bytes of mass each), whichever comes first
+PPR_SCALE = 2.0 ** -48
+
+
+def ppr_parameters(alpha: float = PPR_ALPHA, eps: float = PPR_EPS) -> Tuple[int, int]:
+    """(a16, thr) of eps_ppr_push: a16 = round(alpha * 65536) in [1, 32768] (the effective alpha is a16 / 65536 exactly), thr =
+    ceil(eps * 2^48) in [1, 2^48].  Refused: thr * (65536 - a16) < 65536, where the share of a push could be 0."""
+    alpha, eps = float(alpha), float(eps)
+    a16 = int(round(alpha * 65536)) if np.isfinite(alpha) else 0
+    if not 1 <= a16 <= 32768:
+        raise EpsError(f"ppr: alpha = {alpha} gives a16 = {a16}, outside [1, 32768] (alpha in (0, 1/2])")
+    if not (np.isfinite(eps) and 0.0 < eps <= 1.0):
+        raise EpsError(f"ppr: eps = {eps} outside (0, 1]")
+    thr = int(np.ceil(eps * 2.0 ** 48))          # (a power-of-two scaling of a float is exact)
+    if thr * (65536 - a16) < 65536:
+        raise EpsError(f"ppr: eps = {eps} (thr = {thr}) is too small for alpha = {alpha}: thr * (65536 - a16) < 65536, a share "
+                       "could be 0")
+    return a16, thr
+
+
+def ppr_queries(src: torch.Tensor, dst: torch.Tensor):
+    """Directed requests (src[i] -> dst[i]) grouped by source, as eps_ppr_push takes them: -> (sources int32 [S], the unique
+    sources ascending; qptr int64 [S + 1]; qnode int32 [E], the targets of source j at qptr[j] : qptr[j + 1] in request order;
+    back int64 [E], with mass_of_request = mass[back]).  Plain tensor ops: also on CPU tensors."""
+    src, dst = torch.as_tensor(src).reshape(-1), torch.as_tensor(dst).reshape(-1)
+    if src.numel() != dst.numel():
+        raise EpsError(f"ppr_queries: {src.numel()} sources for {dst.numel()} targets")
+    order = torch.sort(src.to(torch.int64), stable=True).indices
+    sources, counts = torch.unique_consecutive(src[order].to(torch.int64), return_counts=True)
+    qptr = torch.zeros(sources.numel() + 1, dtype=torch.int64, device=src.device)
+    qptr[1:] = torch.cumsum(counts, 0)
+    back = torch.empty_like(order)
+    back[order] = torch.arange(order.numel(), dtype=order.dtype, device=order.device)
+    return sources.to(torch.int32), qptr, dst[order].to(torch.int32).contiguous(), back
+
+
+def _ppr_report(where: str, n_capped: int, n_sources: int, max_rounds: int) -> None:
+    if n_capped:
+        print(f'{where}: {n_capped} of {n_sources} sources stopped at max_rounds = {max_rounds} with a non-empty frontier '
+              '(their estimates keep the bound of the rounds they ran, not eps)')
+
+
+def ppr_mass(A, src, dst, alpha: float = PPR_ALPHA, eps: float = PPR_EPS, max_rounds: int = PPR_MAX_ROUNDS, table: str = 'auto',
+             stats: Optional[dict] = None, where: str = 'ppr') -> torch.Tensor:
+    """int64 [E] on the graph's device: p_src[i](dst[i]) in units of 2^-48 for every directed request, one push per DISTINCT
+    source (``ppr_queries``), at most PPR_SOURCE_CHUNK sources and PPR_QUERY_CHUNK query nodes per launch so that the query and
+    workspace memory stay bounded.  ``stats`` receives sources, capped, pushes, steps and global_sources; capped sources are
+    printed once per call."""
+    a16, thr = ppr_parameters(alpha, eps)
+    g = _as_graph(A)
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"ppr needs a square adjacency, got {g.sparse_sizes()}")
+    src, dst = torch.as_tensor(src).reshape(-1), torch.as_tensor(dst).reshape(-1)
+    check_node_ids(src, g.n_rows, "ppr sources"); check_node_ids(dst, g.n_rows, "ppr targets")
+    sources, qptr, qnode, back = ppr_queries(src.to(g.device), dst.to(g.device))
+    st = {"sources": int(sources.numel()), "capped": 0, "pushes": 0, "steps": 0, "global_sources": 0}
+    mass = torch.empty(qnode.numel(), dtype=torch.int64, device=g.device)
+    ends = qptr.cpu()
+    i, n_s = 0, int(sources.numel())
+    while i < n_s:
+        j = int(torch.searchsorted(ends, ends[i] + PPR_QUERY_CHUNK, right=True).item()) - 1
+        j = max(i + 1, min(j, i + PPR_SOURCE_CHUNK, n_s))
+        q0, q1 = int(ends[i]), int(ends[j])
+        m, _, pushes, steps, capped = ops.ppr_push(g.rowptr, g.col, g.n_rows, sources[i:j].contiguous(), (qptr[i:j + 1] - q0).contiguous(),
+                                                   qnode[q0:q1].contiguous(), a16, thr, max_rounds, table=table, check=False, stats=st)
+        mass[q0:q1] = m
+        c, p, s = torch.stack([capped.sum().to(torch.int64), pushes.sum(), steps.sum()]).tolist()
+        st["capped"] += int(c); st["pushes"] += int(p); st["steps"] += int(s)
+        i = j
+    _ppr_report(where, st["capped"], n_s, max_rounds)
+    if stats is not None:
+        stats.update(st)
+    return mass[back]
+
+
+def ppr(A, edge_index, alpha: float = PPR_ALPHA, eps: float = PPR_EPS, device_out: bool = False, max_rounds: int = PPR_MAX_ROUNDS,
+        table: str = 'auto', stats: Optional[dict] = None) -> torch.Tensor:
+    """The PAIR entry (rank, evaluation lists, the module's forward): float32 [E] of
+        score(u, v) = float32(float64(M[u -> v] + M[v -> u]) * 2^-48)
+    with M the integer mass of ``ppr_mass`` -- SEAL's pi_u(v) + pi_v(u).  Both directions come out of one set of pushes over the
+    union of the endpoints.  The integer sum is below 2^49, so there is exactly one rounding, and score(u, v) == score(v, u) bit
+    for bit.  Stored values are ignored.  ``A``: get_A output or SciPy; ``edge_index``: [2, E]."""
+    g = _as_graph(A)
+    u, v = _as_pairs(edge_index, g.device, g.n_rows)
+    n = u.numel()
+    m = ppr_mass(g, torch.cat([u, v]), torch.cat([v, u]), alpha, eps, max_rounds, table, stats, where='ppr (pair entry)')
+    out = ((m[:n] + m[n:]).to(torch.float64) * PPR_SCALE).to(torch.float32)
+    return out if device_out else out.cpu()
+
+
+def ppr_columns(A, v_lo: int, v_hi: int, colptr, cand_u, alpha: float = PPR_ALPHA, eps: float = PPR_EPS, device_out: bool = False,
+                max_rounds: int = PPR_MAX_ROUNDS, table: str = 'auto', stats: Optional[dict] = None, check: bool = True) -> torch.Tensor:
+    """The COLUMN entry (a filter's column-major candidate blocks: ``colptr`` [v_hi - v_lo + 1], ``cand_u`` [E], as
+    ``candidates.expand_block`` lays a block out): the block already is "sources with query lists", so the source is the column v
+    and, by reversibility (d(v) pi_v(u) = d(u) pi_u(v) on a symmetric pattern), one push per column estimates both directions:
+        score(u, v) = float32(float64(M[v -> u]) * float64(d(u) + d(v)) / float64(d(u)) * 2^-48)
+    as float64 tensor ops in exactly this order.  It is NOT bitwise the pair score and is not claimed to be: from the bound of
+    the push, |column - pair| < eps' d(v) plus the float32 rounding.  A graph whose pattern is not symmetric is refused.
+    ``check``: the list's ids and the column pointers' ends and order are verified on the host first (``check=False``: a list
+    that has just come out of the expansion)."""
+    from . import scan
+    a16, thr = ppr_parameters(alpha, eps)
+    g = _as_graph(A)
+    if g.n_rows != g.n_cols:
+        raise EpsError(f"ppr needs a square adjacency, got {g.sparse_sizes()}")
+    if not scan.is_symmetric(g):
+        raise EpsError("ppr_columns: the column entry reads pi_u(v) off pi_v(u) by reversibility, which needs a symmetric "
+                       "pattern; score this graph with the pair entry (heuristics.ppr)")
+    v_lo, v_hi = int(v_lo), int(v_hi)
+    if not 0 <= v_lo <= v_hi <= g.n_rows:
+        raise EpsError(f"ppr_columns: columns [{v_lo}, {v_hi}) outside [0, {g.n_rows}]")
+    colptr = torch.as_tensor(colptr).to(device=g.device, dtype=torch.int64).contiguous()
+    cand_u = torch.as_tensor(cand_u)
+    if cand_u.dtype != torch.int32:
+        check_node_ids(cand_u, g.n_rows, "candidate list")
+    cand_u = cand_u.to(device=g.device, dtype=torch.int32).contiguous()
+    if colptr.numel() != v_hi - v_lo + 1:
+        raise EpsError(f"ppr_columns: colptr must hold {v_hi - v_lo + 1} entries, got {colptr.numel()}")
+    sources = torch.arange(v_lo, v_hi, dtype=torch.int32, device=g.device)
+    st = {"sources": v_hi - v_lo, "global_sources": 0}
+    m, _, pushes, steps, capped = ops.ppr_push(g.rowptr, g.col, g.n_rows, sources, colptr, cand_u, a16, thr, max_rounds, table=table,
+                                               check=check, stats=st)
+    c, p, s = torch.stack([capped.sum().to(torch.int64), pushes.sum(), steps.sum()]).tolist() if v_hi > v_lo else (0, 0, 0)
+    st.update(capped=int(c), pushes=int(p), steps=int(s))
+    _ppr_report(f'ppr (columns [{v_lo}, {v_hi}))', int(c), v_hi - v_lo, max_rounds)
+    if stats is not None:
+        stats.update(st)
+    deg = g.rowptr[1:] - g.rowptr[:-1]
+    du = deg[cand_u.long()].to(torch.float64)
+    dv = torch.repeat_interleave(deg[v_lo:v_hi], colptr[1:] - colptr[:-1]).to(torch.float64)
+    out = (m.to(torch.float64) * (du + dv) / du * PPR_SCALE)
+    out = torch.where(du > 0, out, torch.zeros_like(out)).to(torch.float32)       # (a node without entries is never reached: 0)
     return out if device_out else out.cpu()

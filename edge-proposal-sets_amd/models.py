@@ -990,15 +990,21 @@ class CommonNeighborsPredictor(torch.nn.Module):
     'resource_allocation', 'katz' return None exactly like the reference (those heuristics are evaluated by
     AA()/resource_allocation(), not by the module).  The cosine variants ('mlpcos', 'simplecos') score the edge-valued
     common-neighbour sum of the cosine graph (heuristics.cosine_common_neighbors: csrc/cosine_cn.hip + eps_pair_scores).
+    The local indices, the local-community indices and 'ppr' (heuristics.ppr with ``ppr_alpha`` / ``ppr_eps``) return the index
+    itself: no parameters, no sigmoid.
     Scoring (``model.eval()`` or ``torch.no_grad()``) builds no autograd graph.  In ``model.train()`` with grad enabled and a
     learnable embedding the cosine variants are differentiable in emb.weight (heuristics.cosine_common_neighbors_raw:
     csrc/cosine_cn_bwd.hip), which is how the reference trains mlpcos (train_and_eval.py:31-96)."""
 
-    def __init__(self, emb, in_channels, hidden_channels, out_channels, num_layers, dropout, model_type='weighted'):
+    def __init__(self, emb, in_channels, hidden_channels, out_channels, num_layers, dropout, model_type='weighted',
+                 ppr_alpha=heuristics.PPR_ALPHA, ppr_eps=heuristics.PPR_EPS):
         super().__init__()
-        assert model_type in ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz',
+        assert model_type in ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz', 'ppr',
                               *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]
         self.type = model_type
+        self.ppr_alpha, self.ppr_eps = float(ppr_alpha), float(ppr_eps)
+        if self.type == 'ppr':
+            heuristics.ppr_parameters(self.ppr_alpha, self.ppr_eps)       # (a refused pair stops here, before any data is scored)
         if self.type == 'mlpcos':
             self.mlp = MLP(in_channels, hidden_channels, out_channels, num_layers, dropout)
         else:
@@ -1046,6 +1052,8 @@ class CommonNeighborsPredictor(torch.nn.Module):
             return heuristics.local_index(adj, edges, self.type)
         if self.type in heuristics.LOCAL_COMMUNITY_INDICES:                  # (likewise: car, cpa, caa, cra, cjc)
             return heuristics.local_community(adj, edges, self.type)
+        if self.type == 'ppr':                                               # (likewise: pi_u(v) + pi_v(u), the pair entry)
+            return heuristics.ppr(adj, edges, alpha=self.ppr_alpha, eps=self.ppr_eps, device_out=True)
         if self.type == 'adamic':
             # models.py:547-554: weight 1/log(rowsum(adj) + 1e-6) per common neighbour (edge values of the two
             # rows are NOT used: only the indices of the product), no inf guard, then sigmoid
@@ -1065,10 +1073,18 @@ class CommonNeighborsPredictor(torch.nn.Module):
 # ----------------------------------------------------------------------------------- factory
 DECODE_MAX_HIDDEN = 256          # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 256
 _MODELS = ['sage', 'sage2', 'gcn', 'dea', 'dea_512', 'mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb',
-           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage', 'buddy']
+           "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage', 'buddy',
+           'ppr']
 _NCN = {'ncn': 'gcn', 'ncn_sage': 'sage'}       # Neural Common Neighbor: name -> the encoder whose arguments and defaults it takes
 _ENCODER_ROW = {**_NCN, 'buddy': 'gcn'}         # models beyond the reference: name -> the row of the defaults table they take
-_HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]
+_HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES,
+               'ppr']
+
+
+def _flag(args, name: str, default):
+    """An optional command-line value: the default when the namespace does not carry it (or carries None)."""
+    x = getattr(args, name, None)
+    return default if x is None else x
 
 
 def build_model(args, data, device):
@@ -1122,8 +1138,11 @@ def build_model(args, data, device):
         return BuddyLinkModel(emb, input_dim, args.hidden_channels, args.num_layers, args.dropout,
                               hops=int(getattr(args, "sketch_hops", 2) or 2)).to(device)
     if args.model in _HEURISTICS:
+        ppr_kw = {}
+        if args.model == 'ppr':
+            ppr_kw = dict(ppr_alpha=_flag(args, "ppr_alpha", heuristics.PPR_ALPHA), ppr_eps=_flag(args, "ppr_eps", heuristics.PPR_EPS))
         return CommonNeighborsPredictor(emb, input_dim, args.hidden_channels, args.hidden_channels, args.num_layers,
-                                        args.dropout, model_type=args.model).to(device)
+                                        args.dropout, model_type=args.model, **ppr_kw).to(device)
     raise NotImplementedError(f"model '{args.model}' (sage2 / ensemble_gcn_sage) is outside the accelerated path "
                               "(SURVEY 2.1: alternative / experimental models, not in the north star)")
 
@@ -1214,7 +1233,8 @@ def default_model_configs(args):
     for attr in _KEYS:
         if getattr(args, attr) is None:
             setattr(args, attr, defaults[attr])
-    if args.model in ['adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz', "ensemble_gcn_sage", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES]:
+    if args.model in ['adamic', 'simple', 'adamic_ogb', "resource_allocation", 'katz', "ensemble_gcn_sage", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES,
+                      'ppr']:
         args.use_feature = False
         args.use_learnable_embedding = False
     if args.model == 'simplecos' and args.dataset != "email":

@@ -1901,6 +1901,98 @@ def sketch_pair_stats(hll, mh, n: int, u, v, check: bool = True):
     return s, z, match
 
 
+PPR_ONE = 1 << 48                 # csrc/ppr_push.hip: the mass of a source, in units of 2^-48
+PPR_WS_BUDGET = 16 << 30          # global tables: fewer workgroups rather than more than this much workspace (one region per
+                                  # workgroup of the launch, also for the workgroups whose sources all stay in LDS: at eps = 1e-4 a
+                                  # region is 15 MB and two workgroups per CU take 7.5 GB; at 1e-5 on the ppa-like graph 59 MB each)
+PPR_MAX_TABLE_NODES = 1 << 30
+_PPR_CUS = {}                     # device -> its number of CUs (the launch takes two workgroups per CU)
+
+
+def ppr_push_limits(table_nodes: int = 0) -> Tuple[int, int, int, int]:
+    """(keys the LDS table of eps_ppr_push takes, row length above which the whole workgroup walks a row, workgroups per CU,
+    workspace bytes per workgroup of a global table of ``table_nodes`` keys -- 0 for 0) (host-only query)."""
+    cap, big, per_cu, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().eps_ppr_push_limits(int(table_nodes), ctypes.byref(cap), ctypes.byref(big), ctypes.byref(per_cu),
+                                               ctypes.byref(ws)), "eps_ppr_push_limits")
+    return cap.value, big.value, per_cu.value, ws.value
+
+
+def ppr_touched_bound(n_nodes: int, alpha16: int, thr: int) -> int:
+    """min(n_nodes, a bound on the nodes one source touches): every push of u keeps at least thr * d(u) * a16 / 65536 - 1 units
+    in p, the kept units sum to at most 2^48, so once thr * a16 >= 2 * 65536 the pushed entries sum to at most
+    2 * 2^48 * 65536 / (thr * a16), and a source touches at most one node more.  Below that the bound is n_nodes."""
+    n_nodes, alpha16, thr = int(n_nodes), int(alpha16), int(thr)
+    if thr * alpha16 < 2 * 65536:
+        return n_nodes
+    return min(n_nodes, 2 * PPR_ONE * 65536 // (thr * alpha16) + 2)
+
+
+def ppr_push(rowptr, col, n_nodes: int, sources, qptr, qnode, alpha16: int, thr: int, max_rounds: int, table: str = 'auto',
+             check: bool = True, stats: Optional[dict] = None):
+    """-> (mass int64[Q], rounds int32[S], pushes int64[S], steps int64[S], capped int32[S]): the fixed-point personalized
+    PageRank push of include/eps_abi.h (csrc/ppr_push.hip) from every node of ``sources`` (int32[S]) on the pattern of the square
+    CSR, read at the query nodes ``qnode[qptr[i] : qptr[i + 1]]`` (int32) of source i.  alpha = alpha16 / 65536, thr =
+    ceil(eps * 2^48).  ``table='global'`` skips the LDS attempt (same bits).  ``check``: the ids, the pointers' ends and order
+    are verified on the host first (one read); without it a source or an entry outside the graph is reported after the launch.
+    A global table that filled up raises: nothing is lost silently.  ``stats``: a dict that receives ``global_sources``, the
+    number of sources whose table left LDS."""
+    if table not in ('auto', 'global'):
+        raise _lib.EpsError(f"ppr_push: table must be 'auto' or 'global', got {table!r}")
+    dev = _need_gpu(rowptr, col, sources, qptr, qnode)
+    _csr(rowptr, col); _chk(_I32, sources=sources, qnode=qnode); _chk(_I64, qptr=qptr)
+    n_nodes, alpha16, thr, max_rounds = int(n_nodes), int(alpha16), int(thr), int(max_rounds)
+    if rowptr.numel() != n_nodes + 1:
+        raise _lib.EpsError(f"ppr_push: rowptr must hold {n_nodes + 1} entries, got {rowptr.numel()}")
+    ns, nq = sources.numel(), qnode.numel()
+    if sources.dim() != 1 or qptr.numel() != ns + 1:
+        raise _lib.EpsError(f"ppr_push: qptr must hold {ns + 1} entries (one more than the sources), got {qptr.numel()}")
+    if check and ns:
+        z = torch.zeros((), dtype=_I64, device=dev)
+        facts = torch.stack([sources.min().to(_I64), sources.max().to(_I64), qptr[0], qptr[-1], (qptr[1:] - qptr[:-1]).min(),
+                             qnode.min().to(_I64) if nq else z, qnode.max().to(_I64) if nq else z,
+                             col.min().to(_I64) if col.numel() else z, col.max().to(_I64) if col.numel() else z,
+                             rowptr[0], rowptr[-1], (rowptr[1:] - rowptr[:-1]).min() if n_nodes else z]).tolist()
+        if facts[0] < 0 or facts[1] >= n_nodes:
+            raise _lib.EpsError(f"ppr_push: sources must lie in [0, {n_nodes}), got [{facts[0]}, {facts[1]}]")
+        if facts[2] != 0 or facts[3] != nq or facts[4] < 0:
+            raise _lib.EpsError(f"ppr_push: qptr must ascend from 0 to {nq} (the query nodes), got {facts[2]} .. {facts[3]}")
+        if facts[5] < 0 or facts[6] >= n_nodes:
+            raise _lib.EpsError(f"ppr_push: query nodes must lie in [0, {n_nodes}), got [{facts[5]}, {facts[6]}]")
+        if facts[7] < 0 or facts[8] >= n_nodes or facts[9] != 0 or facts[10] != col.numel() or facts[11] < 0:
+            raise _lib.EpsError(f"ppr_push: not a square CSR of {n_nodes} nodes (entries in [{facts[7]}, {facts[8]}], rowptr "
+                                f"{facts[9]} .. {facts[10]} for {col.numel()} entries)")
+    mass = torch.empty(nq, dtype=_I64, device=dev)
+    rounds = torch.empty(ns, dtype=_I32, device=dev)
+    pushes, steps = torch.empty(ns, dtype=_I64, device=dev), torch.empty(ns, dtype=_I64, device=dev)
+    capped, used = torch.empty(ns, dtype=_I32, device=dev), torch.empty(ns, dtype=_I32, device=dev)
+    status = torch.zeros(1, dtype=_I32, device=dev)
+    lds_nodes, _, per_cu, _ = ppr_push_limits(0)
+    ws, ws_bytes, table_nodes = None, 0, 0
+    if table == 'global' or n_nodes > lds_nodes:
+        table_nodes = max(1, min(ppr_touched_bound(n_nodes, alpha16, thr), PPR_MAX_TABLE_NODES))
+        per_group = ppr_push_limits(table_nodes)[3]
+        if dev not in _PPR_CUS:
+            with torch.cuda.device(dev):
+                _PPR_CUS[dev] = device_info()[0]
+        groups = max(1, min(per_cu * _PPR_CUS[dev], max(ns, 1), PPR_WS_BUDGET // per_group))
+        ws_bytes = groups * per_group
+        ws = _scratch("ppr_push", dev, ws_bytes // 8, ws_bytes // 8)
+    _call("eps_ppr_push", dev, rowptr, col, n_nodes, sources, ns, qptr, qnode, alpha16, thr, max_rounds, 1 if table == 'global' else 0,
+          table_nodes, ws, ws_bytes, mass, rounds, pushes, steps, capped, used, status, timed=("ppr_push_kernel", ns))
+    if ns:
+        st, n_global = torch.stack([status[0].to(_I64), (used == 1).sum()]).tolist()
+        if st:
+            raise _lib.EpsError(f"ppr_push: status {st}"
+                                + (f": a table of {table_nodes} keys filled up" if st & 1 else "")
+                                + (": a source left LDS without a workspace" if st & 2 else "")
+                                + (": a source outside the graph" if st & 4 else "")
+                                + (": an entry of col outside the graph" if st & 8 else ""))
+        if stats is not None:
+            stats["global_sources"] = stats.get("global_sources", 0) + int(n_global)
+    return mass, rounds, pushes, steps, capped
+
+
 def kth_largest_dist(x: torch.Tensor, k: int, world: int = 1) -> torch.Tensor:
     """The k-th largest value of the UNION of every rank's float32 device vector ``x`` (lengths may differ, 0 allowed) as a
     1-element device tensor, identical on all ranks; -inf when the union holds fewer than k values.  Radix select in four

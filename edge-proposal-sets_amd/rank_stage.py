@@ -18,6 +18,7 @@ import torch
 from .datasets import get_data
 from .evaluate import evaluators, hits, test, test_adamic, test_katz, test_resource_allocation
 from .graph import add_edges
+from .heuristics import PPR_ALPHA, PPR_EPS
 from .runlog import Logger
 from .models import build_model, default_model_configs
 from .rank_helpers import to_undirected
@@ -58,6 +59,8 @@ def make_parser():
     parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
     parser.add_argument('--fused_decode_bn', action="store_true", default=False)   # dea: the same, BatchNorm on batch statistics included
     parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2])   # buddy: hops of the sketches and of the feature propagation
+    parser.add_argument('--ppr_alpha', type=float, default=PPR_ALPHA)   # ppr: teleport probability (rounded to a 16-bit fraction)
+    parser.add_argument('--ppr_eps', type=float, default=PPR_EPS)       # ppr: the push threshold per unit of degree
     parser.add_argument('--no_incremental_graph', action="store_true", default=False)   # rebuild the graph from the edge list at every point
     return parser
 

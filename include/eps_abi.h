@@ -1048,6 +1048,40 @@ int eps_pair_scores_limits(int32_t *small_max, int32_t *cap, int32_t *queue, int
 int eps_pair_scores_grouped_limits(int32_t *chunk, int32_t *queue, int32_t *bitmap_bits, int32_t *ring);
 int eps_rescore_limits(int32_t *window_bits, int32_t *short_max, int32_t *chunk);
 
+/* ---- Personalized PageRank by a fixed-point push (csrc/ppr_push.hip) ---------------------------------------------------------------
+ * The forward push of Andersen, Chung and Lang in integers and synchronous rounds, so that the result is a function of (graph,
+ * source, a16, thr, max_rounds) alone -- bitwise equal across launches, splits and table paths, and to a numpy truth.
+ *   Graph: square CSR, the pattern only (stored values are not read).  Row u = the nodes u pushes to, d(u) its length.
+ *   Mass is in units of 2^-48 (ONE = 2^48).  alpha = a16 / 65536, 1 <= a16 <= 32768.  thr = T = ceil(eps * 2^48), 1 <= T <= 2^48.
+ *   Per source s: r[s] = ONE, everything else 0.  d(s) == 0: p[s] = ONE, no rounds.  While fewer than max_rounds rounds have run:
+ *     F = { u : d(u) > 0 and r[u] >= T d(u) } on the state at the start of the round (T d(u) in exact integers: a product beyond
+ *     ONE admits nothing; a node without entries has nowhere to push and keeps its residual); stop when F is empty; for u in F,
+ *     R = r[u]: keep = (R * a16) >> 16, spread = R - keep, share = spread / d(u) (floor), p[u] += keep, r[u] = spread - share d(u),
+ *     every entry w of row u receives share; the shares are added to r after every node of F has been reset.
+ *   sources int32[n_sources] (duplicates allowed); qptr int64[n_sources + 1] ascending from 0; qnode int32[qptr[n_sources]]: the
+ *   query nodes of every source.  Out, per query: mass = p[x] of its source (0 for a node never touched, or outside the graph);
+ *   per source: rounds, pushes = sum |F|, steps = sum over the pushes of d(u), capped = 1 when the loop ended at max_rounds with
+ *   a non-empty F; table_used (may be NULL) = 0 when the source's table stayed in LDS, 1 when it was redone in the workspace.
+ *   sum p + sum r == ONE exactly.  thr * (65536 - a16) >= 65536 is required (a share could be 0 otherwise).
+ *   Tables: a source that touches more than lds_nodes nodes is redone from the start in its workgroup's region of `workspace`
+ *   (device, 8-byte aligned, contents arbitrary), a table of table_nodes keys: min(n_nodes, a bound on the touched nodes) never
+ *   fills.  force_global != 0 skips the LDS attempt (same bits).  The launch takes min(2 per CU, n_sources, workspace_bytes /
+ *   bytes per group) workgroups.  A graph of at most lds_nodes nodes without force_global needs no workspace.
+ *   status int32[1], zeroed by the caller: bit 0 = a global table filled up (that source has rounds = -1 and mass 0: never a
+ *   silent loss), bit 1 = a source left LDS without a workspace, bit 2 = a source outside the graph (rounds = -1), bit 3 = an
+ *   entry of col outside the graph was skipped.
+ * eps_ppr_push_limits (host only): lds_nodes = the keys the LDS table takes, big_row = the row length above which a row is walked
+ * by the whole workgroup, groups_per_cu, and the workspace bytes per workgroup of a table of table_nodes keys (0 for 0).
+ * EPS_EINVAL before any HIP call: a null pointer, a16 or thr out of range, thr too small for a16, max_rounds < 1, a negative or
+ * oversized size, a workspace that is null, misaligned or smaller than one workgroup's region where one is needed.
+ * Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_ppr_push_limits(int64_t table_nodes, int32_t *lds_nodes, int32_t *big_row, int32_t *groups_per_cu,
+                        int64_t *workspace_bytes_per_group);
+int eps_ppr_push(const int64_t *rowptr, const int32_t *col, int64_t n_nodes, const int32_t *sources, int64_t n_sources,
+                 const int64_t *qptr, const int32_t *qnode, int32_t a16, int64_t thr, int32_t max_rounds, int32_t force_global,
+                 int64_t table_nodes, void *workspace, int64_t workspace_bytes, int64_t *mass, int32_t *rounds, int64_t *pushes,
+                 int64_t *steps, int32_t *capped, int32_t *table_used, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
