@@ -113,6 +113,10 @@ typedef short sp_v2s __attribute__((ext_vector_type(2)));
 // quarter-rate 32-bit one: its weaker mixing lengthens the probe sequences -- 38.0 vs 30.7 ms per launch.)
 __device__ __forceinline__ uint32_t sp_mix(uint32_t x) { return x * 0x9E3779B1u; }
 __device__ __forceinline__ uint32_t sp_mix2(uint32_t x) { return x * 0x85EBCA6Bu; }      // (the sketch pieces' second table)
+// (2026-10-20: both slot indices of a sketch piece from ONE full-rate 24 x 24-bit multiply -- top bits and the bits below them -- were
+//  measured against these two quarter-rate products: the main launch 6394 vs 6377 us, NOTES "Scan sweeps")
+
+typedef unsigned short sp_v2us __attribute__((ext_vector_type(2)));
 
 struct sp_unit {
     sp_v4i u4;
@@ -255,6 +259,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
     __shared__ unsigned int s_ticket;
     __shared__ unsigned int s_out_cur, s_out_end;
     __shared__ unsigned int s_fill_lo, s_fill_hi;       // what is left of an abandoned reservation: filled with "no survivor"
+    __shared__ unsigned long long s_ncand;   // candidates scored by this workgroup: every wave adds a piece's count (one 64-bit LDS add)
     __shared__ unsigned int s_hot;           // sketch pieces: some slot of the first half table reaches the bar (else nothing is looked at again)
     __shared__ uint32_t s_em[SP_EM];         // sketch pieces: id + 1 of every candidate reported so far (a path per report: the set dedupes)
 
@@ -288,10 +293,9 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
         s_fill_lo = 0u;
         s_fill_hi = 0u;
         s_alloc = 0ull;
+        s_ncand = 0ull;
     }
     bool sketch_seen = false;
-    unsigned long long n_cand = 0;           // candidates seen by this thread
-    uint32_t new_keys = 0u;                  // ... of the current hash piece: candidate keys this thread inserted
     const unsigned int ncol = (unsigned int)p.n_columns;
     // Columns are handed out by tickets on ONE device word; the L2 serves same-address atomics at ~11 ns each, and the light
     // columns at the end of the heaviest-first order take a workgroup ~10 us -- with 1024 workgroups drawing, the tickets, not
@@ -503,6 +507,10 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                     }
                 };
                 for (uint32_t part = 0; part < parts; ++part) {
+                    // Candidates are counted per pass and wave: a lane's count lives from the walk (hash pieces: the keys it put in) to
+                    // the end of the sweep (direct pieces: the fields it saw), where lane 63 adds the wave's sum to s_ncand -- no
+                    // counter is carried from piece to piece.
+                    uint32_t new_keys = 0u;
                     // ---- known edges in: the neighbours of v inside the piece take their slots BEFORE the walk, with the flag bit
                     // in the value word -- whatever the paths add on top, the sweep sees that this id is no candidate (rows ascend:
                     // the neighbours inside the piece's windows are vcol[na, nb)).  The first barrier of the describe orders this
@@ -928,13 +936,20 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                     // A word is tested as a SIGNED number: a known edge's flag is its sign bit, so `(int)word >= bar` is false for it
                     // (and for an empty word), and the largest of a uint4's four words decides with one branch whether any of them
                     // needs a closer look -- survivors are a handful per piece.
-                    uint32_t cnt_here = 0u;
                     const int thr_s = thr_v >= SP_FLAG ? 0x7FFFFFFF : (int)thr_v;      // (sums stay below 2^31 - 2)
                     if (d16) {
                         // (two fields per word: the low one shifted up, the high one masked, both signed as above.  The packed
-                        //  16-bit instructions -- v_pk_min / max / add_i16 on the word as it is, 5 instead of 9 per word -- were
-                        //  measured: 17.75 vs 17.57 ms on the same box)
+                        //  16-bit instructions for the GATE -- v_pk_min / max / add_i16 on the word as it is, 5 instead of 9 per word --
+                        //  were measured in r03: 17.75 vs 17.57 ms on the same box; 2026-10-20: the high field read off the unmasked word and
+                        //  v_max3_i32, 9 instead of 16 per uint4: 6377 vs 6380 us, not kept.  The candidate COUNT is packed: see below)
                         const int thr_h = pk_thr >= 0x8000u ? 0x7FFFFFFF : (int)(pk_thr << 16);
+                        sp_v2us pc16 = (sp_v2us)(0);      // (a thread looks at fewer than 2^16 fields of a piece)
+                        // (the pair of ones comes through an empty asm: seen as a constant, max(x, 0) then min(., 1) is folded back
+                        //  into two compares, two selects and a permute per word -- six instructions for three.  The count is right
+                        //  either way; what this buys depends on the compiler, and nothing but the listing notices if a later one
+                        //  folds it again: profiles/scan_sweeps/instruction_budget.txt says how to look -- 48 v_pk_* per trip here)
+                        uint32_t ones = 0x00010001u;
+                        asm("" : "+v"(ones));
                         const uint32_t n4 = (scan_slots + 3u) & ~3u;
                         for (uint32_t i0 = 0; i0 < n4; i0 += 4u * SP_SB * T) {
                             uint4 s4[SP_SB];
@@ -948,14 +963,19 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 const uint32_t i = i0 + 4u * T * b + 4u * tid;
                                 if (i < n4) *(uint4 *)(lds + i) = make_uint4(0u, 0u, 0u, 0u);
                                 const uint32_t wv[4] = {s4[b].x, s4[b].y, s4[b].z, s4[b].w};
+                                // a candidate: a field that was reached and is no known edge, i.e. positive as a signed 16-bit number --
+                                // both fields of a word at once: negative -> 0, then positive -> 1, added to a packed pair of counters
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const sp_v2s pos = __builtin_elementwise_max(__builtin_bit_cast(sp_v2s, wv[e]), (sp_v2s)(0));
+                                    pc16 += __builtin_elementwise_min(__builtin_bit_cast(sp_v2us, pos), __builtin_bit_cast(sp_v2us, ones));
+                                }
                                 int x[8];
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     x[2 * e] = (int)(wv[e] << 16);
                                     x[2 * e + 1] = (int)(wv[e] & 0xFFFF0000u);
                                 }
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) cnt_here += x[e] > 0 ? 1u : 0u;
                                 int m = x[0];
 #pragma unroll
                                 for (int e = 1; e < 8; ++e) m = x[e] > m ? x[e] : m;
@@ -966,6 +986,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 }
                             }
                         }
+                        new_keys += (uint32_t)pc16.x + (uint32_t)pc16.y;
                     } else if (direct) {
                         const uint32_t n4 = (scan_slots + 3u) & ~3u;
                         for (uint32_t i0 = 0; i0 < n4; i0 += 4u * SP_SB * T) {
@@ -981,7 +1002,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 if (i < n4) *(uint4 *)(lds + i) = make_uint4(0u, 0u, 0u, 0u);
                                 const int sv[4] = {(int)s4[b].x, (int)s4[b].y, (int)s4[b].z, (int)s4[b].w};
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) cnt_here += sv[e] > 0 ? 1u : 0u;      // reached and not a known edge
+                                for (int e = 0; e < 4; ++e) new_keys += sv[e] > 0 ? 1u : 0u;      // reached and not a known edge
                                 const int m01 = sv[0] > sv[1] ? sv[0] : sv[1], m23 = sv[2] > sv[3] ? sv[2] : sv[3];
                                 if ((m01 > m23 ? m01 : m23) >= thr_s) {
 #pragma unroll
@@ -1045,8 +1066,10 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             }
                         }
                     }
-                    n_cand += (unsigned long long)cnt_here + (unsigned long long)new_keys;
-                    new_keys = 0u;
+                    {
+                        const uint32_t upto = (uint32_t)sp_wave_incl_scan((int)new_keys);      // (lane 63: the wave's count)
+                        if (lane == 63 && upto) atomicAdd(&s_ncand, (unsigned long long)upto);
+                    }
                     sp_barrier();
                 }
             }
@@ -1071,13 +1094,8 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
             out_val[i] = -__builtin_inff();
         }
     }
-    // candidates scored by this workgroup: one atomic per wave
-    {
-        unsigned long long x = n_cand;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-        if (lane == 0 && x) atomicAdd(&p.out->n_candidates, x);
-    }
+    // candidates scored by this workgroup: one atomic
+    if (tid == 0 && s_ncand) atomicAdd(&p.out->n_candidates, s_ncand);      // (the loop's last barrier is behind every wave's last add)
 }
 
 static const int sp_threads_of[3] = {512, 1024, 256}, sp_bits_of[3] = {13, 14, 12}, sp_per_cu[3] = {2, 1, 4};
