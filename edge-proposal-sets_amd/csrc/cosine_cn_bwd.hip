@@ -6,11 +6,10 @@
 //
 // Given g_p = dL/draw_p:
 //   eps_pair_cn_backward:       gc[(u, w)] += g_p * c[(v, w)],  gc[(v, w)] += g_p * c[(u, w)]  per (pair, common neighbour):
-//                               the intersection of the generic pair kernel (pair_intersect.hip: the longer row staged in LDS,
-//                               the shorter one element per lane, branch-free lower bound) with two adds per hit instead of a
-//                               per-pair sum.  The adds are 64-bit FIXED-POINT integer atomics -- integer addition commutes, so gc
-//                               does not depend on the order the pairs arrive in (float atomics would) -- at a scale taken from
-//                               max |g_p| (one reduction on the device); a convert pass writes float32.
+//                               the walk of row_intersect.h with two adds per hit instead of a per-pair sum.  The adds are 64-bit
+//                               FIXED-POINT integer atomics -- integer addition commutes, so gc does not depend on the order the
+//                               pairs arrive in (float atomics would) -- at a scale taken from max |g_p| (one reduction on the
+//                               device); a convert pass writes float32.
 //   eps_cos_features_backward:  a_r = sum_{e = (r, w)} (gc[e] + gc[rev(e)]) * xhat_w  (both stored copies of an undirected entry
 //                               are the same dot product; a self loop gets its factor 2 here), then the normalisation's backward
 //                               gx'_r = (a_r - xhat_r (xhat_r . a_r)) / nrm_r, or a_r / 1e-8 where the clamp was active.  A row
@@ -18,11 +17,9 @@
 //                               cosine_common.h).  Optionally also gx'_r / deg_r: the operand of the smoothing's backward
 //                               gx = gx' + A (gx' / deg), which is one eps_spmm_csr on a symmetric adjacency.
 #include "cosine_common.h"
-#include "pair_common.h"
+#include "row_intersect.h"
 
 #define PB_WAVES 4            // waves per workgroup
-#define PB_CAP 1024           // long-row entries staged per wave and pass (4 KiB of LDS per wave)
-#define PB_INPLACE_RATIO 32   // long row searched in place when long > PB_CAP && long >= ratio * short
 #define PB_SUM_BITS 60        // |every fixed-point sum| < 2^(PB_SUM_BITS + 1)
 
 // ---- max |g_p| -> its float32 bit pattern (non-negative floats order like unsigned integers; a maximum commutes) ------------
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(PB_WAVES * 64) void pair_cn_backward_kernel(
     const int32_t *__restrict__ pu, const int32_t *__restrict__ pv, const float *__restrict__ g, int64_t n_pairs,
     unsigned int *__restrict__ next_chunk, const unsigned int *__restrict__ gmax_bits, int shift, long long *__restrict__ fx)
 {
-    __shared__ __attribute__((aligned(16))) int32_t s_rows[PB_WAVES][PB_CAP];
+    __shared__ __attribute__((aligned(16))) int32_t s_rows[PB_WAVES][ROW_CAP];
     const unsigned int gb = *gmax_bits;
     if (gb == 0u) return;                                    // every g_p is zero: nothing to add
     const double scale = ldexp(1.0, pb_scale_log2(gb, shift));
@@ -67,14 +64,9 @@ __global__ __launch_bounds__(PB_WAVES * 64) void pair_cn_backward_kernel(
     const int64_t n_chunks = (n_pairs + 63) >> 6;
 
     // 64-pair chunks handed out dynamically, the next ticket drawn while the current chunk is worked on (pair_intersect.hip)
-    auto take = [&]() -> int64_t {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(next_chunk, 1u);
-        return (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-    };
-    int64_t chunk = take();
+    int64_t chunk = take_chunk(next_chunk, lane);
     while (chunk < n_chunks) {
-        const int64_t next = take();
+        const int64_t next = take_chunk(next_chunk, lane);
         const int64_t p = chunk * 64 + lane;
         bool valid = p < n_pairs;
         int32_t nu = valid ? pu[p] : 0, nv = valid ? pv[p] : 0;
@@ -98,72 +90,14 @@ __global__ __launch_bounds__(PB_WAVES * 64) void pair_cn_backward_kernel(
             const int32_t slen = swapped ? djv : dju, llen = swapped ? dju : djv;
             const int64_t sbase = swapped ? bjv : bju, lbase = swapped ? bju : bjv;
 
-            if (llen > PB_CAP && (int64_t)llen >= (int64_t)slen * PB_INPLACE_RATIO) {
-                // very lopsided: the long row is searched in place, log2(llen) probes per element of the short row
-                const int32_t *__restrict__ lcol = col + lbase;
-                for (int s0 = 0; s0 < slen; s0 += 64) {
-                    const int si = s0 + lane;
-                    const bool act = si < slen;
-                    const int t = act ? col[sbase + si] : 0;
-                    const int pos = lower_bound_uniform(lcol, llen, t);
-                    const int pc = pos < llen ? pos : llen - 1;
-                    if (act && pos < llen && lcol[pc] == t) {
-                        const int64_t es = sbase + si, el = lbase + pc;
-                        const float cs = c[es], cl = c[el];
-                        pb_add(fx, es, gj, cl, scale);
-                        pb_add(fx, el, gj, cs, scale);
-                    }
-                }
-                continue;
-            }
-            int s_cursor = 0;
-            const __amdgpu_buffer_rsrc_t srs = row_rsrc(col + sbase, slen);
-            for (int l0 = 0; l0 < llen && s_cursor < slen; l0 += PB_CAP) {
-                const int n = (llen - l0) < PB_CAP ? (llen - l0) : PB_CAP;
-                const int lg = n > 1 ? 32 - __builtin_clz(n - 1) : 0;  // P = 2^lg >= n
-                const int P = 1 << lg;
-                const __amdgpu_buffer_rsrc_t lrs = row_rsrc(col + lbase + l0, n);
-                // stage the pass: every 16-byte load of it is issued before the first LDS write (out-of-range dwords read 0 and
-                // become INT_MAX sentinels), and so is the first 64-entry slice of the short row
-                v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16, 0, 0), x1, x2, x3;
-                if (P > 256) x1 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 1024, 0, 0);
-                if (P > 512) {
-                    x2 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 2048, 0, 0);
-                    x3 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 3072, 0, 0);
-                }
-                const int t_first = __builtin_amdgcn_raw_buffer_load_b32(srs, (s_cursor + lane) * 4, 0, 0);
-                const int s_first = s_cursor;
-                __builtin_amdgcn_wave_barrier();
-                *reinterpret_cast<v4i *>(&L[4 * lane]) = pad_tail(x0, 4 * lane, n);
-                if (P > 256) *reinterpret_cast<v4i *>(&L[256 + 4 * lane]) = pad_tail(x1, 256 + 4 * lane, n);
-                if (P > 512) {
-                    *reinterpret_cast<v4i *>(&L[512 + 4 * lane]) = pad_tail(x2, 512 + 4 * lane, n);
-                    *reinterpret_cast<v4i *>(&L[768 + 4 * lane]) = pad_tail(x3, 768 + 4 * lane, n);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                // several passes co-iterate with the (sorted) short row like a merge: a pass searches the short elements <= its
-                // own last entry only, the cursor marks the first one not yet settled
-                const bool multipass = llen > PB_CAP;
-                const int last = multipass ? __builtin_amdgcn_readfirstlane(L[n - 1]) : 0x7fffffff;
-                for (int s0 = s_cursor; s0 < slen; s0 += 64) {
-                    const int si = s0 + lane;
-                    const int t = s0 == s_first ? t_first : __builtin_amdgcn_raw_buffer_load_b32(srs, si * 4, 0, 0);
-                    const bool mine = si < slen && t <= last;       // a prefix of the lanes (sorted row)
-                    const int n_mine = __popcll(__ballot(mine));
-                    s_cursor = s0 + n_mine;
-                    const int pos = lb_pow2(L, lg, t);
-                    if (mine && L[pos] == t) {
-                        const int64_t es = sbase + si, el = lbase + l0 + pos;
-                        const float cs = c[es], cl = c[el];
-                        pb_add(fx, es, gj, cl, scale);
-                        pb_add(fx, el, gj, cs, scale);
-                    }
-                    if (n_mine < 64 && s0 + 64 < slen) s0 = slen;  // the rest of the short row belongs to later passes
-                }
-                __builtin_amdgcn_wave_barrier();                   // (the next pass / pair overwrites the staged row)
-            }
+            auto two_adds = [&](const bool found, int, const int si, const int li, bool) {
+                if (!found) return;
+                const int64_t es = sbase + si, el = lbase + li;
+                const float cs = c[es], cl = c[el];
+                pb_add(fx, es, gj, cl, scale);
+                pb_add(fx, el, gj, cs, scale);
+            };
+            intersect_rows<ROW_CAP, ROW_INPLACE_RATIO>(col, sbase, slen, lbase, llen, L, lane, two_adds);
         }
         chunk = next;
     }

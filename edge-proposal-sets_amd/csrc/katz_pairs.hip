@@ -23,7 +23,7 @@
 // Arithmetic: each lane accumulates its terms in float64, the wave reduces with a fixed butterfly, segments are added in
 // a fixed order, and the result is rounded to float32 once.  Which pairs are split, and how, depends on the graph and the
 // pair alone, so two launches give bitwise equal outputs (the list's order differs between launches, nothing read from it does).
-#include "pair_common.h"
+#include "row_intersect.h"      // (lds_wave_sync, take_chunk; pair_common.h)
 #include <math.h>
 
 #define KZ_WAVES 4
@@ -45,13 +45,6 @@ struct KzLds {
     int64_t start[KZ_WAVES][64];   // row start of each w
     float aw[KZ_WAVES][64];        // A[a,w]
 };
-
-__device__ __forceinline__ void kz_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Side and walk length of pair (u, v): fwd = walk A from u, else walk A^T from v.
 __device__ __forceinline__ void kz_plan(const int64_t *__restrict__ rp, const int64_t *__restrict__ rp_t,
@@ -92,12 +85,12 @@ __device__ double kz_walk(const KzCsr W, const KzCsr M, int32_t a, int32_t b, in
     const int32_t *keys = M.col + mb;
     const float *vals = M.val ? M.val + mb : nullptr;
     if (md <= KZ_MAP_CAP) {
-        kz_wave_sync();                    // (the previous pair's lookups are done before the map is overwritten)
+        lds_wave_sync();                   // (the previous pair's lookups are done before the map is overwritten)
         for (int i = lane; i < md; i += 64) {
             S.key[wib][i] = keys[i];
             if (vals) S.val[wib][i] = vals[i];
         }
-        kz_wave_sync();
+        lds_wave_sync();
         keys = S.key[wib];
         vals = vals ? S.val[wib] : nullptr;
     }
@@ -126,11 +119,11 @@ __device__ double kz_walk(const KzCsr W, const KzCsr M, int32_t a, int32_t b, in
         const int64_t lo = t_lo > base ? t_lo - base : 0;
         const int64_t hi = t_hi - base < tot ? t_hi - base : tot;
         if (lo < hi) {
-            kz_wave_sync();
+            lds_wave_sync();
             S.excl[wib][lane] = inc - wd;
             S.start[wib][lane] = ws;
             S.aw[wib][lane] = aw;
-            kz_wave_sync();
+            lds_wave_sync();
             const int64_t *ex = S.excl[wib];
             for (int64_t t0 = lo; t0 < hi; t0 += 64) {
                 const int64_t t = t0 + lane;
@@ -169,9 +162,7 @@ __global__ __launch_bounds__(KZ_WAVES * 64) void katz_pairs_kernel(
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t n_chunks = (n_pairs + 63) >> 6;
     for (;;) {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(next_chunk, 1u);
-        const int64_t chunk = (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+        const int64_t chunk = take_chunk(next_chunk, lane);
         if (chunk >= n_chunks) break;
         const int64_t p = chunk * 64 + lane;
         const bool valid = p < n_pairs;

@@ -15,11 +15,11 @@
 //   * SHORT lists (up to LC_SHORT entries: what a filter's candidates have) all together: the ordered (i, j) pairs of all the
 //     chunk's short lists are dealt over the lanes, a lane answers "is z_j stored in row w_i" by a lower bound in the row, and
 //     gamma_i is a segmented count (ballot, popcount of the lanes of one (list, i), one LDS add per group and step);
-//   * longer lists one after the other: the list staged in the wave's LDS slice (LC_CAP entries per pass, padded with INT_MAX
-//     to a power of two; a longer list in passes, the partial counts added in gamma itself by the lane that owns the entry),
+//   * longer lists one after the other: the list staged in the wave's LDS slice by row_intersect.h's stage_issue / stage_commit
+//     (ROW_CAP entries per pass; a longer list in passes, the partial counts added in gamma itself by the lane that owns the entry),
 //     the rows of 64 list members STREAMED one element per lane against it -- the rows laid end to end, so short rows do not
 //     idle the wave -- matches by ballot and popcount, the self match dropped;
-//   * IN PLACE: a member whose row is LC_INPLACE_RATIO times the staged entries (a hub between two low-degree nodes) is not
+//   * IN PLACE: a member whose row is ROW_INPLACE_RATIO times the staged entries (a hub between two low-degree nodes) is not
 //     streamed; the staged entries are searched in its row, 64 per step.
 //   Plain vector stores only; the one global atomic is the ticket.  Integer counts: no float atomics, nothing depends on order.
 // eps_local_community_scores: per pair, G (int64) and the float64 sum of the index's terms in a FIXED association of the list
@@ -28,14 +28,12 @@
 //   alone, not on launch shape, place in the batch, route or orientation.  Lists up to LC_SHORT entries are summed by one lane
 //   each (the same tree, written out), longer ones by the whole wave; chunks by ticket, so one 40,000-entry list occupies one
 //   wave while the others go on.
-#include "pair_common.h"
+#include "row_intersect.h"
 
 #include <math.h>
 
 #define LC_WAVES 4            // waves per workgroup
 #define LC_SHORT 8            // lists up to this many entries: ordered pairs dealt over the lanes / one lane per list in the scores
-#define LC_CAP 1024           // list entries staged per wave and pass (4 KiB of LDS per wave): lb_pow2's largest table
-#define LC_INPLACE_RATIO 32   // row searched in place when it holds >= ratio * the staged entries
 #define LC_INDICES 5
 
 enum { LC_CAR = 0, LC_CPA, LC_CAA, LC_CRA, LC_CJC };
@@ -63,13 +61,6 @@ __device__ __forceinline__ double lc_term(int index, int32_t g, int64_t d)
     if (index == LC_CAA) return (double)g / log2((double)d);
     if (index == LC_CRA) return (double)g / (double)d;
     return 0.0;
-}
-
-__device__ __forceinline__ void lc_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Exclusive prefix of x over the wave's lanes; total = the sum.
@@ -114,13 +105,6 @@ __device__ __forceinline__ int lc_lower_bound(const int32_t *__restrict__ a, int
     return lo;
 }
 
-__device__ __forceinline__ int64_t lc_take(unsigned int *next_chunk, int lane)
-{
-    unsigned int t = 0;
-    if (lane == 0) t = atomicAdd(next_chunk, 1u);
-    return (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-}
-
 // Segment p of ptr clamped into [0, total]; `bad` when it had to be.
 __device__ __forceinline__ void lc_segment(const int64_t *__restrict__ ptr, int64_t p, int64_t total, int64_t &sb, int64_t &se, bool &bad)
 {
@@ -138,7 +122,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
     const int32_t *__restrict__ w, int64_t n_pairs, int group, unsigned int *__restrict__ next_chunk, int32_t *__restrict__ gamma,
     int32_t *__restrict__ status)
 {
-    __shared__ __attribute__((aligned(16))) int32_t s_list[LC_WAVES][LC_CAP];
+    __shared__ __attribute__((aligned(16))) int32_t s_list[LC_WAVES][ROW_CAP];
     __shared__ int32_t s_off[LC_WAVES][64];
     __shared__ int32_t s_acc[LC_WAVES][64];
     const int lane = threadIdx.x & 63;
@@ -174,7 +158,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
         E[lane] = off;
 #pragma unroll
         for (int k = 0; k < LC_SHORT; ++k) L[k * 64 + lane] = 0;  // counts of (list s, entry i) at L[s * LC_SHORT + i]
-        lc_lds_sync();
+        lds_wave_sync();
         for (int t0 = 0; t0 < n_items; t0 += 64) {
             const int t = t0 + lane;
             const bool act = t < n_items;
@@ -202,7 +186,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                     if (cnt) L[s * LC_SHORT + i] += cnt;
                 }
             }
-            lc_lds_sync();                                   // (a group that straddles two steps is added to by two lanes in turn)
+            lds_wave_sync();                                   // (a group that straddles two steps is added to by two lanes in turn)
         }
 #pragma unroll
         for (int k = 0; k < LC_SHORT; ++k) {
@@ -212,7 +196,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
             const int64_t bs = lc_shfl64(sb, s);
             if (i < cs) gamma[bs + i] = L[slot];             // (a refused list: zeros)
         }
-        lc_lds_sync();
+        lds_wave_sync();
 
         // ---- the longer lists, one after the other ----------------------------------------------------------------------
         for (int j = 0; j < group; ++j) {
@@ -237,37 +221,22 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                 if (lane == j) bad = true;
                 continue;
             }
-            for (int l0 = 0; l0 < cj; l0 += LC_CAP) {
-                const int n = (cj - l0) < LC_CAP ? (cj - l0) : LC_CAP;
-                const int lg = n > 1 ? 32 - __builtin_clz(n - 1) : 0;  // P = 2^lg >= n
-                const int P = 1 << lg;
-                const __amdgpu_buffer_rsrc_t lrs = row_rsrc(seg + l0, n);
-                v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16, 0, 0), x1, x2, x3;
-                if (P > 256) x1 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 1024, 0, 0);
-                if (P > 512) {
-                    x2 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 2048, 0, 0);
-                    x3 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 3072, 0, 0);
-                }
-                __builtin_amdgcn_wave_barrier();
-                *reinterpret_cast<v4i *>(&L[4 * lane]) = pad_tail(x0, 4 * lane, n);
-                if (P > 256) *reinterpret_cast<v4i *>(&L[256 + 4 * lane]) = pad_tail(x1, 256 + 4 * lane, n);
-                if (P > 512) {
-                    *reinterpret_cast<v4i *>(&L[512 + 4 * lane]) = pad_tail(x2, 512 + 4 * lane, n);
-                    *reinterpret_cast<v4i *>(&L[768 + 4 * lane]) = pad_tail(x3, 768 + 4 * lane, n);
-                }
-                lc_lds_sync();
+            for (int l0 = 0; l0 < cj; l0 += ROW_CAP) {
+                const int n = (cj - l0) < ROW_CAP ? (cj - l0) : ROW_CAP;
+                const int lg = stage_lg(n);
+                stage_commit(L, stage_issue(seg + l0, n, lg, lane), n, lg, lane);
                 for (int i0 = 0; i0 < cj; i0 += 64) {        // 64 members of the list, lane m <-> entry i0 + m in every pass
                     const int i = i0 + lane;
                     const bool am = i < cj;
                     const int wi = am ? seg[i] : 0;
                     const int64_t rb = am ? rowptr[wi] : 0;
                     const int d = am ? (int)(rowptr[wi + 1] - rb) : 0;
-                    const bool inplace = am && d >= 64 && (int64_t)d >= (int64_t)n * LC_INPLACE_RATIO;
-                    const int fd = inplace ? 0 : d;          // streamed rows, laid end to end (each below 32 * LC_CAP entries)
+                    const bool inplace = am && d >= 64 && (int64_t)d >= (int64_t)n * ROW_INPLACE_RATIO;
+                    const int fd = inplace ? 0 : d;          // streamed rows, laid end to end (each below 32 * ROW_CAP entries)
                     int n_flat = 0;
                     E[lane] = lc_prefix(fd, lane, n_flat);
                     ACC[lane] = 0;
-                    lc_lds_sync();
+                    lds_wave_sync();
                     for (int t0 = 0; t0 < n_flat; t0 += 64) {
                         const int t = t0 + lane;
                         const bool act = t < n_flat;
@@ -287,7 +256,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                                 if (cnt) ACC[m] += cnt;
                             }
                         }
-                        lc_lds_sync();
+                        lds_wave_sync();
                     }
                     int mine = 0;
                     uint64_t todo = __ballot(inplace);
@@ -313,16 +282,16 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                         if (l0 == 0) gseg[i] = got;
                         else gseg[i] += got;                 // (a later pass: the same lane wrote the earlier passes' count)
                     }
-                    lc_lds_sync();                           // (the next 64 members overwrite E and ACC)
+                    lds_wave_sync();                           // (the next 64 members overwrite E and ACC)
                 }
                 __builtin_amdgcn_wave_barrier();             // (the next pass overwrites the staged entries)
             }
         }
         if (valid && bad) *status = 1;
     };
-    int64_t chunk = lc_take(next_chunk, lane);
+    int64_t chunk = take_chunk(next_chunk, lane);
     while (chunk < n_chunks) {
-        const int64_t next = lc_take(next_chunk, lane);
+        const int64_t next = take_chunk(next_chunk, lane);
         do_chunk(chunk);
         chunk = next;
     }
@@ -394,9 +363,9 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_scores_kernel(
         }
         if (valid) score[p] = ok ? lc_score(index, c, a, b, G, S) : __builtin_nanf("");
     };
-    int64_t chunk = lc_take(next_chunk, lane);
+    int64_t chunk = take_chunk(next_chunk, lane);
     while (chunk < n_chunks) {
-        const int64_t next = lc_take(next_chunk, lane);
+        const int64_t next = take_chunk(next_chunk, lane);
         do_chunk(chunk);
         chunk = next;
     }
@@ -413,8 +382,8 @@ static int64_t lc_blocks(int64_t n_pairs)
 extern "C" int eps_local_community_limits(int32_t *short_max, int32_t *cap, int32_t *inplace_ratio)
 {
     if (short_max) *short_max = LC_SHORT;
-    if (cap) *cap = LC_CAP;
-    if (inplace_ratio) *inplace_ratio = LC_INPLACE_RATIO;
+    if (cap) *cap = ROW_CAP;
+    if (inplace_ratio) *inplace_ratio = ROW_INPLACE_RATIO;
     return EPS_OK;
 }
 

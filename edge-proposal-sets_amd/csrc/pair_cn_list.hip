@@ -8,23 +8,19 @@
 // Work decomposition: pair_intersect.hip's generic kernel (PART 0) without the sums --
 //   * 64-pair chunks are handed to waves by ticket (one device-scope atomic per chunk, drawn one chunk ahead);
 //   * lane i fetches pair i's ids, row bounds and (fill) segment bounds; the 64 pairs are then listed one after the other by the
-//     whole wave: the LONGER row staged in LDS (CL_CAP entries per pass, 16-byte raw buffer loads, INT_MAX padding up to the
-//     next power of two), the SHORTER row one element per lane with the unrolled branch-free lower bound; very lopsided pairs
-//     search the long row in place;
+//     whole wave, each by the walk of row_intersect.h;
 //   * the matches of a 64-element slice are compacted by ballot + prefix popcount, so a slice is written in the short row's
-//     order; the passes co-iterate with the short row like a merge (a pass settles the short elements <= its last entry), so the
-//     whole segment ascends in w whichever row is the short one: list(u, v) and list(v, u) are the same array.
-// COUNT and FILL are the two modes of ONE template: the same staging, the same in-place branch and the same compare decide what
-// is a match in both.  The fill writes plain vector stores at ptr[b] + rank, never at or past ptr[b + 1] (nor past ptr[n_pairs]),
-// and reports a segment whose length is not the pair's match count in *status.  No atomics on global memory but the ticket.
+//     order; the walk delivers the slices in the short row's order too, pass after pass, so the whole segment ascends in w
+//     whichever row is the short one: list(u, v) and list(v, u) are the same array.
+// COUNT and FILL are the two modes of ONE template: the same walk decides what is a match in both.  The fill writes plain vector
+// stores at ptr[b] + rank, never at or past ptr[b + 1] (nor past ptr[n_pairs]), and reports a segment whose length is not the
+// pair's match count in *status.  No atomics on global memory but the ticket.
 // HBM traffic: both rows once, 4 bytes per match, 24 (count) / 32 (fill) bytes of header per pair.
-#include "pair_common.h"
+#include "row_intersect.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #define CL_WAVES 4            // waves per workgroup
-#define CL_CAP 1024           // long-row entries staged per wave and pass (4 KiB of LDS per wave): lb_pow2's largest table
-#define CL_INPLACE_RATIO 32   // long row searched in place when long > CL_CAP && long >= ratio * short
 
 template <bool FILL>
 __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
@@ -32,18 +28,13 @@ __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
     const int32_t *__restrict__ pv, int64_t n_pairs, unsigned int *__restrict__ next_chunk, int32_t *__restrict__ out_count,
     const int64_t *__restrict__ ptr, int32_t *__restrict__ out_w, int32_t *__restrict__ status)
 {
-    __shared__ __attribute__((aligned(16))) int32_t s_rows[CL_WAVES][CL_CAP];
+    __shared__ __attribute__((aligned(16))) int32_t s_rows[CL_WAVES][ROW_CAP];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int32_t *L = s_rows[wib];
     const int64_t n_chunks = (n_pairs + 63) >> 6;
     const int64_t total = FILL ? ptr[n_pairs] : 0;           // no store at or past the end of out_w, whatever ptr holds
 
-    auto take = [&]() -> int64_t {
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(next_chunk, 1u);
-        return (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
-    };
     auto do_chunk = [&](const int64_t chunk) {
         const int64_t p = chunk * 64 + lane;
         const bool valid = p < n_pairs;
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
             const int64_t sbase = swapped ? bjv : bju, lbase = swapped ? bju : bjv;
             int cnt = 0;                                     // wave-uniform: matches of this pair so far
             // one slice of the short row: t per lane, `found` where it is a common neighbour
-            auto emit = [&](const bool found, const int t) {
+            auto emit = [&](const bool found, const int t, int, int, bool) {
                 const uint64_t m = __ballot(found);
                 if (m == 0ull) return;
                 if (FILL) {
@@ -83,60 +74,7 @@ __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
                 }
                 cnt += __popcll(m);
             };
-            if (llen > CL_CAP && (int64_t)llen >= (int64_t)slen * CL_INPLACE_RATIO) {
-                const int32_t *__restrict__ lcol = col + lbase;
-                for (int s0 = 0; s0 < slen; s0 += 64) {
-                    const int si = s0 + lane;
-                    const bool act = si < slen;
-                    const int t = act ? col[sbase + si] : 0;
-                    const int pos = lower_bound_uniform(lcol, llen, t);
-                    const int pc = pos < llen ? pos : llen - 1;
-                    emit(act && pos < llen && lcol[pc] == t, t);
-                }
-            } else {
-                int s_cursor = 0;
-                const __amdgpu_buffer_rsrc_t srs = row_rsrc(col + sbase, slen);
-                for (int l0 = 0; l0 < llen && s_cursor < slen; l0 += CL_CAP) {
-                    const int n = (llen - l0) < CL_CAP ? (llen - l0) : CL_CAP;
-                    const int lg = n > 1 ? 32 - __builtin_clz(n - 1) : 0;  // P = 2^lg >= n
-                    const int P = 1 << lg;
-                    const __amdgpu_buffer_rsrc_t lrs = row_rsrc(col + lbase + l0, n);
-                    // stage the pass: every 16-byte load of it, and the first slice of the short row, before the first LDS write
-                    v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16, 0, 0), x1, x2, x3;
-                    if (P > 256) x1 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 1024, 0, 0);
-                    if (P > 512) {
-                        x2 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 2048, 0, 0);
-                        x3 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 3072, 0, 0);
-                    }
-                    const int t_first = __builtin_amdgcn_raw_buffer_load_b32(srs, (s_cursor + lane) * 4, 0, 0);
-                    const int s_first = s_cursor;
-                    __builtin_amdgcn_wave_barrier();
-                    *reinterpret_cast<v4i *>(&L[4 * lane]) = pad_tail(x0, 4 * lane, n);
-                    if (P > 256) *reinterpret_cast<v4i *>(&L[256 + 4 * lane]) = pad_tail(x1, 256 + 4 * lane, n);
-                    if (P > 512) {
-                        *reinterpret_cast<v4i *>(&L[512 + 4 * lane]) = pad_tail(x2, 512 + 4 * lane, n);
-                        *reinterpret_cast<v4i *>(&L[768 + 4 * lane]) = pad_tail(x3, 768 + 4 * lane, n);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    // a pass settles the short elements <= its own last entry (a prefix of what is left: both rows ascend), so
-                    // the matches of pass k all precede those of pass k + 1
-                    const bool multipass = llen > CL_CAP;
-                    const int last = multipass ? __builtin_amdgcn_readfirstlane(L[n - 1]) : 0x7fffffff;
-                    for (int s0 = s_cursor; s0 < slen; s0 += 64) {
-                        const int si = s0 + lane;
-                        const int t = s0 == s_first ? t_first : __builtin_amdgcn_raw_buffer_load_b32(srs, si * 4, 0, 0);
-                        const bool mine = si < slen && t <= last;
-                        const int n_mine = __popcll(__ballot(mine));
-                        s_cursor = s0 + n_mine;
-                        const int pos = lb_pow2(L, lg, t);
-                        emit(mine && L[pos] == t, t);
-                        if (n_mine < 64) break;              // the rest of the short row belongs to later passes
-                    }
-                    __builtin_amdgcn_wave_barrier();         // (the next pass overwrites the staged entries)
-                }
-            }
+            intersect_rows<ROW_CAP, ROW_INPLACE_RATIO>(col, sbase, slen, lbase, llen, L, lane, emit);
             if (lane == j) my_count = cnt;
         }
         if (valid) {
@@ -148,9 +86,9 @@ __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
             }
         }
     };
-    int64_t chunk = take();
+    int64_t chunk = take_chunk(next_chunk, lane);
     while (chunk < n_chunks) {
-        const int64_t next = take();
+        const int64_t next = take_chunk(next_chunk, lane);
         do_chunk(chunk);
         chunk = next;
     }
@@ -176,8 +114,8 @@ static int launch_cn_list(const char *who, const int64_t *rowptr, const int32_t 
 
 extern "C" int eps_pair_cn_list_limits(int32_t *cap, int32_t *inplace_ratio)
 {
-    if (cap) *cap = CL_CAP;
-    if (inplace_ratio) *inplace_ratio = CL_INPLACE_RATIO;
+    if (cap) *cap = ROW_CAP;
+    if (inplace_ratio) *inplace_ratio = ROW_INPLACE_RATIO;
     return EPS_OK;
 }
 

@@ -24,31 +24,18 @@ __device__ __forceinline__ int lower_bound_uniform(P a, int n, int t)
     return pos;
 }
 
+// One common neighbour t of (u, v), stored at es in the shorter row and at el in the longer (swapped: the shorter row is v's):
+// its A[u,t] * A[v,t] and its weighted product, added to the lane's sums.
 template <bool HAS_VAL, bool HAS_W, typename WT>
-__device__ __forceinline__ void score_pair_inplace(const int32_t *__restrict__ col, const float *__restrict__ val,
-                                                   const WT *__restrict__ node_w, int64_t bu, int32_t du, int64_t bv,
-                                                   int32_t dv, int lane, int &cnt, float &acc_cn, WT &acc_ws)
+__device__ __forceinline__ void pair_products(const float *__restrict__ val, const WT *__restrict__ node_w, int64_t es, int64_t el,
+                                              bool swapped, int t, float &acc_cn, WT &acc_ws)
 {
-    const bool swapped = du > dv;
-    const int32_t slen = swapped ? dv : du, llen = swapped ? du : dv;
-    const int64_t sbase = swapped ? bv : bu, lbase = swapped ? bu : bv;
-    const int32_t *__restrict__ lcol = col + lbase;
-    for (int s0 = 0; s0 < slen; s0 += 64) {
-        const int si = s0 + lane;
-        const bool act = si < slen;
-        const int t = act ? col[sbase + si] : 0;
-        const int pos = lower_bound_uniform(lcol, llen, t);
-        const int pc = pos < llen ? pos : llen - 1;
-        const bool found = act && pos < llen && lcol[pc] == t;
-        cnt += __popcll(__ballot(found));
-        if ((HAS_VAL || HAS_W) && found) {
-            float vs = 1.0f, vl = 1.0f;
-            if (HAS_VAL) { vs = val[sbase + si]; vl = val[lbase + pc]; }
-            const float va = swapped ? vl : vs, vbv = swapped ? vs : vl;
-            if (HAS_VAL) acc_cn += va * vbv;
-            if (HAS_W) acc_ws += (WT)va * ((WT)vbv * node_w[t]);
-        }
-    }
+    if (!HAS_VAL && !HAS_W) return;
+    float vs = 1.0f, vl = 1.0f;
+    if (HAS_VAL) { vs = val[es]; vl = val[el]; }
+    const float va = swapped ? vl : vs, vbv = swapped ? vs : vl;  // va = A[u,w], vbv = A[v,w]
+    if (HAS_VAL) acc_cn += va * vbv;
+    if (HAS_W) acc_ws += (WT)va * ((WT)vbv * node_w[t]);  // A_ entry rounded first (adamic_utils.py:17)
 }
 
 typedef int v4i __attribute__((ext_vector_type(4)));

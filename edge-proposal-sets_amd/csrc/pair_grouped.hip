@@ -1,6 +1,21 @@
 // Column-run pair scoring (candidate lists in the reference's column-major order), gfx950.
 // See pair_intersect.hip for the generic kernel and the entry points' semantics (include/eps_abi.h).
-#include "pair_common.h"
+#include "row_intersect.h"
+
+// A pair off the bitmap path (its v is not the segment's): row_intersect.h's in-place search with the generic kernel's products.
+template <bool HAS_VAL, bool HAS_W, typename WT>
+__device__ __forceinline__ void score_pair_inplace(const int32_t *__restrict__ col, const float *__restrict__ val,
+                                                   const WT *__restrict__ node_w, int64_t bu, int32_t du, int64_t bv,
+                                                   int32_t dv, int lane, int &cnt, float &acc_cn, WT &acc_ws)
+{
+    const bool swapped = du > dv;
+    const int64_t sbase = swapped ? bv : bu, lbase = swapped ? bu : bv;
+    intersect_rows_inplace(col, sbase, swapped ? dv : du, lbase, swapped ? du : dv, lane,
+                           [&](const bool found, const int t, const int si, const int li, bool) {
+                               cnt += __popcll(__ballot(found));
+                               if (found) pair_products<HAS_VAL, HAS_W, WT>(val, node_w, sbase + si, lbase + li, swapped, t, acc_cn, acc_ws);
+                           });
+}
 
 // =====================================================================================
 // Column-run variant: candidate lists in the reference's order (filter.py:96-109: column-major,

@@ -12,22 +12,15 @@
 //     pair costs are heavy-tailed, a static split leaves the slowest wave running long after the others.
 //   * lane i fetches pair i's (u,v) and the four rowptr words in parallel -- one coalesced metadata fetch per 64
 //     pairs instead of a dependent scalar chain per pair -- and lane i finally stores pair i's results (coalesced).
-//   * the 64 pairs are then scored one after the other by the whole wave: the LONGER adjacency row is staged in LDS
-//     (PI_CAP entries per pass) with 16-byte raw buffer loads, all issued before the first LDS write (out-of-range
-//     lanes read 0 and are replaced by INT_MAX sentinels up to the next power of two: no bounds branch); the SHORTER
-//     row is spread one element per lane and every lane runs a fully unrolled, branch-free lower bound over the
-//     padded row.  Matches are counted with ballot+popcount; for unit-weight graphs the node_w gathers of the hits are
-//     queued in LDS and resolved once per 64 pairs (no dependent global load on a pair's critical path); weighted
-//     graphs / float64 weights accumulate inline and reduce with a DPP butterfly.
-//   * very lopsided pairs (long row >> short row) skip the staging and search the long row in place (L2-resident
-//     binary search), so a degree-100k hub costs log2(d) probes per element of the short row instead of a full read.
+//   * the 64 pairs are then scored one after the other by the whole wave, each by the walk of row_intersect.h (the longer row
+//     staged in LDS or, for very lopsided pairs, searched in place).  Matches are counted with ballot+popcount; for unit-weight
+//     graphs the node_w gathers of the hits are queued in LDS and resolved once per 64 pairs (no dependent global load on a
+//     pair's critical path); weighted graphs / float64 weights accumulate inline and reduce with a DPP butterfly.
 // HBM traffic is the algorithmic minimum: both rows once, coalesced; rowptr/pair/outputs once.
-#include "pair_common.h"
+#include "row_intersect.h"
 
 #define PI_WAVES 4           // waves per workgroup
-#define PI_CAP 1024          // long-row entries staged per wave and pass (4 KiB of LDS per wave)
 #define PI_QCAP 256          // per-wave hit queue (1 KiB): deferred node_w gathers
-#define PI_INPLACE_RATIO 32  // long row searched in place when long > PI_CAP && long >= ratio*short
 #define PI_TICKET 4          // consecutive 64-pair chunks per ticket of the launch that scores the longer pairs (PART 2)
 #define PI_SMALL 128         // pairs whose LONGER row has at most this many entries are scored four at a time (16 lanes each).
                              // r06, 2^24 pairs of the ppa-like graph, uniform / stored edges: 64: 3.55 / 10.64 ms, 128: 3.33 / 10.41, 256: 5.20 / 11.81
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pair_scores_kernel(
         if (split != (PART != 0)) return;
     }
     constexpr bool DEFER = HAS_W && !HAS_VAL && sizeof(WT) == 4;  // unit weights: node_w gathers resolved per 64 pairs
-    __shared__ __attribute__((aligned(16))) int32_t s_rows[PI_WAVES][PI_CAP];
+    __shared__ __attribute__((aligned(16))) int32_t s_rows[PI_WAVES][ROW_CAP];
     __shared__ uint32_t s_q[PI_WAVES][PI_QCAP];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -81,9 +74,7 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pair_scores_kernel(
             static_next += n_waves;
             return c;
         }
-        unsigned int t = 0;
-        if (lane == 0) t = atomicAdd(next_chunk, 1u);
-        return (int64_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)t);
+        return take_chunk(next_chunk, lane);
     };
     auto do_chunk = [&](const int64_t chunk) {
         const int64_t p = chunk * 64 + lane;
@@ -218,85 +209,35 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pair_scores_kernel(
             int cnt = 0;
             float acc_cn = 0.0f;
             WT acc_ws = 0;
-            bool inline_sums = !DEFER;
-            if (llen > PI_CAP && (int64_t)llen >= (int64_t)slen * PI_INPLACE_RATIO) {
-                score_pair_inplace<HAS_VAL, HAS_W, WT>(col, val, node_w, bju, dju, bjv, djv, lane, cnt, acc_cn, acc_ws);
-                inline_sums = true;
-            } else {
-                int q0 = qlen;
-                int s_cursor = 0;
-                const __amdgpu_buffer_rsrc_t srs = row_rsrc(col + sbase, slen);
-                for (int l0 = 0; l0 < llen && s_cursor < slen; l0 += PI_CAP) {
-                    const int n = (llen - l0) < PI_CAP ? (llen - l0) : PI_CAP;
-                    const int lg = n > 1 ? 32 - __builtin_clz(n - 1) : 0;  // P = 2^lg >= n
-                    const int P = 1 << lg;
-                    const __amdgpu_buffer_rsrc_t lrs = row_rsrc(col + lbase + l0, n);
-                    // stage the pass: every 16-byte load of it is issued before the first LDS write
-                    v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16, 0, 0), x1, x2, x3;
-                    if (P > 256) x1 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 1024, 0, 0);
-                    if (P > 512) {
-                        x2 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 2048, 0, 0);
-                        x3 = __builtin_amdgcn_raw_buffer_load_b128(lrs, lane * 16 + 3072, 0, 0);
-                    }
-                    // ... and so is the first 64-entry slice of the short row: the pair then costs one memory round trip,
-                    // not two (most short rows ARE one slice)
-                    const int t_first = __builtin_amdgcn_raw_buffer_load_b32(srs, (s_cursor + lane) * 4, 0, 0);
-                    const int s_first = s_cursor;
-                    __builtin_amdgcn_wave_barrier();
-                    *reinterpret_cast<v4i *>(&L[4 * lane]) = pad_tail(x0, 4 * lane, n);
-                    if (P > 256) *reinterpret_cast<v4i *>(&L[256 + 4 * lane]) = pad_tail(x1, 256 + 4 * lane, n);
-                    if (P > 512) {
-                        *reinterpret_cast<v4i *>(&L[512 + 4 * lane]) = pad_tail(x2, 512 + 4 * lane, n);
-                        *reinterpret_cast<v4i *>(&L[768 + 4 * lane]) = pad_tail(x3, 768 + 4 * lane, n);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    // Long rows take several passes; both rows are sorted, so the passes co-iterate with the short row like
-                    // a merge: a cursor marks the first short element not yet settled, a pass only searches the short
-                    // elements <= its own last entry, and everything stops once the short row is used up.
-                    const bool multipass = llen > PI_CAP;
-                    const int last = multipass ? __builtin_amdgcn_readfirstlane(L[n - 1]) : 0x7fffffff;
-                    for (int s0 = s_cursor; s0 < slen; s0 += 64) {
-                        const int si = s0 + lane;
-                        const int t = s0 == s_first ? t_first : __builtin_amdgcn_raw_buffer_load_b32(srs, si * 4, 0, 0);
-                        const bool mine = si < slen && t <= last;       // a prefix of the lanes (sorted row)
-                        const int n_mine = __popcll(__ballot(mine));
-                        s_cursor = s0 + n_mine;
-                        const int pos = lb_pow2(L, lg, t);
-                        const bool found = mine && L[pos] == t;
-                        const uint64_t m = __ballot(found);
-                        if (n_mine < 64 && s0 + 64 < slen) s0 = slen;  // the rest of the short row belongs to later passes
-                        if (m == 0ull) continue;
-                        const int c = __popcll(m);
-                        cnt += c;
-                        if (DEFER) {
-                            if (qlen > PI_QCAP - 64) {
-                                flush(j, q0);
-                                q0 = 0;
-                            }
-                            const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                            if (found) q[qlen + below] = (uint32_t)t;
-                            qlen += c;
-                        } else if ((HAS_VAL || HAS_W) && found) {
-                            float vs = 1.0f, vl = 1.0f;
-                            if (HAS_VAL) { vs = val[sbase + si]; vl = val[lbase + l0 + pos]; }
-                            const float va = swapped ? vl : vs, vbv = swapped ? vs : vl;  // va = A[u,w], vbv = A[v,w]
-                            if (HAS_VAL) acc_cn += va * vbv;
-                            if (HAS_W) acc_ws += (WT)va * ((WT)vbv * node_w[t]);  // A_ entry rounded first (adamic_utils.py:17)
+            int q0 = qlen;
+            // the slice's matches: counted; unit weights queue their node_w gathers (staged pairs), the rest multiply inline
+            const bool staged = intersect_rows<ROW_CAP, ROW_INPLACE_RATIO>(
+                col, sbase, slen, lbase, llen, L, lane, [&](const bool found, const int t, const int si, const int li, const bool staged) {
+                    const uint64_t m = __ballot(found);
+                    if (m == 0ull) return;
+                    const int c = __popcll(m);
+                    cnt += c;
+                    if (DEFER && staged) {
+                        if (qlen > PI_QCAP - 64) {
+                            flush(j, q0);
+                            q0 = 0;
                         }
+                        const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+                        if (found) q[qlen + below] = (uint32_t)t;
+                        qlen += c;
+                    } else if (found) {
+                        pair_products<HAS_VAL, HAS_W, WT>(val, node_w, sbase + si, lbase + li, swapped, t, acc_cn, acc_ws);
                     }
-                }
-                if (DEFER) {
-                    if (cnt != 0 && lane == j) { my_count = cnt; my_cn = (float)cnt; my_qstart = q0; my_qcnt = qlen - q0; }
-                    continue;
-                }
+                });
+            if (DEFER && staged) {
+                if (cnt != 0 && lane == j) { my_count = cnt; my_cn = (float)cnt; my_qstart = q0; my_qcnt = qlen - q0; }
+                continue;
             }
             if (cnt != 0) {  // wave-uniform
                 float r_cn = (float)cnt;
                 if (HAS_VAL) r_cn = eps_wave_sum(acc_cn);
                 WT r_ws = 0;
-                if (HAS_W && inline_sums) r_ws = eps_wave_sum(acc_ws);
+                if (HAS_W) r_ws = eps_wave_sum(acc_ws);
                 if (lane == j) { my_count = cnt; my_cn = r_cn; my_ws = r_ws; }
             }
         }
@@ -410,9 +351,9 @@ extern "C" int eps_pair_scores_limits(int32_t *small_max, int32_t *cap, int32_t 
                                       int32_t *cls_stride)
 {
     if (small_max) *small_max = PI_SMALL;
-    if (cap) *cap = PI_CAP;
+    if (cap) *cap = ROW_CAP;
     if (queue) *queue = PI_QCAP;
-    if (inplace_ratio) *inplace_ratio = PI_INPLACE_RATIO;
+    if (inplace_ratio) *inplace_ratio = ROW_INPLACE_RATIO;
     if (ticket) *ticket = PI_TICKET;
     if (cls_stride) *cls_stride = PI_CLS_STRIDE;
     return EPS_OK;

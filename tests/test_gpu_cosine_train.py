@@ -114,6 +114,68 @@ def test_pair_backward_hub_rows(eps, dev):
     check_pair_backward(eps, A, x_dev, x_np, pairs, gvec, "hub rows")
 
 
+def switch_point_case(cap, ratio):
+    """The boundary graph and pairs of cn_list_truth (rows of 0, 1, 63, 64, 65, cap - 1, cap, cap + 1, 2 cap + 1 entries and an
+    in-place hub, every class against every class, u == v), c and g random multiples of 2^-8 in [-1, 1] (some g exactly 0), and
+    the SPARSE float64 truth: for every pair and every listed w, at the places e_u, e_v of w in rows u and v,
+    gc[e_u] += g c[e_v] and gc[e_v] += g c[e_u].  Checked here, on the CPU: the sums are exact (multiples of 2^-16 below 2^37),
+    and one-pass, several-pass and in-place pairs each occur with matches and without."""
+    import cn_list_truth as ct
+    A, special, stranger = ct.boundary_graph(cap, ratio)
+    u, v = ct.boundary_pairs(A, special, stranger)
+    ptr, w = ct.cn_lists(A, u, v)
+    n, nnz = A.shape[0], A.nnz
+    rng = np.random.default_rng(31)
+    c = rng.integers(-256, 257, nnz).astype(np.float64) / 256.0
+    g = rng.integers(-256, 257, len(u)).astype(np.float64) / 256.0
+    g[rng.integers(0, len(u), len(u) // 10)] = 0.0
+    g[0] = 1.0                                                                     # (max |g| is known: the scale is 2^46)
+    keys = np.repeat(np.arange(n, dtype=np.int64), np.diff(A.indptr)) * n + A.indices      # ascending: CSR with sorted rows
+    b = np.repeat(np.arange(len(u)), np.diff(ptr))
+    eu = np.searchsorted(keys, u[b].astype(np.int64) * n + w)
+    ev = np.searchsorted(keys, v[b].astype(np.int64) * n + w)
+    assert np.array_equal(A.indices[eu], w) and np.array_equal(A.indices[ev], w)
+    truth = np.zeros(nnz, np.float64)
+    np.add.at(truth, eu, g[b] * c[ev])
+    np.add.at(truth, ev, g[b] * c[eu])                                             # (u == v: the one entry receives both)
+    reached = np.zeros(nnz, bool)
+    reached[eu] = reached[ev] = True
+    assert np.array_equal(truth * 65536.0, np.round(truth * 65536.0)) and np.abs(truth).max() < 2.0 ** 37
+    assert (g == 0.0).any() and np.abs(g).max() == 1.0 and not truth[~reached].any()
+    deg, cnt = np.diff(A.indptr), np.diff(ptr)
+    lo, hi = np.minimum(deg[u], deg[v]), np.maximum(deg[u], deg[v])
+    inplace = (hi > cap) & (hi >= lo * ratio) & (lo > 0)
+    for path in (inplace, (hi > cap) & ~inplace & (lo > 0), (hi <= cap) & (lo > 0)):
+        assert (cnt[path] > 0).any() and (cnt[path] == 0).any()
+        assert ((cnt > 0) & path & (g != 0.0)).any()                               # ... and some of the matches carry a gradient
+    assert deg[special].tolist() == ct.boundary_lengths(cap, ratio)
+    return A, u, v, c.astype(np.float32), g.astype(np.float32), truth, reached
+
+
+def test_pair_backward_switch_points(eps, dev):
+    """The backward at every switch point of its walk (csrc/row_intersect.h), bit for bit.  Every term g c 2^46 is an integer
+    (g and c are multiples of 2^-8, the scale is 2^(60 - 12 - 1 - 1) for about 1,100 pairs with max |g| = 1), every fixed-point
+    sum is exact, pb_convert_kernel rounds once: gc has the bits of float32(truth), an entry no pair reaches is 0, and the order
+    of the list does not matter."""
+    from eps_amd import ops
+    cap, ratio = ops.pair_cn_list_limits()
+    A, u, v, c, g, truth, reached = switch_point_case(cap, ratio)
+    rowptr = torch.from_numpy(A.indptr.astype(np.int64)).to(dev)
+    col = torch.from_numpy(A.indices.astype(np.int32)).to(dev)
+    cd, gd = torch.from_numpy(c).to(dev), torch.from_numpy(g).to(dev)
+    ud, vd = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
+    gc = ops.pair_cn_backward(rowptr, col, cd, ud, vd, gd)
+    got, want = gc.cpu().numpy(), truth.astype(np.float32)
+    diff = got.view(np.int32) != want.view(np.int32)
+    print(f"[cosine-train] switch points: {len(u)} pairs, {A.shape[0]} nodes, {int(reached.sum())} entries reached, "
+          f"{int(diff.sum())} entries differ from float32(truth) in their bits")
+    assert not diff.any()
+    assert not got[~reached].any(), "an entry no pair reaches must stay zero"
+    perm = torch.from_numpy(np.random.default_rng(5).permutation(len(u))).to(dev)
+    shuffled = ops.pair_cn_backward(rowptr, col, cd, ud[perm].contiguous(), vd[perm].contiguous(), gd[perm].contiguous())
+    assert torch.equal(gc.view(torch.int32), shuffled.view(torch.int32)), "the result depends on the order of the pair list"
+
+
 def test_pair_backward_zero_gradient_and_empty_list(eps, dev):
     from eps_amd import ops
     A = random_graph(100, 400, seed=1)

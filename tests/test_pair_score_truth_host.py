@@ -86,12 +86,13 @@ def test_limit_queries(eps):
         assert re.search(r"\bint %s\s*\(" % name, text) and sig[name] == (ctypes.c_int, [pi32] * k) and hasattr(lib, name)
         assert getattr(lib, name)(*[None] * k) == 0                                # (a NULL pointer skips that value)
     assert lib.eps_version() == eps._lib.ABI_VERSION == 7
-    src = {f: open(os.path.join(ROOT, "edge-proposal-sets_amd", "csrc", f)).read() for f in ("pair_intersect.hip", "pair_grouped.hip", "rescore.hip")}
+    src = {f: open(os.path.join(ROOT, "edge-proposal-sets_amd", "csrc", f)).read() for f in ("pair_intersect.hip", "row_intersect.h", "pair_grouped.hip", "rescore.hip")}
 
     def define(f, name):
         return int(eval(re.search(r"^#define %s\s+(\(?[0-9 <]+\)?)" % name, src[f], flags=re.M).group(1)))          # noqa: S307
-    assert ops.pair_scores_limits() == tuple(define("pair_intersect.hip", d) for d in
-                                             ("PI_SMALL", "PI_CAP", "PI_QCAP", "PI_INPLACE_RATIO", "PI_TICKET", "PI_CLS_STRIDE"))
+    assert ops.pair_scores_limits() == (define("pair_intersect.hip", "PI_SMALL"), define("row_intersect.h", "ROW_CAP"),
+                                        define("pair_intersect.hip", "PI_QCAP"), define("row_intersect.h", "ROW_INPLACE_RATIO"),
+                                        define("pair_intersect.hip", "PI_TICKET"), define("pair_intersect.hip", "PI_CLS_STRIDE"))
     assert ops.pair_scores_grouped_limits() == (define("pair_grouped.hip", "PG_CHUNK"), define("pair_grouped.hip", "PG_QCAP"),
                                                 define("pair_grouped.hip", "PG_MAX_WORDS") * 32, define("pair_grouped.hip", "PG_RING"))
     assert ops.rescore_limits() == tuple(define("rescore.hip", d) for d in ("RS_BITS", "RS_SHORT", "RS_CHUNK"))
