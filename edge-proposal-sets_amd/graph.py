@@ -59,7 +59,10 @@ def merge_keys(extra_edges: torch.Tensor) -> torch.Tensor:
 
 
 class CSRGraph:
-    """Coalesced CSR matrix [n_rows, n_cols]; float32 values or implicit ones."""
+    """Coalesced CSR matrix [n_rows, n_cols]; float32 values or implicit ones.
+    A stored self loop (v, v) is an entry like any other: it counts in degrees and column sums -- so in the AA / RA weight of
+    its node --, it never makes a candidate (filter.py:96-109 removes the diagonal of A @ A), and ``to_symmetric`` doubles its
+    value as the reference's coalesce does (tests/test_gpu_self_loops.py holds every filter path to the oracle on such graphs)."""
 
     def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, val: Optional[torch.Tensor], n_rows: int,
                  n_cols: int):

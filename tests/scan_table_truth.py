@@ -33,11 +33,13 @@ def bit_length(x):
 
 
 # ------------------------------------------------------------------------------------------------------------ graphs
-def csr_from_edges(n, r, c):
-    """(rowptr, col) of the symmetric, loop-free, deduplicated graph with these edges; rows sorted."""
+def csr_from_edges(n, r, c, keep_loops=False):
+    """(rowptr, col) of the symmetric, deduplicated graph with these edges; rows sorted.  Loop-free unless ``keep_loops``: an
+    edge (v, v) then stays, as ONE diagonal entry -- an entry like any other, and its own mirror."""
     r, c = _i64(r), _i64(c)
-    keep = r != c
-    r, c = r[keep], c[keep]
+    if not keep_loops:
+        keep = r != c
+        r, c = r[keep], c[keep]
     key = np.unique(np.concatenate([r * n + c, c * n + r]))
     rows, col = key // n, key % n
     rowptr = np.zeros(n + 1, np.int64)
@@ -51,7 +53,8 @@ def row_of(rowptr):
 
 
 def revpos(rowptr, col):
-    """revpos[e] for e = (v, j), w = col[e]: the position of v in row w (the graph is symmetric, rows are sorted)."""
+    """revpos[e] for e = (v, j), w = col[e]: the position of v in row w (the graph is symmetric, rows are sorted).  A diagonal entry
+    (v, v) is its own mirror: its revpos is its position in row v, the number of entries of that row below v."""
     rowptr, col = _i64(rowptr), _i64(col)
     n = len(rowptr) - 1
     row = row_of(rowptr)
@@ -62,7 +65,7 @@ def revpos(rowptr, col):
 
 
 def half_paths(rowptr, col):
-    """Two-hop paths v - w - u with u < v, per column v."""
+    """Two-hop paths v - w - u with u < v, per column v (a diagonal entry gives the paths v - v - u: they end on known edges)."""
     rowptr, col = _i64(rowptr), _i64(col)
     out = np.zeros(len(rowptr) - 1, np.int64)
     np.add.at(out, row_of(rowptr), revpos(rowptr, col))
@@ -480,19 +483,20 @@ def rewalk(recs, variant):
 
 
 # ------------------------------------------------------------------------------------- the graphs the GPU tests use
-def relabel(rowptr, col, new_of_old):
-    """The same graph with node i renamed new_of_old[i] (rows sorted again)."""
+def relabel(rowptr, col, new_of_old, keep_loops=False):
+    """The same graph with node i renamed new_of_old[i] (rows sorted again; diagonal entries are dropped unless ``keep_loops``)."""
     new = _i64(new_of_old)
-    return csr_from_edges(len(new), new[row_of(rowptr)], new[_i64(col)])
+    return csr_from_edges(len(new), new[row_of(rowptr)], new[_i64(col)], keep_loops)
 
 
-def hubs_first(rowptr, col, last=False):
-    """Nodes renamed by falling degree (stable); ``last``: by rising degree, the mirror image."""
+def hubs_first(rowptr, col, last=False, keep_loops=False):
+    """Nodes renamed by falling degree (stable); ``last``: by rising degree, the mirror image.  The degree is the row length: a
+    stored diagonal entry counts in it."""
     deg = np.diff(_i64(rowptr))
     order = np.argsort(-deg, kind="stable")
     inv = np.empty_like(order)
     inv[order] = np.arange(len(order))
-    return relabel(rowptr, col, len(order) - 1 - inv if last else inv)
+    return relabel(rowptr, col, len(order) - 1 - inv if last else inv, keep_loops)
 
 
 def star(leaves, hub_first):
