@@ -5,7 +5,8 @@ against the model its own comment states, in numpy / torch, exactly:
                           value only changes the end Katz expands a pair from -- no end-to-end result shows it)
   ops.row_window_splits   splits[k * N + w] = entries of row w below id (k + 1) * win_ids     (csrc/filter_scan.hip)
   ops.compact_at_least    the slots with key >= 0 and score >= *cut, in any order; a NULL cut keeps every survivor
-                          (csrc/topk_select.hip)"""
+                          (csrc/topk_select.hip; ops.compact_between, the same kernel with an upper end, its chunk edges and
+                          its second grid-stride trip: tests/test_gpu_shard_kernels.py)"""
 import numpy as np
 import pytest
 import torch
