@@ -69,4 +69,32 @@ __device__ __forceinline__ double eps_wave_sum(double x)
 }
 
 __device__ __forceinline__ int eps_lane() { return threadIdx.x & 63; }
+
+// Inclusive prefix of x over the wave's lanes (lane = 0..63 of the caller) ...
+template <typename T>
+__device__ __forceinline__ T eps_wave_incl_scan(T x, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(x, o);
+        if (lane >= o) x += up;
+    }
+    return x;
+}
+// ... and the exclusive one; total = the wave's sum, in every lane.
+template <typename T>
+__device__ __forceinline__ T eps_wave_excl_scan(T x, int lane, T &total)
+{
+    const T incl = eps_wave_incl_scan(x, lane);
+    total = __shfl(incl, 63);
+    return incl - x;
+}
+
+// LDS written by some lanes of the wave is read by others after this.
+__device__ __forceinline__ void lds_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 #endif

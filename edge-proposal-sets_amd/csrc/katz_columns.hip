@@ -12,7 +12,7 @@
 // again) and many light columns share one unit.  Per (column, part of its candidates):
 //   1. y2's support is inserted into an open-addressing table keyed by node id (atomicCAS: the slot a key lands in depends on
 //      the order, nothing read from the table does).  The support is walked over A^T from v: x in row v of A^T, w in row x
-//      of A^T, the two-paths flattened over the lanes as kz_walk does.  Its size is at most ub = min(paths_in[v], n): the
+//      of A^T, the two-paths flattened over the lanes (flat_rows.h).  Its size is at most ub = min(paths_in[v], n): the
 //      table gets >= 2 ub slots (a power of two), in LDS when ub <= KC_LDS_CAP (KC_LDS_SLOTS slots, load <= 0.5625), else in
 //      this workgroup's region of the caller's workspace.
 //   2. one owner thread per slot sums y2[w] = sum_x A[w,x] * A[x,v] in ascending x: row w of A against the sorted row v of
@@ -23,6 +23,7 @@
 //      adding its entries j = l, l + T, ... in order, the team reducing with a fixed butterfly.
 // Arithmetic: float64 throughout, rounded to float32 once.  A score therefore depends on the graph, the coefficients and the
 // pair alone -- not on the block, the slice, the launch or the workgroup: bitwise reproducible, and equal under any split.
+#include "flat_rows.h"
 #include "pair_common.h"
 #include <math.h>
 
@@ -41,14 +42,8 @@
 #define KC_T1_DEG 8                     // rows up to this length: one lane
 #define KC_T8_DEG 128                   // ... up to this length: 8 lanes; longer: the wave
 
-struct KcCsr {
-    const int64_t *__restrict__ rp;
-    const int32_t *__restrict__ col;
-    const float *__restrict__ val;
-};
-
 struct KcLds {
-    double val[KC_LDS_SLOTS];
+    unsigned long long val[KC_LDS_SLOTS];   // y2 as float64 bits (a unit-valued graph: the two-path count until step 2)
     int32_t key[KC_LDS_SLOTS];
     int32_t rkey[KC_ROW_CAP];
     float rval[KC_ROW_CAP];
@@ -62,68 +57,12 @@ struct KcLds {
     int fail;
 };
 
-__device__ __forceinline__ void kc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A global table is written with atomics (they execute in L2) and read back by other waves of the workgroup: every access
-// goes to L2 (agent scope), never through a vector-L1 line that an earlier column left behind.
-template <bool IN_LDS>
-__device__ __forceinline__ int32_t kc_ld_key(const int32_t *p)
-{
-    if (IN_LDS) return *p;
-    return __hip_atomic_load((int32_t *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool IN_LDS>
-__device__ __forceinline__ unsigned long long kc_ld_bits(const double *p)
-{
-    if (IN_LDS) return *(const unsigned long long *)p;
-    return __hip_atomic_load((unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool IN_LDS>
-__device__ __forceinline__ void kc_st_key(int32_t *p, int32_t x)
-{
-    if (IN_LDS) *p = x;
-    else __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool IN_LDS>
-__device__ __forceinline__ void kc_st_bits(double *p, unsigned long long x)
-{
-    if (IN_LDS) *(unsigned long long *)p = x;
-    else __hip_atomic_store((unsigned long long *)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t kc_hash(int32_t w, int lg) { return ((uint32_t)w * 2654435761u) >> (32 - lg); }
-
-// The slot of key w (inserted if new), or -1 when the table is full (it never is while the support bound holds).
-__device__ __forceinline__ int kc_insert(int32_t *keys, int lg, int32_t w)
-{
-    const uint32_t mask = (1u << lg) - 1;
-    uint32_t h = kc_hash(w, lg);
-    for (uint32_t t = 0; t <= mask; ++t) {
-        const int32_t prev = atomicCAS(&keys[h], -1, w);
-        if (prev == -1 || prev == w) return (int)h;
-        h = (h + 1) & mask;
-    }
-    return -1;
-}
-
 // y2[w]; 0 when w is not in the table.
 template <bool IN_LDS>
-__device__ __forceinline__ double kc_find(const int32_t *keys, const double *vals, int lg, int32_t w)
+__device__ __forceinline__ double kc_find(const int32_t *keys, const unsigned long long *vals, int lg, int32_t w)
 {
-    const uint32_t mask = (1u << lg) - 1;
-    uint32_t h = kc_hash(w, lg);
-    for (uint32_t t = 0; t <= mask; ++t) {
-        const int32_t k = kc_ld_key<IN_LDS>(keys + h);
-        if (k == w) return __builtin_bit_cast(double, kc_ld_bits<IN_LDS>(vals + h));
-        if (k < 0) return 0.0;
-        h = (h + 1) & mask;
-    }
-    return 0.0;
+    const int slot = tbl_find_slot<IN_LDS>(keys, lg, w);
+    return slot < 0 ? 0.0 : __builtin_bit_cast(double, tbl_ld<IN_LDS>(vals + slot));
 }
 
 // sum over the common keys x of two sorted rows of a[x] * b[x], in ascending x; the shorter row is walked, the longer searched.
@@ -158,9 +97,9 @@ __device__ __forceinline__ int kc_table_lg(int64_t ub)
 // Candidates [p0, p1) of column v (all of them in that column).  Every thread of the workgroup calls this with the same
 // arguments; the table is free again when it returns.
 template <bool IN_LDS, bool UNIT>
-__device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t n, int32_t v, int64_t p0, int64_t p1,
+__device__ __forceinline__ void kc_column(const EpsCsr A, const EpsCsr AT, int64_t n, int32_t v, int64_t p0, int64_t p1,
                                           const int32_t *__restrict__ cand_u, double c1, double c2, double c3, KcLds &S,
-                                          int32_t *keys, double *vals, int lg, float *__restrict__ out)
+                                          int32_t *keys, unsigned long long *vals, int lg, float *__restrict__ out)
 {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -177,8 +116,8 @@ __device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t
     }
     const int slots = 1 << lg;
     for (int i = tid; i < slots; i += KC_THREADS) {
-        kc_st_key<IN_LDS>(keys + i, -1);
-        kc_st_bits<IN_LDS>(vals + i, 0ull);
+        tbl_st<IN_LDS>(keys + i, (int32_t)-1);
+        tbl_st<IN_LDS>(vals + i, 0ull);
     }
     const bool staged = md <= KC_ROW_CAP;
     if (staged)
@@ -198,29 +137,22 @@ __device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t
         const int32_t x = act ? AT.col[mb + j] : 0;
         const int64_t xs = AT.rp[x];
         const int64_t xd = act ? AT.rp[x + 1] - xs : 0;
-        int64_t inc = xd;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        const int64_t tot = __shfl(inc, 63);
-        kc_wave_sync();
-        S.excl[wib][lane] = inc - xd;
+        int64_t tot;
+        const int64_t xex = eps_wave_excl_scan(xd, lane, tot);
+        lds_wave_sync();
+        S.excl[wib][lane] = xex;
         S.start[wib][lane] = xs;
-        kc_wave_sync();
+        lds_wave_sync();
         const int64_t *ex = S.excl[wib];
         for (int64_t t0 = 0; t0 < tot; t0 += 64) {
             const int64_t t = t0 + lane;
             if (t < tot) {
-                int k = 0;                     // the last slice entry whose exclusive prefix is <= t (it has degree > 0)
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1)
-                    if (ex[k + step] <= t) k += step;
+                const int k = flat_owner(ex, t);           // t's x (it has degree > 0)
                 const int32_t w = AT.col[S.start[wib][k] + (t - ex[k])];
-                const int slot = kc_insert(keys, lg, w);
+                bool won;                      // (not needed: a key's value starts at 0 whoever inserts it)
+                const int slot = tbl_insert(keys, lg, w, &won);        // -1: never while the support bound holds
                 if (slot < 0) S.fail = 1;
-                else if (UNIT) atomicAdd((unsigned long long *)(vals + slot), 1ull);
+                else if (UNIT) atomicAdd(vals + slot, 1ull);
             }
         }
     }
@@ -233,16 +165,16 @@ __device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t
 
     // 2. y2 of every key, by the thread that owns its slot
     for (int i = tid; i < slots; i += KC_THREADS) {
-        const int32_t w = kc_ld_key<IN_LDS>(keys + i);
+        const int32_t w = tbl_ld<IN_LDS>(keys + i);
         if (w < 0) continue;
         double y;
         if (UNIT) {
-            y = (double)kc_ld_bits<IN_LDS>(vals + i);
+            y = (double)tbl_ld<IN_LDS>(vals + i);
         } else {
             const int64_t wb = A.rp[w];
             y = kc_sorted_dot(A.col + wb, A.val ? A.val + wb : nullptr, (int)(A.rp[w + 1] - wb), rk, rv, md);
         }
-        kc_st_bits<IN_LDS>(vals + i, __builtin_bit_cast(unsigned long long, y));
+        tbl_st<IN_LDS>(vals + i, __builtin_bit_cast(unsigned long long, y));
     }
     __syncthreads();
 
@@ -278,12 +210,12 @@ __device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t
             out[p] = (float)(base + c3 * acc);
         }
         if ((m2 | m3) == 0) continue;
-        kc_wave_sync();                        // (the previous step's teams are done with the arrays)
+        lds_wave_sync();                        // (the previous step's teams are done with the arrays)
         S.crs[wib][lane] = rs;
         S.cdeg[wib][lane] = deg;
         S.cbase[wib][lane] = base;
         if (cls == 2) S.list[wib][__popcll(m2 & ((1ull << lane) - 1))] = lane;
-        kc_wave_sync();
+        lds_wave_sync();
         const int n2 = __popcll(m2);
         for (int i0 = 0; i0 < n2; i0 += 8) {
             const int ci = i0 + (lane >> 3);
@@ -323,7 +255,7 @@ __device__ __forceinline__ void kc_column(const KcCsr A, const KcCsr AT, int64_t
 
 template <bool UNIT>
 __global__ __launch_bounds__(KC_THREADS) void katz_columns_kernel(
-    const KcCsr A, const KcCsr AT, const int64_t *__restrict__ paths_in, int64_t n, int64_t v_lo, int64_t n_cols,
+    const EpsCsr A, const EpsCsr AT, const int64_t *__restrict__ paths_in, int64_t n, int64_t v_lo, int64_t n_cols,
     const int64_t *__restrict__ colptr, const int32_t *__restrict__ cand_u, int64_t n_cand, double c1, double c2, double c3,
     int64_t max_support, int64_t chunk, char *__restrict__ tables, int glg, unsigned int *__restrict__ next_unit,
     float *__restrict__ out)
@@ -332,7 +264,7 @@ __global__ __launch_bounds__(KC_THREADS) void katz_columns_kernel(
     const int tid = threadIdx.x;
     const int64_t n_units = (n_cand + chunk - 1) / chunk;
     // this workgroup's global table: values, then keys
-    double *gval = tables ? (double *)(tables + (int64_t)blockIdx.x * (((int64_t)12) << glg)) : nullptr;
+    unsigned long long *gval = tables ? (unsigned long long *)(tables + (int64_t)blockIdx.x * (((int64_t)12) << glg)) : nullptr;
     int32_t *gkey = tables ? (int32_t *)(gval + ((int64_t)1 << glg)) : nullptr;
     for (;;) {
         __syncthreads();
@@ -342,12 +274,7 @@ __global__ __launch_bounds__(KC_THREADS) void katz_columns_kernel(
         if (unit >= n_units) break;
         int64_t p = unit * chunk;
         const int64_t pe = p + chunk < n_cand ? p + chunk : n_cand;
-        int64_t lo = 0, hi = n_cols - 1;       // the last column whose first candidate is at or before p
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (colptr[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        int64_t c = lo;
+        int64_t c = column_of(colptr, 0, n_cols - 1, p);
         while (p < pe) {
             while (c + 1 < n_cols && colptr[c + 1] <= p) ++c;      // (columns without candidates)
             const int64_t ce = colptr[c + 1];
@@ -439,7 +366,7 @@ extern "C" int eps_katz_column_scores(const int64_t *rowptr, const int32_t *col,
     unsigned int *next_unit = nullptr;
     const int crc = eps_take_counter(&next_unit, s, "eps_katz_column_scores");
     if (crc) return crc;
-    const KcCsr A{rowptr, col, val}, AT{rowptr_t, col_t, val_t};
+    const EpsCsr A{rowptr, col, val}, AT{rowptr_t, col_t, val_t};
     const int64_t n_units = (n_cand + per_unit - 1) / per_unit;
     int64_t blocks = kc_groups(max_support);
     if (blocks > eps_num_cus()) blocks = eps_num_cus();

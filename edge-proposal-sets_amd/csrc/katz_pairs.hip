@@ -23,7 +23,8 @@
 // Arithmetic: each lane accumulates its terms in float64, the wave reduces with a fixed butterfly, segments are added in
 // a fixed order, and the result is rounded to float32 once.  Which pairs are split, and how, depends on the graph and the
 // pair alone, so two launches give bitwise equal outputs (the list's order differs between launches, nothing read from it does).
-#include "row_intersect.h"      // (lds_wave_sync, take_chunk; pair_common.h)
+#include "flat_rows.h"
+#include "row_intersect.h"      // (take_chunk; pair_common.h)
 #include <math.h>
 
 #define KZ_WAVES 4
@@ -31,12 +32,6 @@
 #define KZ_BIG 2048          // walks longer than this (two-paths) are split over several waves
 #define KZ_SEG 1024          // target two-paths per segment of a split walk
 #define KZ_NSEG 16           // at most this many segments per pair
-
-struct KzCsr {
-    const int64_t *__restrict__ rp;
-    const int32_t *__restrict__ col;
-    const float *__restrict__ val;
-};
 
 struct KzLds {
     int32_t key[KZ_WAVES][KZ_MAP_CAP];
@@ -74,7 +69,7 @@ __device__ __forceinline__ double kz_lookup(const int32_t *keys, const float *va
 
 // The part of pair (a, b)'s score held by the two-paths [t_lo, t_hi) of the walk over W from a; the map is row b of M
 // (M = W^T).  `first` adds the c1 and c2 terms (they belong to the first segment only).  Returns the wave's total in every lane.
-__device__ double kz_walk(const KzCsr W, const KzCsr M, int32_t a, int32_t b, int64_t t_lo, int64_t t_hi, bool first,
+__device__ double kz_walk(const EpsCsr W, const EpsCsr M, int32_t a, int32_t b, int64_t t_lo, int64_t t_hi, bool first,
                           double c1, double c2, double c3, KzLds &S, int wib, int lane)
 {
     const int64_t mb = M.rp[b];
@@ -109,18 +104,13 @@ __device__ double kz_walk(const KzCsr W, const KzCsr M, int32_t a, int32_t b, in
             const double m = kz_lookup(keys, vals, md, w, act);
             acc += c2 * ((double)aw * m);
         }
-        int64_t inc = wd;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        const int64_t tot = __shfl(inc, 63);
+        int64_t tot;
+        const int64_t wex = eps_wave_excl_scan(wd, lane, tot);
         const int64_t lo = t_lo > base ? t_lo - base : 0;
         const int64_t hi = t_hi - base < tot ? t_hi - base : tot;
         if (lo < hi) {
             lds_wave_sync();
-            S.excl[wib][lane] = inc - wd;
+            S.excl[wib][lane] = wex;
             S.start[wib][lane] = ws;
             S.aw[wib][lane] = aw;
             lds_wave_sync();
@@ -128,10 +118,7 @@ __device__ double kz_walk(const KzCsr W, const KzCsr M, int32_t a, int32_t b, in
             for (int64_t t0 = lo; t0 < hi; t0 += 64) {
                 const int64_t t = t0 + lane;
                 const bool on = t < hi;
-                int k = 0;                  // the last slice entry whose exclusive prefix is <= t: t's w (it has degree > 0)
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1)
-                    if (ex[k + step] <= t) k += step;
+                const int k = flat_owner(ex, t);        // t's w (it has degree > 0)
                 int32_t x = 0;
                 double wx = 0.0;
                 if (on) {
@@ -152,7 +139,7 @@ __device__ __forceinline__ int32_t kz_readlane(int32_t x, int l) { return __buil
 
 // One wave per pair, 64-pair chunks handed out dynamically; pairs with long walks are listed for katz_split_kernel.
 __global__ __launch_bounds__(KZ_WAVES * 64) void katz_pairs_kernel(
-    const KzCsr A, const KzCsr AT, const int64_t *__restrict__ paths_out, const int64_t *__restrict__ paths_in,
+    const EpsCsr A, const EpsCsr AT, const int64_t *__restrict__ paths_out, const int64_t *__restrict__ paths_in,
     const int32_t *__restrict__ pu, const int32_t *__restrict__ pv, int64_t n_pairs, double c1, double c2, double c3,
     unsigned int *__restrict__ next_chunk, unsigned int *__restrict__ n_big, int32_t *__restrict__ big_list,
     float *__restrict__ out)
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(KZ_WAVES * 64) void katz_pairs_kernel(
 // One wave per (listed pair, segment): item i is segment i % KZ_NSEG of big_list[i / KZ_NSEG].  Segments past the pair's
 // count write 0.
 __global__ __launch_bounds__(KZ_WAVES * 64) void katz_split_kernel(
-    const KzCsr A, const KzCsr AT, const int64_t *__restrict__ paths_out, const int64_t *__restrict__ paths_in,
+    const EpsCsr A, const EpsCsr AT, const int64_t *__restrict__ paths_out, const int64_t *__restrict__ paths_in,
     const int32_t *__restrict__ pu, const int32_t *__restrict__ pv, double c1, double c2, double c3,
     const unsigned int *__restrict__ n_big, const int32_t *__restrict__ big_list, double *__restrict__ part)
 {
@@ -287,7 +274,7 @@ extern "C" int eps_katz_pair_scores(const int64_t *rowptr, const int32_t *col, c
     if (crc) return crc;
     int32_t *big_list = (int32_t *)workspace;
     double *part = (double *)((char *)workspace + kz_list_bytes(n_pairs));
-    const KzCsr A{rowptr, col, val}, AT{rowptr_t, col_t, val_t};
+    const EpsCsr A{rowptr, col, val}, AT{rowptr_t, col_t, val_t};
     const int64_t n_chunks = (n_pairs + 63) / 64;
     int64_t blocks = (n_chunks + KZ_WAVES - 1) / KZ_WAVES;
     const int64_t max_blocks = (int64_t)eps_num_cus() * 4;

@@ -28,6 +28,7 @@
 //   alone, not on launch shape, place in the batch, route or orientation.  Lists up to LC_SHORT entries are summed by one lane
 //   each (the same tree, written out), longer ones by the whole wave; chunks by ticket, so one 40,000-entry list occupies one
 //   wave while the others go on.
+#include "flat_rows.h"
 #include "row_intersect.h"
 
 #include <math.h>
@@ -61,28 +62,6 @@ __device__ __forceinline__ double lc_term(int index, int32_t g, int64_t d)
     if (index == LC_CAA) return (double)g / log2((double)d);
     if (index == LC_CRA) return (double)g / (double)d;
     return 0.0;
-}
-
-// Exclusive prefix of x over the wave's lanes; total = the sum.
-__device__ __forceinline__ int lc_prefix(int x, int lane, int &total)
-{
-    int incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    total = __shfl(incl, 63);
-    return incl - x;
-}
-
-// The last m of 0..63 with E[m] <= t (E ascends, E[0] == 0 <= t): the owner of item t of rows laid end to end.
-__device__ __forceinline__ int lc_owner(const int32_t *E, int t)
-{
-    int pos = 0;
-#pragma unroll
-    for (int step = 32; step > 0; step >>= 1) pos += (E[pos + step] <= t) ? step : 0;
-    return pos;
 }
 
 __device__ __forceinline__ uint64_t lc_lanes(int lo, int hi) { return (~0ull >> (63 - hi)) & (~0ull << lo); }   // 0 <= lo <= hi <= 63
@@ -154,7 +133,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
             if (!ok) bad = true;
         }
         int n_items = 0;
-        const int off = lc_prefix(ok ? c * (c - 1) : 0, lane, n_items);
+        const int off = eps_wave_excl_scan(ok ? c * (c - 1) : 0, lane, n_items);
         E[lane] = off;
 #pragma unroll
         for (int k = 0; k < LC_SHORT; ++k) L[k * 64 + lane] = 0;  // counts of (list s, entry i) at L[s * LC_SHORT + i]
@@ -162,7 +141,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
         for (int t0 = 0; t0 < n_items; t0 += 64) {
             const int t = t0 + lane;
             const bool act = t < n_items;
-            const int s = act ? lc_owner(E, t) : 0;
+            const int s = act ? flat_owner(E, t) : 0;
             const int cs = __shfl(c, s);
             const int64_t bs = lc_shfl64(sb, s);
             const int cm1 = act ? cs - 1 : 1;                // (an owner has c >= 2)
@@ -234,13 +213,13 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                     const bool inplace = am && d >= 64 && (int64_t)d >= (int64_t)n * ROW_INPLACE_RATIO;
                     const int fd = inplace ? 0 : d;          // streamed rows, laid end to end (each below 32 * ROW_CAP entries)
                     int n_flat = 0;
-                    E[lane] = lc_prefix(fd, lane, n_flat);
+                    E[lane] = eps_wave_excl_scan(fd, lane, n_flat);
                     ACC[lane] = 0;
                     lds_wave_sync();
                     for (int t0 = 0; t0 < n_flat; t0 += 64) {
                         const int t = t0 + lane;
                         const bool act = t < n_flat;
-                        const int m = act ? lc_owner(E, t) : 0;
+                        const int m = act ? flat_owner(E, t) : 0;
                         const int em = E[m];
                         const int dm = __shfl(fd, m);
                         const int wm = __shfl(wi, m);

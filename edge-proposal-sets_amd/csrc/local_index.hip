@@ -19,7 +19,7 @@
 //   waits on another: the same inputs give the same bits in the same places.
 // Both are streaming kernels (4 B id + 4 B count in, 4 B score out per candidate; 16-byte accesses where four consecutive
 // slots are live in one column), rowptr is the only gathered table.
-#include "eps_common.h"
+#include "flat_rows.h"      // (column_of)
 
 #include <math.h>
 
@@ -114,16 +114,6 @@ struct LiBlock {
     int64_t *__restrict__ slice_ofs;          // [n_slices + 1]: survivors per slice, then their exclusive prefix
 };
 
-// The last column of [lo, hi] whose segment starts at or before slot p (colptr ascends; colptr[lo] <= p).
-__device__ __forceinline__ int64_t li_column_of(const int64_t *__restrict__ colptr, int64_t lo, int64_t hi, int64_t p)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (colptr[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 #define LI_MODE_SCORE 0     // score[] only
 #define LI_MODE_COUNT 1     // survivors per slice (and score[] when given)
 #define LI_MODE_FILL 2      // the survivors, at their places
@@ -144,8 +134,8 @@ __global__ __launch_bounds__(LI_THREADS) void local_index_columns_kernel(const L
     const float bar = MODE == LI_MODE_SCORE ? 0.0f : *B.bar;
     const float qnan = __builtin_nanf("");
     // the columns this slice meets (the same for every thread)
-    const int64_t c_first = li_column_of(B.colptr, 0, B.n_cols - 1, s0);
-    const int64_t c_last = li_column_of(B.colptr, c_first, B.n_cols - 1, s1 - 1);
+    const int64_t c_first = column_of(B.colptr, 0, B.n_cols - 1, s0);
+    const int64_t c_last = column_of(B.colptr, c_first, B.n_cols - 1, s1 - 1);
     uint32_t n_over = 0;
     int buf = 0;
 
@@ -155,7 +145,7 @@ __global__ __launch_bounds__(LI_THREADS) void local_index_columns_kernel(const L
         bool live[LI_VEC] = {false, false, false, false};
         bool whole = false;
         if (p0 < s1) {
-            int64_t c = li_column_of(B.colptr, c_first, c_last, p0);
+            int64_t c = column_of(B.colptr, c_first, c_last, p0);
             int64_t next = c + 1 < B.n_cols ? B.colptr[c + 1] : B.n_slots;
             if (next > B.n_slots) next = B.n_slots;
             int64_t end = B.counts ? B.colptr[c] + B.counts[c] : next;      // the counted entries of column c end here
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(LI_THREADS) void local_index_columns_kernel(const L
                     s[j] = 0.0f;
                     if (p >= s1) continue;
                     if (p >= next) {                                        // the next column with a segment at or before p
-                        c = li_column_of(B.colptr, c + 1, c_last, p);
+                        c = column_of(B.colptr, c + 1, c_last, p);
                         next = c + 1 < B.n_cols ? B.colptr[c + 1] : B.n_slots;
                         if (next > B.n_slots) next = B.n_slots;
                         end = B.counts ? B.colptr[c] + B.counts[c] : next;
@@ -224,12 +214,7 @@ __global__ __launch_bounds__(LI_THREADS) void local_index_columns_kernel(const L
             continue;
         }
         // fill: the survivors of this step in slot order -- an exclusive prefix over the workgroup's threads
-        uint32_t incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const uint32_t incl = eps_wave_incl_scan(own, lane);
         if (lane == 63) s_w[buf][wv] = incl;
         __syncthreads();
         uint32_t front = 0, all = 0;
@@ -281,12 +266,7 @@ __global__ __launch_bounds__(LI_SCAN_THREADS) void local_index_scan_kernel(int64
 #pragma unroll
         for (int j = 0; j < 4; ++j) x[j] = i + j < n ? ofs[i + j] : 0;
         const int64_t own = x[0] + x[1] + x[2] + x[3];
-        int64_t incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const int64_t incl = eps_wave_incl_scan(own, lane);
         if (lane == 63) s_w[buf][wv] = incl;
         __syncthreads();
         int64_t front = 0, all = 0;

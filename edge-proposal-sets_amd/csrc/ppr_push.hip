@@ -17,7 +17,7 @@
 // lengths, one search per entry), the workgroup walks each long row together; every entry adds its share to r[w] with a 64-bit
 // integer atomic, inserting w when it is new; barrier.  No floating point anywhere; nothing waits on another workgroup; rounds
 // are bounded by max_rounds, probes by the slot count.
-#include "eps_common.h"
+#include "flat_rows.h"
 
 #define PP_THREADS 256
 #define PP_WAVES (PP_THREADS / 64)
@@ -77,61 +77,6 @@ struct PpArgs {
     unsigned int *__restrict__ next;
 };
 
-__device__ __forceinline__ void pp_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A global table is written with atomics (they execute in L2) and read back by other waves of the workgroup: every access
-// goes to L2 (agent scope), never through a vector-L1 line that an earlier source left behind.
-template <bool IN_LDS, typename T>
-__device__ __forceinline__ T pp_ld(const T *p)
-{
-    if (IN_LDS) return *p;
-    return __hip_atomic_load((T *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool IN_LDS, typename T>
-__device__ __forceinline__ void pp_st(T *p, T x)
-{
-    if (IN_LDS) *p = x;
-    else __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t pp_hash(int32_t w, int lg) { return ((uint32_t)w * 2654435761u) >> (32 - lg); }
-
-// The slot of key w (inserted if new: *won), or -1 when every slot holds another key.
-__device__ __forceinline__ int pp_insert(int32_t *keys, int lg, int32_t w, bool *won)
-{
-    const uint32_t mask = (1u << lg) - 1;
-    uint32_t h = pp_hash(w, lg);
-    for (uint32_t t = 0; t <= mask; ++t) {
-        const int32_t prev = atomicCAS(&keys[h], -1, w);
-        if (prev == -1 || prev == w) {
-            *won = prev == -1;
-            return (int)h;
-        }
-        h = (h + 1) & mask;
-    }
-    *won = false;
-    return -1;
-}
-
-template <bool IN_LDS>
-__device__ __forceinline__ int pp_find(const int32_t *keys, int lg, int32_t w)
-{
-    const uint32_t mask = (1u << lg) - 1;
-    uint32_t h = pp_hash(w, lg);
-    for (uint32_t t = 0; t <= mask; ++t) {
-        const int32_t k = pp_ld<IN_LDS>(keys + h);
-        if (k == w) return (int)h;
-        if (k < 0) return -1;
-        h = (h + 1) & mask;
-    }
-    return -1;
-}
-
 // r[w] += share; a new w enters the table with its degree and joins the list.  More keys than the table takes: S.fail.
 template <bool IN_LDS>
 __device__ __forceinline__ void pp_add(const PpArgs &a, const PpTable &t, PpLds &S, int32_t w, pp_u64 share)
@@ -144,16 +89,16 @@ __device__ __forceinline__ void pp_add(const PpArgs &a, const PpTable &t, PpLds 
     //  cost every later insert a probe of all of it)
     if (__hip_atomic_load(&S.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
     bool won;
-    const int slot = pp_insert(t.key, t.lg, w, &won);
+    const int slot = tbl_insert(t.key, t.lg, w, &won);
     if (slot < 0) {
         S.fail = 1;
         return;
     }
     if (won) {
         const int64_t d = a.rowptr[w + 1] - a.rowptr[w];
-        pp_st<IN_LDS>(t.deg + slot, (uint32_t)d);
+        tbl_st<IN_LDS>(t.deg + slot, (uint32_t)d);
         const unsigned int i = atomicAdd(&S.n_list, 1u);
-        if (i < (unsigned int)t.cap) pp_st<IN_LDS>(t.list + i, (int32_t)slot);
+        if (i < (unsigned int)t.cap) tbl_st<IN_LDS>(t.list + i, (int32_t)slot);
         else S.fail = 1;
     }
     atomicAdd(t.r + slot, share);
@@ -164,9 +109,9 @@ __device__ __forceinline__ void pp_clear(const PpTable &t)
 {
     const int slots = 1 << t.lg;
     for (int i = threadIdx.x; i < slots; i += PP_THREADS) {
-        pp_st<IN_LDS>(t.key + i, (int32_t)-1);
-        pp_st<IN_LDS>(t.r + i, (pp_u64)0);
-        pp_st<IN_LDS>(t.p + i, (pp_u64)0);
+        tbl_st<IN_LDS>(t.key + i, (int32_t)-1);
+        tbl_st<IN_LDS>(t.r + i, (pp_u64)0);
+        tbl_st<IN_LDS>(t.p + i, (pp_u64)0);
     }
 }
 
@@ -186,11 +131,11 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
         S.pushes = 0;
         S.steps = 0;
         bool won;
-        const int slot = pp_insert(t.key, t.lg, s, &won);       // (an empty table: it succeeds)
-        pp_st<IN_LDS>(t.deg + slot, (uint32_t)sd);
-        pp_st<IN_LDS>(t.list + 0, (int32_t)slot);
+        const int slot = tbl_insert(t.key, t.lg, s, &won);       // (an empty table: it succeeds)
+        tbl_st<IN_LDS>(t.deg + slot, (uint32_t)sd);
+        tbl_st<IN_LDS>(t.list + 0, (int32_t)slot);
         // an isolated source keeps all of its mass: p[s] = 2^48, no rounds
-        pp_st<IN_LDS>(sd == 0 ? t.p + slot : t.r + slot, (pp_u64)PP_ONE);
+        tbl_st<IN_LDS>(sd == 0 ? t.p + slot : t.r + slot, (pp_u64)PP_ONE);
         S.n_list = 1;
     }
     int32_t n_rounds = 0, is_capped = 0;
@@ -205,9 +150,9 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
         const unsigned int n_list = S.n_list;
         // (A) the frontier, off the state at the start of the round
         for (unsigned int i = tid; i < n_list; i += PP_THREADS) {
-            const int slot = pp_ld<IN_LDS>(t.list + i);
-            const pp_u64 d = pp_ld<IN_LDS>(t.deg + slot);
-            const pp_u64 R = pp_ld<IN_LDS>(t.r + slot);
+            const int slot = tbl_ld<IN_LDS>(t.list + i);
+            const pp_u64 d = tbl_ld<IN_LDS>(t.deg + slot);
+            const pp_u64 R = tbl_ld<IN_LDS>(t.r + slot);
             // T d(u), saturated at 2^48 + 1 (r never exceeds 2^48); a node without entries has nowhere to push
             const pp_u64 bar = (d == 0 || d > a.dmax) ? PP_ONE + 1 : a.thr * d;
             if (R < bar) continue;
@@ -218,13 +163,13 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
             const pp_u64 keep = (R * a.a16) >> 16;             // R <= 2^48, a16 <= 2^15
             const pp_u64 spread = R - keep;
             const pp_u64 share = spread / d;
-            pp_st<IN_LDS>(t.p + slot, pp_ld<IN_LDS>(t.p + slot) + keep);
-            pp_st<IN_LDS>(t.r + slot, spread - share * d);
+            tbl_st<IN_LDS>(t.p + slot, tbl_ld<IN_LDS>(t.p + slot) + keep);
+            tbl_st<IN_LDS>(t.r + slot, spread - share * d);
             my_pushes += 1;
             my_steps += d;
             const unsigned int q = d > PP_BIG_ROW ? (unsigned int)t.cap - 1u - atomicAdd(&S.n_big, 1u) : atomicAdd(&S.n_small, 1u);
-            pp_st<IN_LDS>(t.qslot + q, (int32_t)slot);          // (small + big <= the list's length <= cap: the ends never meet)
-            pp_st<IN_LDS>(t.qshare + q, share);
+            tbl_st<IN_LDS>(t.qslot + q, (int32_t)slot);          // (small + big <= the list's length <= cap: the ends never meet)
+            tbl_st<IN_LDS>(t.qshare + q, share);
         }
         __syncthreads();
         const int n_small = (int)S.n_small, n_big = (int)S.n_big;
@@ -238,31 +183,23 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
         for (int c0 = wib * 64; c0 < n_small; c0 += PP_WAVES * 64) {
             const int j = c0 + lane;
             const bool act = j < n_small;
-            const int slot = act ? pp_ld<IN_LDS>(t.qslot + j) : 0;
-            const int32_t u = act ? pp_ld<IN_LDS>(t.key + slot) : 0;
+            const int slot = act ? tbl_ld<IN_LDS>(t.qslot + j) : 0;
+            const int32_t u = act ? tbl_ld<IN_LDS>(t.key + slot) : 0;
             const int64_t us = act ? a.rowptr[u] : 0;
-            const int64_t ud = act ? (int64_t)pp_ld<IN_LDS>(t.deg + slot) : 0;
-            const pp_u64 sh = act ? pp_ld<IN_LDS>(t.qshare + j) : 0;
-            int64_t inc = ud;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int64_t y = __shfl_up(inc, o);
-                if (lane >= o) inc += y;
-            }
-            const int64_t tot = __shfl(inc, 63);
-            pp_wave_sync();                    // (the previous step's lanes are done with the arrays)
-            S.excl[wib][lane] = inc - ud;
+            const int64_t ud = act ? (int64_t)tbl_ld<IN_LDS>(t.deg + slot) : 0;
+            const pp_u64 sh = act ? tbl_ld<IN_LDS>(t.qshare + j) : 0;
+            int64_t tot;
+            const int64_t uex = eps_wave_excl_scan(ud, lane, tot);
+            lds_wave_sync();                   // (the previous step's lanes are done with the arrays)
+            S.excl[wib][lane] = uex;
             S.start[wib][lane] = us;
             S.wshare[wib][lane] = sh;
-            pp_wave_sync();
+            lds_wave_sync();
             const int64_t *ex = S.excl[wib];
             for (int64_t t0 = 0; t0 < tot; t0 += 64) {
                 const int64_t e = t0 + lane;
                 if (e < tot) {
-                    int k = 0;                 // the last row of the step whose exclusive prefix is <= e (it has entries)
-#pragma unroll
-                    for (int step = 32; step > 0; step >>= 1)
-                        if (ex[k + step] <= e) k += step;
+                    const int k = flat_owner(ex, e);           // e's row (it has entries)
                     pp_add<IN_LDS>(a, t, S, a.col[S.start[wib][k] + (e - ex[k])], S.wshare[wib][k]);
                 }
             }
@@ -270,11 +207,11 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
         // ... long rows: one after the other, by the whole workgroup
         for (int b = 0; b < n_big; ++b) {
             const int q = t.cap - 1 - b;
-            const int slot = pp_ld<IN_LDS>(t.qslot + q);
-            const int32_t u = pp_ld<IN_LDS>(t.key + slot);
+            const int slot = tbl_ld<IN_LDS>(t.qslot + q);
+            const int32_t u = tbl_ld<IN_LDS>(t.key + slot);
             const int64_t us = a.rowptr[u];
-            const int64_t ud = (int64_t)pp_ld<IN_LDS>(t.deg + slot);
-            const pp_u64 sh = pp_ld<IN_LDS>(t.qshare + q);
+            const int64_t ud = (int64_t)tbl_ld<IN_LDS>(t.deg + slot);
+            const pp_u64 sh = tbl_ld<IN_LDS>(t.qshare + q);
             for (int64_t j = tid; j < ud; j += PP_THREADS) pp_add<IN_LDS>(a, t, S, a.col[us + j], sh);
         }
         __syncthreads();
@@ -291,16 +228,16 @@ __device__ bool pp_source(const PpArgs &a, const PpTable &t, PpLds &S, int64_t s
     const int64_t q0 = a.qptr[si], q1 = a.qptr[si + 1];
     for (int64_t q = q0 + tid; q < q1; q += PP_THREADS) {
         const int32_t x = a.qnode[q];
-        const int slot = (uint32_t)x < (uint64_t)a.n ? pp_find<IN_LDS>(t.key, t.lg, x) : -1;
-        a.mass[q] = slot < 0 ? 0 : (int64_t)pp_ld<IN_LDS>(t.p + slot);
+        const int slot = (uint32_t)x < (uint64_t)a.n ? tbl_find_slot<IN_LDS>(t.key, t.lg, x) : -1;
+        a.mass[q] = slot < 0 ? 0 : (int64_t)tbl_ld<IN_LDS>(t.p + slot);
     }
     __syncthreads();
     const unsigned int n_list = S.n_list;
     for (unsigned int i = tid; i < n_list; i += PP_THREADS) {
-        const int slot = pp_ld<IN_LDS>(t.list + i);
-        pp_st<IN_LDS>(t.key + slot, (int32_t)-1);
-        pp_st<IN_LDS>(t.r + slot, (pp_u64)0);
-        pp_st<IN_LDS>(t.p + slot, (pp_u64)0);
+        const int slot = tbl_ld<IN_LDS>(t.list + i);
+        tbl_st<IN_LDS>(t.key + slot, (int32_t)-1);
+        tbl_st<IN_LDS>(t.r + slot, (pp_u64)0);
+        tbl_st<IN_LDS>(t.p + slot, (pp_u64)0);
     }
     if (tid == 0) {
         a.rounds[si] = n_rounds;

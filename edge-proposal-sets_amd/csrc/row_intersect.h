@@ -18,14 +18,6 @@
 #define ROW_CAP 1024          // long-row entries staged per wave and pass (4 KiB of LDS per wave): lb_pow2's largest table (lg = 10)
 #define ROW_INPLACE_RATIO 32  // long row searched in place when long > ROW_CAP && long >= ratio * short
 
-// LDS written by some lanes of the wave is read by others after this.
-__device__ __forceinline__ void lds_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The wave's next ticket off one device word (lane 0 draws, every lane gets it).
 __device__ __forceinline__ int64_t take_chunk(unsigned int *next_chunk, int lane)
 {

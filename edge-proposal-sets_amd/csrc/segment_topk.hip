@@ -227,12 +227,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_group_kernel(const int64_t *_
 #pragma unroll
                     for (int j = 0; j < 4; ++j) c[j] = s_hist[255 - 4 * lane - j];
                     const uint32_t own = c[0] + c[1] + c[2] + c[3];
-                    uint32_t incl = own;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const uint32_t up = __shfl_up(incl, d);
-                        if (lane >= d) incl += up;
-                    }
+                    const uint32_t incl = eps_wave_incl_scan(own, lane);
                     const unsigned long long reach = __ballot(incl >= t);
                     const int owner = reach ? __builtin_ctzll(reach) : 63;
                     if (lane == owner) {
@@ -277,12 +272,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_group_kernel(const int64_t *_
                     const bool in = base + 4 * tid + j < len;
                     own += (in && cur[j] > prefix ? 1u : 0u) + (in && cur[j] == prefix ? 1u << 16 : 0u);
                 }
-                uint32_t incl = own;                               // (a chunk holds 1024 entries: both halves stay below 2^16)
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d);
-                    if (lane >= d) incl += up;
-                }
+                const uint32_t incl = eps_wave_incl_scan(own, lane);   // (a chunk holds 1024 entries: both halves stay below 2^16)
                 if (lane == 63) s_wcnt[buf][wv] = incl;
                 __syncthreads();
                 uint32_t front = 0u, whole = 0u;

@@ -94,8 +94,37 @@ def test_kernel_on_hubs_beyond_the_lds_map(eps, dev, weighted):
     assert_within_one_ulp(kernel_scores(eps, A, pairs), truncated_truth(A, pairs, COEFFS), "hubs")
 
 
+def flat_walk_graph():
+    """Directed, weighted, 98 nodes: nodes 0 and 1 point at the first 64 and at all 65 of the middle nodes 2 .. 66, middle node
+    2 + i has (i + 1) % 4 entries among eight collectors 70 .. 77, every collector points at node 80, and eight feeders 90 .. 97
+    point at every collector.  The walk of pair (0, 80) or (1, 80) is cheaper from the left end (the feeders make node 80's side
+    dear) and short enough for one wave: one wave step of exactly 64 rows -- empty rows between rows of 1, 2 and 3 entries,
+    96 entries in all -- and for node 1 a second step of one row."""
+    rng = np.random.default_rng(64)
+    mids, coll = np.arange(2, 67), np.arange(70, 78)
+    e = [(0, m) for m in mids[:64]] + [(1, m) for m in mids]
+    e += [(m, coll[(i + j) % 8]) for i, m in enumerate(mids) for j in range((i + 1) % 4)]
+    e += [(c, 80) for c in coll] + [(f, c) for f in range(90, 98) for c in coll]
+    r, c = zip(*e)
+    return ssp.coo_matrix((rng.integers(1, 7, len(e)).astype(np.float64), (r, c)), shape=(98, 98)).tocsr()
+
+
 def test_kernel_edge_cases(eps, dev):
-    """Isolated nodes, u == v, pairs with no path of length <= 3 (exactly 0.0), and an empty list."""
+    """Isolated nodes, u == v, pairs with no path of length <= 3 (exactly 0.0), and an empty list; then one wave step of exactly
+    64 rows of the flattened walk, and 65 rows, with empty rows inside the step -- from either end of the pair."""
+    F = flat_walk_graph()
+    out_deg, in_deg = np.diff(F.indptr), np.diff(F.tocsc().indptr)
+    p_out, p_in = (F != 0) @ out_deg, (F != 0).T @ in_deg               # the two-path counts the kernel plans with
+    assert out_deg[0] == 64 and out_deg[1] == 65 and p_out[0] == 96 and p_out[1] == 97
+    rows = out_deg[F[0].indices]
+    assert rows[0] > 0 and rows[-2] > 0 and (rows == 0).sum() == 16
+    for a in (0, 1):                                                    # walked from a (the cheaper end), by one wave
+        assert p_out[a] + in_deg[80] <= p_in[80] + out_deg[a] and p_out[a] <= 2048
+    fp = np.array([[0, 80], [1, 80], [0, 70], [1, 77], [0, 2], [1, 66], [90, 80], [0, 1], [80, 0]])
+    ft = truncated_truth(F, fp, COEFFS)
+    assert np.all(ft[:7] > 0) and np.all(ft[7:] == 0)
+    assert_within_one_ulp(kernel_scores(eps, F, fp), ft, "flat walk, forward")
+    assert_within_one_ulp(kernel_scores(eps, F.T.tocsr(), fp[:, ::-1]), ft, "flat walk, backward")
     # a path 0-1-2-3-4-5-6, a triangle 7-8-9, isolated 10, 11
     e = [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (5, 6), (7, 8), (8, 9), (7, 9)]
     r, c = zip(*e)
