@@ -169,6 +169,10 @@ SIGNATURES = {
     "eps_ppr_push_limits": (_int, [_i64, _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64)]),
     "eps_ppr_push": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp]),
+    "eps_gat_aggregate": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _c.c_float, _vp, _int, _vp, _i64, _vp,
+                                 _vp]),
+    "eps_gat_aggregate_backward": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _c.c_float, _vp, _vp, _i64, _vp, _i64,
+                                          _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 7        # include/eps_abi.h EPS_ABI_VERSION

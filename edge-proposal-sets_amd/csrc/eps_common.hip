@@ -104,7 +104,7 @@ int eps_take_counters8(unsigned int **counters, hipStream_t stream, const char *
     X(pair_intersect) X(pair_grouped) X(expand_score) X(filter_scan) X(spmm_csr) \
     X(gemm_f32) X(dense_cn) X(mlp_decode) X(mlp_decode_bf16) X(mlp_decode_train) X(topk_keys) X(topk_select) X(segment_topk) \
     X(tail_sort) X(rows_by_score) X(katz_pairs) X(katz_columns) X(local_index) X(cosine_cn) X(cosine_cn_bwd) X(pair_cn_list) X(local_community) X(sketch) \
-    X(ppr_push)
+    X(ppr_push) X(gat_attend)
 
 #define EPS_DECLARE_WARM(unit) extern "C" void eps_warm_##unit(void *stream);
 EPS_UNITS(EPS_DECLARE_WARM)

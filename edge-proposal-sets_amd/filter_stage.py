@@ -64,6 +64,9 @@ def make_parser():
                              'command is unchanged')
     parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2],
                         help='--model buddy: hops of the subgraph sketches and of the node-feature propagation (default 2)')
+    parser.add_argument('--gat_heads', type=int, default=None,
+                        help='--model gat: attention heads per layer, 1 to 8; --hidden_channels must be a multiple of 4 * heads '
+                             '(default 4)')
     parser.add_argument('--ppr_alpha', type=float, default=PPR_ALPHA,
                         help=f'--model ppr: the teleport probability, rounded to a 16-bit fraction in (0, 1/2] (default {PPR_ALPHA})')
     parser.add_argument('--ppr_eps', type=float, default=PPR_EPS,
@@ -75,7 +78,7 @@ def make_parser():
 
 
 DECODE_GUARD_DEFAULT = 4.0     # the rule: twice the smallest measured guard with recall 1.0 on both stand-ins; DESIGN 4.5d says what is measured
-BF16_FILTER_MODELS = ('gcn', 'sage', 'dea', 'dea_512')
+BF16_FILTER_MODELS = ('gcn', 'sage', 'dea', 'dea_512', 'gat')
 
 
 def screen_size(keep: int, guard: float) -> int:
@@ -108,7 +111,7 @@ def check_decode_args(args) -> None:
     if hc is None or hc % 16 != 0 or hc > ops.BF16_MAX_HIDDEN:
         raise ValueError(f"--decode_precision bf16: --model {args.model} with --hidden_channels {hc}: the bf16 decode kernel takes "
                          f"a multiple of 16 up to {ops.BF16_MAX_HIDDEN} (wider or odd widths decode in fp32)")
-    if args.model in ('gcn', 'sage') and (args.num_layers is None or args.num_layers < 2):
+    if args.model in ('gcn', 'sage', 'gat') and (args.num_layers is None or args.num_layers < 2):
         raise ValueError(f"--decode_precision bf16: --num_layers {args.num_layers}: a one-layer decoder has no matrix work")
     import os
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -16,7 +16,8 @@ GNN for each batch (models.py:505 called from filter.py:118).  Results are ident
 
 Beyond the reference: ``NCNPredictor`` / ``NCNLinkGNN`` (``--model ncn | ncn_sage``), Neural Common Neighbor on the
 common-neighbour lists of csrc/pair_cn_list.hip (``cn_embed_sum``); ``BuddyPredictor`` / ``BuddyLinkModel`` (``--model buddy``),
-BUDDY on the subgraph sketches of csrc/sketch.hip (``heuristics.sketch_features``).
+BUDDY on the subgraph sketches of csrc/sketch.hip (``heuristics.sketch_features``); ``GATConv`` / ``GAT`` (``--model gat``), a
+graph-attention encoder on the fused softmax-and-gather kernels of csrc/gat_attend.hip.
 """
 from __future__ import annotations
 
@@ -200,6 +201,119 @@ class SAGEConv(torch.nn.Module):
         return f"SAGEConv({self.in_channels}, {self.out_channels})"
 
 
+class _GATAggregate(torch.autograd.Function):
+    """Differentiable attention aggregate for TRAINING: ``apply(z, s_src, s_dst, graph, heads)`` -> the aggregate without bias
+    and ReLU, on eps_gat_aggregate; the backward is eps_gat_aggregate_backward and returns the gradients of ``z`` (the gathered
+    features), ``s_src`` and ``s_dst``.  The two score tables are functions of ``z`` on torch, so autograd carries their
+    gradients on to ``att_*`` and ``lin.weight``.  The backward sums over the rows that attend to a node along that node's own
+    row: the pattern must be symmetric, which GATConv checks (``_check_trainable``) BEFORE it gets here."""
+
+    @staticmethod
+    def forward(ctx, z, s_src, s_dst, graph, heads):
+        z, s_src, s_dst = z.contiguous(), s_src.contiguous(), s_dst.contiguous()
+        out, lse = ops.gat_aggregate(graph.rowptr, graph.col, z, s_src, s_dst, heads, want_lse=True)
+        ctx.save_for_backward(z, s_src, s_dst, lse, out)
+        ctx.graph, ctx.heads = graph, heads
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        z, s_src, s_dst, lse, out = ctx.saved_tensors
+        g = ctx.graph
+        gz, gs, gd = ops.gat_aggregate_backward(g.rowptr, g.col, z, s_src, s_dst, ctx.heads, lse, out, grad_out.contiguous())
+        return gz, gs, gd, None, None
+
+
+class GATConv(torch.nn.Module):
+    """The graph attention layer of Velickovic et al. (ICLR 2018) as torch_geometric publishes it [third-party, restated]:
+    ``GATConv(in_channels, out_channels, heads)`` with C = out_channels / heads; the heads are concatenated, so the output
+    is ``out_channels`` wide.
+
+    Parameters (the state-dict keys of the published layer): ``lin.weight`` [heads * C, in] (no bias in ``lin``), ``att_src``
+    [1, heads, C], ``att_dst`` [1, heads, C], ``bias`` [heads * C]; glorot for ``lin.weight`` and the two ``att_*``, zeros for
+    ``bias``.
+    Features and scores: z = x W^T viewed as [N, heads, C]; s_src[j,h] = <z[j,h,:], att_src[h,:]>, s_dst[i,h] = <z[i,h,:],
+    att_dst[h,:]>.
+    Neighbourhood of row i: the stored entries of row i with col != i, plus i itself exactly once -- a stored self loop is not
+    counted twice; stored values are ignored; an empty row attends to itself alone, so its output is z[i] + bias.  The
+    adjacency must be square.
+    Attention: e_ij = LeakyReLU_0.2(s_src[j,h] + s_dst[i,h]), alpha_i.h = softmax_j e_ij.
+    Output: out[i,h,:] = sum_j alpha_ijh z[j,h,:] + bias, optionally followed by ReLU.
+    Not built: attention dropout, edge features, ``concat=False``, GATv2.
+
+    Eval runs on the HIP kernels: the transform is ``ops.gemm``, the two score tables are a second small product of z with the
+    block-diagonal [2 heads, heads * C] matrix of ``att_src`` / ``att_dst`` (the same sums, over the same z, as training
+    forms), the aggregate is eps_gat_aggregate with the bias and the ReLU in its epilogue.  Training runs the aggregate and its
+    backward on the HIP kernels inside autograd (``_GATAggregate``) and the dense part on torch."""
+
+    SLOPE = ops.GAT_SLOPE
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1):
+        super().__init__()
+        if heads < 1 or out_channels % heads:
+            raise ValueError(f"GATConv: out_channels {out_channels} is not a multiple of heads {heads}")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.att_src = torch.nn.Parameter(torch.empty(1, heads, out_channels // heads))
+        self.att_dst = torch.nn.Parameter(torch.empty(1, heads, out_channels // heads))
+        self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            torch.nn.init.xavier_uniform_(self.lin.weight)       # glorot
+            torch.nn.init.xavier_uniform_(self.att_src)
+            torch.nn.init.xavier_uniform_(self.att_dst)
+            self.bias.zero_()
+
+    def _att_matrix(self, pad: bool) -> torch.Tensor:
+        """[2 heads (rounded up to 4 rows with ``pad``), heads * C]: row h holds att_src[h, :] in head h's columns, row heads + h
+        att_dst[h, :], zeros elsewhere -- z times its transpose is [s_src || s_dst].  Differentiable in ``att_*``."""
+        h, c = self.heads, self.out_channels // self.heads
+        eye = torch.eye(h, dtype=self.att_src.dtype, device=self.att_src.device)[:, :, None]
+        rows = [(eye * a.view(1, h, c)).reshape(h, h * c) for a in (self.att_src, self.att_dst)]
+        if pad and (2 * h) % 4:
+            rows.append(rows[0].new_zeros((4 - (2 * h) % 4, h * c)))
+        return torch.cat(rows, 0)
+
+    @staticmethod
+    def _check_square(adj_t: CSRGraph) -> None:
+        if adj_t.n_rows != adj_t.n_cols:
+            raise ValueError(f"GATConv: the self loop needs a square adjacency, got {adj_t.n_rows} x {adj_t.n_cols}")
+
+    def forward(self, x: torch.Tensor, adj_t: CSRGraph, relu: bool = False) -> torch.Tensor:
+        _check_rows(x, adj_t, "GATConv")
+        self._check_square(adj_t)
+        if torch.is_grad_enabled() and self.training:
+            _check_trainable(adj_t, "GATConv", values=False)      # the attention reads the pattern only
+            h = self.heads
+            z = self.lin(x)
+            s = z @ self._att_matrix(False).t()
+            out = _GATAggregate.apply(z, s[:, :h], s[:, h:2 * h], adj_t, h) + self.bias
+            return F.relu(out) if relu else out
+        with torch.no_grad():
+            return self._forward_hip(x, adj_t, relu)
+
+    def _forward_hip(self, x, adj_t, relu, rows=None):
+        h = self.heads
+        z = ops.gemm(_pad4(x), self.lin.weight.detach())         # transform ...
+        s = ops.gemm(z, self._att_matrix(True).detach().contiguous())         # ... the two score tables, [N, 2 heads (+ pad)] ...
+        lo, hi = (0, adj_t.n_rows) if rows is None else rows
+        rowptr = adj_t.rowptr if rows is None else adj_t.rowptr[lo:hi + 1]     # row block: absolute offsets into col
+        return ops.gat_aggregate(rowptr, adj_t.col, z, s[:, :h], s[:, h:2 * h], h, row0=lo, slope=self.SLOPE,
+                                 bias=self.bias.detach(), relu=relu)           # ... then attend
+
+    @torch.no_grad()
+    def forward_rows(self, x: torch.Tensor, adj_t: CSRGraph, lo: int, hi: int, relu: bool = False) -> torch.Tensor:
+        """Rows [lo, hi) of the layer output from the FULL input (multi-GPU row sharding, dist.py)."""
+        _check_rows(x, adj_t, "GATConv")
+        self._check_square(adj_t)
+        return self._forward_hip(x, adj_t, relu, rows=(lo, hi))
+
+    def __repr__(self):
+        return f"GATConv({self.in_channels}, {self.out_channels}, heads={self.heads})"
+
+
 class _ConvStack(torch.nn.Module):
     conv_cls = None
 
@@ -247,6 +361,20 @@ class GCN(_ConvStack):
 class SAGE(_ConvStack):
     """models.py:417-440."""
     conv_cls = SAGEConv
+
+
+GAT_HEADS = 4                    # --gat_heads default
+
+
+class GAT(_ConvStack):
+    """A stack of GATConv layers in the mould of GCN / SAGE (beyond the reference): every layer concatenates its ``heads`` heads,
+    so the stack keeps the width ``hidden_channels`` throughout; ReLU (+ dropout) after every layer but the last."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, dropout, heads=GAT_HEADS):
+        import functools
+        object.__setattr__(self, "conv_cls", functools.partial(GATConv, heads=int(heads)))   # (bound before the stack is built)
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, dropout)
+        self.heads = int(heads)
 
 
 REORDER_MIN_NODES = 100_000      # graphs from this size on run their GNN layers on the hubs-first relabelling
@@ -1074,9 +1202,9 @@ class CommonNeighborsPredictor(torch.nn.Module):
 DECODE_MAX_HIDDEN = 256          # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 256
 _MODELS = ['sage', 'sage2', 'gcn', 'dea', 'dea_512', 'mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb',
            "resource_allocation", 'katz', 'ensemble_gcn_sage', *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES, 'ncn', 'ncn_sage', 'buddy',
-           'ppr']
+           'ppr', 'gat']
 _NCN = {'ncn': 'gcn', 'ncn_sage': 'sage'}       # Neural Common Neighbor: name -> the encoder whose arguments and defaults it takes
-_ENCODER_ROW = {**_NCN, 'buddy': 'gcn'}         # models beyond the reference: name -> the row of the defaults table they take
+_ENCODER_ROW = {**_NCN, 'buddy': 'gcn', 'gat': 'gcn'}         # models beyond the reference: name -> the row of the defaults table they take
 _HEURISTICS = ['mlpcos', 'simplecos', 'adamic', 'simple', 'adamic_ogb', 'katz', "resource_allocation", *heuristics.LOCAL_INDICES, *heuristics.LOCAL_COMMUNITY_INDICES,
                'ppr']
 
@@ -1100,6 +1228,8 @@ def build_model(args, data, device):
                              "them) or --use_learnable_embedding True")
     if args.model in ('dea', 'dea_512'):
         return _build_dea(args, data, device)
+    if args.model == 'gat':
+        _check_gat_args(args)
     if args.model in _ENCODER_ROW:
         # (before anything is allocated: ppa has no defaults, and the decoder's two first layers and its output layer make 2)
         if args.hidden_channels is None:
@@ -1126,6 +1256,11 @@ def build_model(args, data, device):
         linkpred = LinkPredictor(args.hidden_channels, args.hidden_channels, 1, args.num_layers,
                                  args.dropout).to(device)
         return LinkGNN(emb, gnn, linkpred)
+    if args.model == 'gat':
+        gnn = GAT(input_dim, args.hidden_channels, args.hidden_channels, args.num_layers, args.dropout,
+                  heads=int(_flag(args, "gat_heads", GAT_HEADS))).to(device)
+        linkpred = LinkPredictor(args.hidden_channels, args.hidden_channels, 1, args.num_layers, args.dropout).to(device)
+        return LinkGNN(emb, gnn, linkpred)
     if args.model in _NCN:
         gnn_cls = SAGE if args.model == 'ncn_sage' else GCN
         gnn = gnn_cls(input_dim, args.hidden_channels, args.hidden_channels, args.num_layers, args.dropout).to(device)
@@ -1145,6 +1280,24 @@ def build_model(args, data, device):
                                         args.dropout, model_type=args.model, **ppr_kw).to(device)
     raise NotImplementedError(f"model '{args.model}' (sage2 / ensemble_gcn_sage) is outside the accelerated path "
                               "(SURVEY 2.1: alternative / experimental models, not in the north star)")
+
+
+def _check_gat_args(args) -> None:
+    """The rules of --model gat, each refused by name before anything is allocated."""
+    heads = int(_flag(args, "gat_heads", GAT_HEADS))
+    hc, nl = args.hidden_channels, args.num_layers
+    if not 1 <= heads <= ops.GAT_MAX_HEADS:
+        raise UnsupportedModelConfig(f"--model gat: --gat_heads {heads}: the attention kernel takes 1 to {ops.GAT_MAX_HEADS} heads")
+    if hc is None:
+        raise UnsupportedModelConfig(f"--model gat needs --hidden_channels (there is no {getattr(args, 'dataset', '')} default for it)")
+    if hc % (4 * heads) != 0:
+        fit = [h for h in range(1, ops.GAT_MAX_HEADS + 1) if hc % (4 * h) == 0]
+        raise UnsupportedModelConfig(f"--model gat: --hidden_channels {hc} is not a multiple of 4 * heads = {4 * heads} (every head is a "
+                                     f"whole number of float4 columns); with this width pass --gat_heads {' or '.join(map(str, fit)) or '(none fits)'}")
+    if hc > DECODE_MAX_HIDDEN:
+        raise UnsupportedModelConfig(f"--model gat: --hidden_channels {hc}: the fused decode kernel takes a width up to {DECODE_MAX_HIDDEN}")
+    if nl is None or nl < 2:
+        raise UnsupportedModelConfig(f"--model gat: --num_layers {nl}: the encoder stack and the decoder have at least 2 layers")
 
 
 DEA_MAX_HIDDEN = 512             # csrc/mlp_decode.hip: hdim % 4 == 0 && hdim <= 512
@@ -1174,7 +1327,7 @@ def _build_dea(args, data, device):
 
 
 # per-dataset defaults, one row per (dataset group, model group): restates the table of models.py:673-790
-_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage', 'ncn', 'ncn_sage', 'buddy')
+_GNNS = ('sage', 'sage2', 'gcn', 'dea', 'dea_512', 'ensemble_gcn_sage', 'ncn', 'ncn_sage', 'buddy', 'gat')
 _KEYS = ["num_layers", "hidden_channels", "dropout", "batch_size", "lr", "epochs", "use_feature",
          "use_learnable_embedding"]
 

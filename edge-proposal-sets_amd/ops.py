@@ -1024,6 +1024,86 @@ def spmm_csr(rowptr, col, val, x: torch.Tensor, bias=None, relu=False, mean=Fals
     return out
 
 
+GAT_MAX_HEADS = 8        # csrc/gat_attend.hip: GA_MAX_HEADS
+GAT_SLOPE = 0.2          # the LeakyReLU slope of the published layer
+
+
+def _gat_tables(who: str, n: int, heads: int, z, s_src, s_dst) -> int:
+    """The shared operand checks of the two attention calls -> the row stride of the score tables."""
+    f = int(z.shape[1])
+    if not 1 <= heads <= GAT_MAX_HEADS or f < 4 or f % (4 * heads):
+        raise _lib.EpsError(f"{who}: width {f} with {heads} heads is outside the kernel's domain (1 <= heads <= {GAT_MAX_HEADS}, "
+                            f"width a multiple of 4 * heads)")
+    if z.shape[0] != n:
+        raise _lib.EpsError(f"{who}: z must have one row per node ({n}), got {tuple(z.shape)}")
+    for name, s in (("s_src", s_src), ("s_dst", s_dst)):
+        if tuple(s.shape) != (n, heads):
+            raise _lib.EpsError(f"{who}: {name} must be [{n}, {heads}], got {tuple(s.shape)}")
+    lds = s_src.stride(0) if n > 1 else max(heads, s_src.stride(0))
+    if n > 1 and s_dst.stride(0) != lds:
+        raise _lib.EpsError(f"{who}: s_src and s_dst must share one row stride ({s_src.stride(0)} vs {s_dst.stride(0)})")
+    return lds
+
+
+def _ld16(who: str, name: str, t: torch.Tensor) -> int:
+    """The row stride of a float4-read operand: 16-byte aligned rows."""
+    ld = t.stride(0) if t.shape[0] > 1 else max(int(t.shape[1]), t.stride(0))
+    if ld % 4 or t.data_ptr() % 16:
+        raise _lib.EpsError(f"{who}: {name} needs 16-byte aligned rows (row stride {ld} floats, address % 16 = {t.data_ptr() % 16})")
+    return ld
+
+
+def gat_aggregate(rowptr, col, z: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor, heads: int, row0: int = 0,
+                  slope: float = GAT_SLOPE, bias=None, relu=False, out=None, want_lse=False):
+    """The attention aggregate of GATConv (eps_gat_aggregate): rows [row0, row0 + len(rowptr) - 1) of
+    out[i,h,:] = sum_{j in N(i) + {i}} softmax_j(LeakyReLU(s_src[j,h] + s_dst[i,h])) z[j,h,:] (+ bias, ReLU).  ``rowptr``: the row
+    block's slice of the graph's (absolute offsets into ``col``); ``z`` float32 [N, heads * C] (a row stride of its own is fine);
+    ``s_src`` / ``s_dst`` float32 [N, heads] (two column blocks of one table are fine).  The column ids are the caller's to check
+    (< N): the kernel gathers unchecked.  -> out [rows, heads * C], or (out, lse [rows, heads]) with ``want_lse``."""
+    _chk_2d("gat_aggregate", z=z, s_src=s_src, s_dst=s_dst, out=out)
+    dev = _need_gpu(rowptr, col, z, s_src, s_dst, bias, out, row_strided=(z, s_src, s_dst, out))
+    _csr(rowptr, col); _chk(_F32, z=z, s_src=s_src, s_dst=s_dst, bias=bias, out=out)
+    n, f, heads, row0 = int(z.shape[0]), int(z.shape[1]), int(heads), int(row0)
+    n_rows = rowptr.numel() - 1
+    lds = _gat_tables("gat_aggregate", n, heads, z, s_src, s_dst)
+    if n_rows < 0 or row0 < 0 or row0 + n_rows > n:
+        raise _lib.EpsError(f"gat_aggregate: rows [{row0}, {row0 + n_rows}) are outside the {n} nodes of z")
+    _chk_len("gat_aggregate", "bias", bias, f, "one per column of z")
+    _chk_out("gat_aggregate", out, n_rows, f)
+    if out is None:
+        out = torch.empty((n_rows, f), dtype=_F32, device=dev)
+    lse = torch.empty((n_rows, heads), dtype=_F32, device=dev) if want_lse else None
+    _call("eps_gat_aggregate", dev, rowptr, col, row0, n_rows, n, z, _ld16("gat_aggregate", "z", z), heads, f, s_src, s_dst, lds,
+          ctypes.c_float(slope), bias, int(relu), out, _ld16("gat_aggregate", "out", out), lse)
+    return (out, lse) if want_lse else out
+
+
+def gat_aggregate_backward(rowptr, col, z: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor, heads: int, lse: torch.Tensor,
+                           out_nobias: torch.Tensor, gout: torch.Tensor, slope: float = GAT_SLOPE):
+    """The backward of ``gat_aggregate`` over the whole graph (eps_gat_aggregate_backward), whose pattern must be symmetric (the
+    caller's to check: the sums over the rows that attend to j are taken over row j).  ``lse`` and ``out_nobias``: what the
+    forward returned without bias and ReLU; ``gout``: the gradient of that output.  -> (gz [N, heads * C], g_s_src [N, heads],
+    g_s_dst [N, heads]); the same bits on every call."""
+    _chk_2d("gat_aggregate_backward", z=z, s_src=s_src, s_dst=s_dst, lse=lse, out_nobias=out_nobias, gout=gout)
+    dev = _need_gpu(rowptr, col, z, s_src, s_dst, lse, out_nobias, gout, row_strided=(z, s_src, s_dst, out_nobias, gout))
+    _csr(rowptr, col); _chk(_F32, z=z, s_src=s_src, s_dst=s_dst, lse=lse, out_nobias=out_nobias, gout=gout)
+    n, f, heads = int(z.shape[0]), int(z.shape[1]), int(heads)
+    who = "gat_aggregate_backward"
+    lds = _gat_tables(who, n, heads, z, s_src, s_dst)
+    if rowptr.numel() != n + 1:
+        raise _lib.EpsError(f"{who}: rowptr holds {rowptr.numel()} offsets, not {n + 1} (the whole graph, one row per row of z)")
+    if tuple(lse.shape) != (n, heads):
+        raise _lib.EpsError(f"{who}: lse must be [{n}, {heads}], got {tuple(lse.shape)}")
+    for name, t in (("out_nobias", out_nobias), ("gout", gout)):
+        if tuple(t.shape) != (n, f):
+            raise _lib.EpsError(f"{who}: {name} must be [{n}, {f}], got {tuple(t.shape)}")
+    gz = torch.empty((n, f), dtype=_F32, device=dev)
+    gs, gd, dwork = (torch.empty((n, heads), dtype=_F32, device=dev) for _ in range(3))
+    _call("eps_gat_aggregate_backward", dev, rowptr, col, n, z, _ld16(who, "z", z), heads, f, s_src, s_dst, lds, ctypes.c_float(slope),
+          lse, out_nobias, _ld16(who, "out_nobias", out_nobias), gout, _ld16(who, "gout", gout), gz, f, gs, gd, dwork)
+    return gz, gs, gd
+
+
 COS_ROW_FLOATS = 32      # xhat rows padded to a multiple of 128 bytes (whole cache lines per gathered row)
 
 

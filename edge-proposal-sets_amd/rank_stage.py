@@ -59,6 +59,7 @@ def make_parser():
     parser.add_argument('--fused_decode', action="store_true", default=False)   # gcn / sage: train through the fused HIP decode
     parser.add_argument('--fused_decode_bn', action="store_true", default=False)   # dea: the same, BatchNorm on batch statistics included
     parser.add_argument('--sketch_hops', type=int, default=2, choices=[1, 2])   # buddy: hops of the sketches and of the feature propagation
+    parser.add_argument('--gat_heads', type=int, default=None)          # gat: attention heads per layer (1 to 8, default 4)
     parser.add_argument('--ppr_alpha', type=float, default=PPR_ALPHA)   # ppr: teleport probability (rounded to a 16-bit fraction)
     parser.add_argument('--ppr_eps', type=float, default=PPR_EPS)       # ppr: the push threshold per unit of degree
     parser.add_argument('--no_incremental_graph', action="store_true", default=False)   # rebuild the graph from the edge list at every point
@@ -203,7 +204,7 @@ def _print_epoch(results, run_i: int, epoch: int, loss: float) -> None:
 def run(args):
     args = default_model_configs(args)
     print(args)
-    if getattr(args, 'fused_decode', False) and args.model not in ('gcn', 'sage'):
+    if getattr(args, 'fused_decode', False) and args.model not in ('gcn', 'sage', 'gat'):
         # (before any data is read)
         raise ValueError(f"--fused_decode trains the LinkPredictor decoder of --model gcn / sage through the fused HIP kernels; "
                          f"--model {args.model} has no such decoder (dea's decoder applies BatchNorm on batch statistics, which "

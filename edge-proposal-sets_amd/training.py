@@ -7,7 +7,8 @@ Function in models.py), dense layers and the pairwise decode run on torch in tra
 csrc/mlp_decode_train.hip instead when LinkGNN.fused_decode is set: rank.py --fused_decode; DEA_GNN_JK.fused_decode:
 rank.py --fused_decode_bn).  ncn / ncn_sage train like gcn / sage; their common-neighbour sums run on the HIP list kernel and the
 SpMM in both directions (models.cn_embed_sum).  buddy trains like gcn too; its structural features come from the graph's sketches
-(csrc/sketch.hip) and carry no gradient.
+(csrc/sketch.hip) and carry no gradient.  gat trains like gcn; its aggregate and that aggregate's backward run on csrc/gat_attend.hip
+(models._GATAggregate).
 """
 from __future__ import annotations
 
@@ -49,7 +50,7 @@ def train(model, data, dataset_name, split_edge, optimizer, batch_size, use_para
         if use_params:
             optimizer.zero_grad()
         pos_edge = to_undirected(pos_train_edge[perm].t())
-        if model_str in ['gcn', 'sage', 'dea', 'dea_512', 'ncn', 'ncn_sage', 'buddy']:
+        if model_str in ['gcn', 'sage', 'dea', 'dea_512', 'ncn', 'ncn_sage', 'buddy', 'gat']:
             if dataset_name in ["collab"]:
                 neg_edge = torch.randint(0, data.num_nodes, pos_edge.size(), dtype=torch.long, device=pos_edge.device)
             else:

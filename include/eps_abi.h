@@ -1082,6 +1082,35 @@ int eps_ppr_push(const int64_t *rowptr, const int32_t *col, int64_t n_nodes, con
                  int64_t table_nodes, void *workspace, int64_t workspace_bytes, int64_t *mass, int32_t *rounds, int64_t *pushes,
                  int64_t *steps, int32_t *capped, int32_t *table_used, int32_t *status, void *stream);
 
+/* ---- graph attention aggregate (GATConv; csrc/gat_attend.hip) ---------------------------------------------------------------
+ * eps_gat_aggregate: rows [row0, row0 + n_rows) of
+ *     out[i,h,:] = sum_{j in N(i) + {i}} alpha_ijh z[j,h,:]  (+ bias, then ReLU),
+ *     alpha_i.h = softmax_j e_ijh,   e_ijh = LeakyReLU_slope(s_src[j,h] + s_dst[i,h]),
+ *   N(i) = the stored entries of row i with col != i, plus i itself exactly once (stored values are not read; an empty row gives
+ *   z[i] + bias exactly).  rowptr int64[n_rows + 1]: the row block's ABSOLUTE offsets into col (the slice rowptr[row0 .. row0 +
+ *   n_rows] of the graph's); col int32, every id < n_nodes; z float32 [n_nodes, ldz], its first f columns read as [heads, C],
+ *   C = f / heads; s_src / s_dst float32 [n_nodes, lds], their first `heads` columns read (two column blocks of one table are
+ *   fine); bias float32[f] or NULL; out float32 [n_rows, ldo]; lse float32 [n_rows, heads] or NULL: m + log(sum_j exp(e - m)), the
+ *   row's log-sum-exp per head, what the backward needs.  The maximum is subtracted before exp: scores of any magnitude give
+ *   finite output.  Summation order: the self loop first, then the stored entries in stored order, sequentially -- the same bits
+ *   on every call and from every row block.
+ * eps_gat_aggregate_backward: the whole (square, SYMMETRIC-pattern) graph.  With alpha_ij = exp(e_ij - lse_i), D_ih =
+ *   <gout[i,h,:], out_nobias[i,h,:]> and ds_ij = alpha_ij (<gout[i,h,:], z[j,h,:]> - D_ih) (raw_ij > 0 ? 1 : slope):
+ *     gz[j] = sum_i alpha_ij gout[i],   g_s_src[j,h] = sum_i ds_ij,   g_s_dst[i,h] = sum_j ds_ij
+ *   (g_s_src / g_s_dst float32 [n_nodes, heads] contiguous; out_nobias: the forward's output without bias and ReLU; dwork:
+ *   float32 [n_nodes, heads] scratch, receives D).  Two gather launches, no floating-point atomics: the same bits on every call.
+ * Domain: 1 <= heads <= 8, f % 4 == 0, f % heads == 0, (f / heads) % 4 == 0, 16-byte aligned rows (pointers and row strides) of
+ * z, out, out_nobias, gout, gz and bias.  Anything else, and a null pointer, is EPS_EINVAL before any HIP call.
+ * Additions: no existing call changes, EPS_ABI_VERSION stays. */
+int eps_gat_aggregate(const int64_t *rowptr, const int32_t *col, int64_t row0, int64_t n_rows, int64_t n_nodes,
+                      const float *z, int64_t ldz, int32_t heads, int32_t f, const float *s_src, const float *s_dst,
+                      int64_t lds, float slope, const float *bias, int relu, float *out, int64_t ldo, float *lse,
+                      void *stream);
+int eps_gat_aggregate_backward(const int64_t *rowptr, const int32_t *col, int64_t n_nodes, const float *z, int64_t ldz,
+                               int32_t heads, int32_t f, const float *s_src, const float *s_dst, int64_t lds, float slope,
+                               const float *lse, const float *out_nobias, int64_t ldo, const float *gout, int64_t ldg,
+                               float *gz, int64_t ldgz, float *g_s_src, float *g_s_dst, float *dwork, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
