@@ -28,7 +28,7 @@ __global__ __launch_bounds__(CC_THREADS) void cos_node_features_kernel(
     const float *__restrict__ x, int64_t ldx, int32_t f, int32_t lg, float *__restrict__ xhat, int64_t ldh,
     float *__restrict__ nrm_out)
 {
-    using V = typename CcVec<VEC>::type;
+    using V = typename eps_vec<VEC>::type;
     constexpr int FLIGHT = (CC_FLIGHT_VEC4 * 4 / VEC / NCR) > 0 ? (CC_FLIGHT_VEC4 * 4 / VEC / NCR) : 1;
     const int lane = threadIdx.x & 63;
     const int G = 1 << lg, S = 64 >> lg;
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(CC_THREADS) void cos_node_features_kernel(
         for (int32_t c0 = 0; c0 < f; c0 += panel) {
             V acc[NCR];
 #pragma unroll
-            for (int t = 0; t < NCR; ++t) acc[t] = cc_zero(V());
+            for (int t = 0; t < NCR; ++t) acc[t] = eps_zero(V());
             for (int64_t k0 = b; k0 < e; k0 += 64) {
                 const int nk = (e - k0) < 64 ? (int)(e - k0) : 64;
                 const int my_col = lane < nk ? col[k0 + lane] : 0;
@@ -77,23 +77,23 @@ __global__ __launch_bounds__(CC_THREADS) void cos_node_features_kernel(
 #pragma unroll
                         for (int t = 0; t < NCR; ++t) {
                             const int c = c0 + t * span + j * VEC;
-                            xv[q][t] = cc_zero(V());
+                            xv[q][t] = eps_zero(V());
                             if (cw[q] >= 0 && c < f) xv[q][t] = cc_load(x + (int64_t)cw[q] * ldx, c, f, V());
                         }
 #pragma unroll
                     for (int q = 0; q < FLIGHT; ++q)
                         if (cw[q] >= 0)
 #pragma unroll
-                            for (int t = 0; t < NCR; ++t) cc_fma(acc[t], vw[q], xv[q][t]);
+                            for (int t = 0; t < NCR; ++t) eps_fma(acc[t], vw[q], xv[q][t]);
                 }
             }
 #pragma unroll
             for (int t = 0; t < NCR; ++t) {
                 acc[t] = cc_xor_sum(acc[t], G, 64);          // the slots' partial sums: (A @ x)_r in every slot
                 const int c = c0 + t * span + j * VEC;
-                V xp = cc_zero(V());
+                V xp = eps_zero(V());
                 if (c < f) xp = cc_axpy_div(cc_load(xr, c, f, V()), acc[t], deg);
-                ss += cc_dot(xp, xp);
+                ss += eps_dot(xp, xp);
                 keep[t] = xp;
                 if (multi && slot == 0 && c < f) cc_store(hr, c, f, xp);
             }
@@ -140,21 +140,14 @@ __global__ __launch_bounds__(CC_THREADS) void edge_cosines_kernel(const int64_t 
     for (int64_t r = wave; r < n_rows; r += n_waves) {
         int64_t b = rowptr[r];
         const int64_t e = rowptr[r + 1];
-        if (revpos) {                        // first entry with col >= r (lower bound; wave-uniform)
-            int64_t lo = b, hi = e;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (col[mid] < r) lo = mid + 1; else hi = mid;
-            }
-            b = lo;
-        }
+        if (revpos) b = eps_lower_bound(col, b, e, r);      // first entry with col >= r (wave-uniform)
         if (b >= e) continue;
         const float *__restrict__ hr = xhat + r * ldh;
         float4 xr[NCR];
 #pragma unroll
         for (int t = 0; t < NCR; ++t) {
             const int c = t * span + j * 4;
-            xr[t] = c < f ? cc_load(hr, c, f, float4()) : cc_zero(float4());
+            xr[t] = c < f ? cc_load(hr, c, f, float4()) : eps_zero(float4());
         }
         for (int64_t k0 = b; k0 < e; k0 += 64) {
             const int nk = (e - k0) < 64 ? (int)(e - k0) : 64;
@@ -175,20 +168,20 @@ __global__ __launch_bounds__(CC_THREADS) void edge_cosines_kernel(const int64_t 
 #pragma unroll
                     for (int t = 0; t < NCR; ++t) {
                         const int c = t * span + j * 4;
-                        xw[q][t] = cc_zero(float4());
+                        xw[q][t] = eps_zero(float4());
                         if (cw[q] >= 0 && c < f) xw[q][t] = cc_load(xhat + (int64_t)cw[q] * ldh, c, f, float4());
                     }
 #pragma unroll
                 for (int q = 0; q < FLIGHT; ++q)
 #pragma unroll
-                    for (int t = 0; t < NCR; ++t) d[q] += cc_dot(xr[t], xw[q][t]);
+                    for (int t = 0; t < NCR; ++t) d[q] += eps_dot(xr[t], xw[q][t]);
                 for (int t = NCR; t < nc; ++t) {     // chunks beyond the registers (F > NCR x 4G): the row re-read from cache
                     const int c = t * span + j * 4;
                     if (c >= f) break;
                     const float4 xrt = cc_load(hr, c, f, float4());
 #pragma unroll
                     for (int q = 0; q < FLIGHT; ++q)
-                        if (cw[q] >= 0) d[q] += cc_dot(xrt, cc_load(xhat + (int64_t)cw[q] * ldh, c, f, float4()));
+                        if (cw[q] >= 0) d[q] += eps_dot(xrt, cc_load(xhat + (int64_t)cw[q] * ldh, c, f, float4()));
                 }
 #pragma unroll
                 for (int q = 0; q < FLIGHT; ++q) {

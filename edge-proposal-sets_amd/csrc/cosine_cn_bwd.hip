@@ -82,7 +82,7 @@ __global__ __launch_bounds__(PB_WAVES * 64) void pair_cn_backward_kernel(
             const int32_t dju = __builtin_amdgcn_readlane(du, j);
             const int32_t djv = __builtin_amdgcn_readlane(dv, j);
             if (dju == 0 || djv == 0) continue;              // wave-uniform (also: lanes past the end of the list)
-            const int64_t bju = bcast64(ub, j), bjv = bcast64(vb, j);
+            const int64_t bju = eps_bcast64(ub, j), bjv = eps_bcast64(vb, j);
             const float gj = lane_get(gp, j);
             // (the two ends are interchangeable here: a hit at (short row, si) and (long row, li) adds g c[long] to the short
             //  row's entry and g c[short] to the long row's; u == v makes them one entry that receives both)
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(CC_THREADS) void cos_features_backward_kernel(
         for (int32_t c0 = 0; c0 < f; c0 += panel) {
             float4 acc[NCR];
 #pragma unroll
-            for (int t = 0; t < NCR; ++t) acc[t] = cc_zero(float4());
+            for (int t = 0; t < NCR; ++t) acc[t] = eps_zero(float4());
             for (int64_t k0 = b; k0 < e; k0 += 64) {
                 const int nk = (e - k0) < 64 ? (int)(e - k0) : 64;
                 const int my_col = lane < nk ? col[k0 + lane] : 0;
@@ -221,21 +221,21 @@ __global__ __launch_bounds__(CC_THREADS) void cos_features_backward_kernel(
 #pragma unroll
                         for (int t = 0; t < NCR; ++t) {
                             const int c = c0 + t * span + j * 4;
-                            xv[q][t] = cc_zero(float4());
+                            xv[q][t] = eps_zero(float4());
                             if (cw[q] >= 0 && c < f) xv[q][t] = cc_load(xhat + (int64_t)cw[q] * ldh, c, f, float4());
                         }
 #pragma unroll
                     for (int q = 0; q < FLIGHT; ++q)
                         if (cw[q] >= 0)
 #pragma unroll
-                            for (int t = 0; t < NCR; ++t) cc_fma(acc[t], sw[q], xv[q][t]);
+                            for (int t = 0; t < NCR; ++t) eps_fma(acc[t], sw[q], xv[q][t]);
                 }
             }
 #pragma unroll
             for (int t = 0; t < NCR; ++t) {
                 acc[t] = cc_xor_sum(acc[t], G, 64);          // the slots' partial sums: a_r in every slot
                 const int c = c0 + t * span + j * 4;
-                if (c < f) dotp += cc_dot(cc_load(hr, c, f, float4()), acc[t]);
+                if (c < f) dotp += eps_dot(cc_load(hr, c, f, float4()), acc[t]);
                 keep[t] = acc[t];
                 if (multi && slot == 0 && c < f) cc_store(gr, c, f, acc[t]);
             }

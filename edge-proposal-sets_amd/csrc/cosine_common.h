@@ -7,30 +7,6 @@
 #define CC_REG_CHUNKS 8          // chunks of G x VEC floats a lane keeps in registers (float4: 2048 features per wave)
 #define CC_FLIGHT_VEC4 8         // float4 loads in flight per lane per batch (divided over the chunks of a row)
 
-template <int VEC>
-struct CcVec;
-template <>
-struct CcVec<4> {
-    using type = float4;
-};
-template <>
-struct CcVec<1> {
-    using type = float;
-};
-
-__device__ __forceinline__ float4 cc_zero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float cc_zero(float) { return 0.f; }
-__device__ __forceinline__ void cc_fma(float4 &a, float s, const float4 &x)
-{
-    a.x = fmaf(s, x.x, a.x);
-    a.y = fmaf(s, x.y, a.y);
-    a.z = fmaf(s, x.z, a.z);
-    a.w = fmaf(s, x.w, a.w);
-}
-__device__ __forceinline__ void cc_fma(float &a, float s, float x) { a = fmaf(s, x, a); }
-__device__ __forceinline__ float cc_dot(const float4 &a, const float4 &b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float cc_dot(float a, float b) { return a * b; }
-
 // elements [c, c + VEC) of row p, zero past column f (c < f)
 __device__ __forceinline__ float4 cc_load(const float *__restrict__ p, int c, int f, float4)
 {

@@ -41,25 +41,8 @@ static unsigned cm_blocks(int64_t n, int per_block)
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
-// first index of [lo, hi) whose key is not below `key` (hi when there is none)
-__device__ __forceinline__ int64_t cm_lower_bound_key(const int64_t *__restrict__ x, int64_t lo, int64_t hi, int64_t key)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (x[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// first index of [lo, hi) whose column is not below c (ids compare as unsigned: a column taken from a key may be any 32 bits)
-__device__ __forceinline__ int64_t cm_lower_bound_col(const int32_t *__restrict__ col, int64_t lo, int64_t hi, uint32_t c)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((uint32_t)col[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (The searches below are eps_lower_bound.  Over col[] the key is a uint32_t, so ids compare as unsigned: a column taken from
+// a key may be any 32 bits.)
 
 // end of the run of keys equal to x[p] == key inside [p, hi): doubling steps, then a search between the last two probes (a
 // pair that occurs once costs one load; every probe stays below hi whatever the keys hold)
@@ -95,7 +78,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_flag_kernel(const int64_t *__re
         int32_t f = 0;
         if (!(bad & CM_BAD_RANGE) && (p == 0 || prev != key)) {
             const int64_t b = rowptr[row], e = rowptr[row + 1];
-            const int64_t at = cm_lower_bound_col(col, b, e, c);
+            const int64_t at = eps_lower_bound(col, b, e, c);
             f = !(at < e && (uint32_t)col[at] == c);
         }
         flag[p] = f;
@@ -113,8 +96,8 @@ __global__ __launch_bounds__(CM_THREADS) void cm_count_kernel(const int64_t *__r
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
         int64_t d = rowptr[r + 1] - rowptr[r];
         if (m > 0) {
-            const int64_t xs = cm_lower_bound_key(x, 0, m, r << 32);
-            const int64_t xe = cm_lower_bound_key(x, xs, m, (r + 1) << 32);
+            const int64_t xs = eps_lower_bound(x, (int64_t)0, m, r << 32);
+            const int64_t xe = eps_lower_bound(x, xs, m, (r + 1) << 32);
             d += xrank[xe] - xrank[xs];
         }
         new_deg[r] = d;
@@ -142,24 +125,19 @@ __global__ __launch_bounds__(CM_THREADS) void cm_fill_base_kernel(const int64_t 
             const int64_t r = r0 + tid;
             s_b[tid] = rowptr[r];
             s_nb[tid] = new_rowptr[r];
-            s_xs[tid] = m > 0 ? cm_lower_bound_key(x, 0, m, r << 32) : 0;
+            s_xs[tid] = m > 0 ? eps_lower_bound(x, (int64_t)0, m, r << 32) : 0;
         }
         __syncthreads();
         const int64_t i_end = s_b[nr];
         for (int64_t i = s_b[0] + tid; i < i_end; i += CM_THREADS) {
-            int lo = 0, hi = nr - 1;             // the row of entry i: the first k with s_b[k + 1] > i
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_b[mid + 1] <= i) lo = mid + 1; else hi = mid;
-            }
-            const int k = lo;
+            const int k = eps_lower_bound(s_b + 1, 0, nr - 1, i + 1);     // the row of entry i: the first k with s_b[k + 1] > i
             const int32_t c = col[i];
             float v = val ? val[i] : 1.0f;
             int64_t dest = s_nb[k] + (i - s_b[k]);
             const int64_t xs = s_xs[k], xe = s_xs[k + 1];
             if (xe > xs) {                       // the row receives keys: the new ones among those with a smaller column go in front
                 const int64_t key = ((r0 + k) << 32) | (int64_t)(uint32_t)c;
-                const int64_t p = cm_lower_bound_key(x, xs, xe, key);
+                const int64_t p = eps_lower_bound(x, xs, xe, key);
                 dest += xrank[p] - xrank[xs];
                 if (new_val && p < xe && x[p] == key) v += (float)(cm_run_end(x, p, xe, key) - p);
             }
@@ -186,7 +164,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_fill_new_kernel(const int64_t *
         const int64_t key = x[p], row = key >> 32;
         if (row < 0 || row >= n) continue;
         const uint32_t c = (uint32_t)key;
-        const int64_t dest = cm_lower_bound_col(col, rowptr[row], rowptr[row + 1], c) + g;
+        const int64_t dest = eps_lower_bound(col, rowptr[row], rowptr[row + 1], c) + g;
         if (dest < 0 || dest < new_rowptr[row] || dest >= new_rowptr[row + 1] || dest >= new_nnz) continue;
         new_col[dest] = (int32_t)c;
         if (new_val) new_val[dest] = (float)(cm_run_end(x, p, m, key) - p);

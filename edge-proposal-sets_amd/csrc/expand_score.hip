@@ -36,7 +36,6 @@
 // host falls back to the tensor-op expansion above that.
 #include "eps_common.h"
 
-
 #define EX_THREADS 1024
 #define EX_WAVES (EX_THREADS / 64)
 #define EX_FIXED_SHIFT 40
@@ -47,29 +46,9 @@
 #define EX_TILE 8192        // candidate ranks per tile: 64 KiB of accumulators + 32 KiB of counters, aliasing the bitmap
 #define EX_TABLE_WORDS (5 * EX_RANGES + 1)
 
-
-__device__ __forceinline__ int wave_incl_scan(int x, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ long long ex_to_fixed(float x)
 {
     return __double2ll_rn((double)x * (double)(1ll << EX_FIXED_SHIFT));
-}
-
-__device__ __forceinline__ int64_t ex_bcast64(int64_t x, int j)
-{
-    const int lo = __builtin_amdgcn_readlane((int)(x & 0xffffffffll), j);
-    const int hi = __builtin_amdgcn_readlane((int)(x >> 32), j);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
 }
 
 // Walk the 2-hop paths v - w - u of one column, all 16 waves of the workgroup together.
@@ -123,8 +102,7 @@ __device__ __forceinline__ void for_each_path(const int64_t *__restrict__ rowptr
         auto first_unit = [&](int jj) {
             const int jl = jj & 63;
             const int32_t dn = jj < nrows ? __builtin_amdgcn_readlane(dw_mine, jl) : 0;
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc((void *)(col + ex_bcast64(wb_mine, jl)), 0, dn * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = eps_raw_rsrc(col + eps_bcast64(wb_mine, jl), dn * 4);
             return __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, 0);
         };
         v4i ring[EX_RING];
@@ -136,7 +114,7 @@ __device__ __forceinline__ void for_each_path(const int64_t *__restrict__ rowptr
                 const int j = j0 + r;
                 if (j >= nrows) break;
                 const int32_t dw = __builtin_amdgcn_readlane(dw_mine, j);
-                const int64_t wb = ex_bcast64(wb_mine, j);
+                const int64_t wb = eps_bcast64(wb_mine, j);
                 const v4i cur = ring[r];
                 ring[r] = first_unit(j + EX_RING);
                 const int k = b0 + EX_WAVES * j;
@@ -149,8 +127,7 @@ __device__ __forceinline__ void for_each_path(const int64_t *__restrict__ rowptr
                     if (q < EX_LONGQ) {
                         if (lane == 0) s_long[q] = k;
                     } else {  // queue full (a hub column with thousands of long rows): finish this row here
-                        const __amdgpu_buffer_rsrc_t rj =
-                            __builtin_amdgcn_make_buffer_rsrc((void *)(col + wb), 0, dw * 4, 0x00020000);
+                        const __amdgpu_buffer_rsrc_t rj = eps_raw_rsrc(col + wb, dw * 4);
                         for (int e0 = 256; e0 < dw; e0 += 512) {
                             const v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(rj, lane * 16 + e0 * 4, 0, 0);
                             const v4i x1 = __builtin_amdgcn_raw_buffer_load_b128(rj, lane * 16 + e0 * 4 + 1024, 0, 0);
@@ -176,12 +153,12 @@ __device__ __forceinline__ void for_each_path(const int64_t *__restrict__ rowptr
         const int n = nl - q0 < 64 ? nl - q0 : 64;
         for (int j = 0; j < n; ++j) {
             const int32_t dw = __builtin_amdgcn_readlane(dw_mine, j);
-            const int64_t wb = ex_bcast64(wb_mine, j);
+            const int64_t wb = eps_bcast64(wb_mine, j);
             const int k = __builtin_amdgcn_readlane(k_mine, j);
             int c0 = (wib - (q0 + j)) & (EX_WAVES - 1);
             if (c0 == 0) c0 = EX_WAVES;
             if (c0 * 256 >= dw) continue;
-            const __amdgpu_buffer_rsrc_t rj = __builtin_amdgcn_make_buffer_rsrc((void *)(col + wb), 0, dw * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rj = eps_raw_rsrc(col + wb, dw * 4);
             for (int e0 = c0 * 256; e0 < dw; e0 += 2 * EX_WAVES * 256) {  // two of this wave's units in flight per trip
                 const int e1 = e0 + EX_WAVES * 256;
                 const v4i x0 = __builtin_amdgcn_raw_buffer_load_b128(rj, lane * 16 + e0 * 4, 0, 0);
@@ -297,7 +274,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
             // words, so the candidates a wave emits in one trip are consecutive in rank and their stores land in a few lines.
             int local = 0;
             for (int i = 0; i < wpt; ++i) local += __popc(bm[w0 + 64 * i]);
-            const int incl = wave_incl_scan(local, lane);
+            const int incl = eps_wave_incl_scan<int>(local, lane);
             if (lane == 63) s_wave_tot[wib] = incl;
             __syncthreads();
             int wave_base = 0, total = 0;
@@ -334,7 +311,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
                     const int wi = w0 + 64 * i;
                     uint32_t bits = bm[wi];
                     const int c = __popc(bits);
-                    const int inc = wave_incl_scan(c, lane);
+                    const int inc = eps_wave_incl_scan<int>(c, lane);
                     int run = wrun + inc - c;          // rank of this word's first bit
                     const int gbase = __shfl(run, lane & ~7);   // ... of its 8-word group's first bit (the 8 lanes are neighbours)
                     if ((lane & 7) == 0) base32[wi >> 3] = (uint32_t)run;
@@ -366,7 +343,7 @@ __global__ __launch_bounds__(EX_THREADS) void expand_kernel(
                 const uint32_t rs = in ? base32[tid << (range_shift - 8)] : 0u;       // rank at the start of the range
                 const uint32_t paths = in ? hist[tid] : 0u;
                 if (in) hist[tid] = 0u;
-                const int pin = wave_incl_scan((int)paths, lane);
+                const int pin = eps_wave_incl_scan<int>((int)paths, lane);
                 if (lane == 63) s_wave_tot[wib] = pin;
                 __syncthreads();
                 uint32_t pbase = 0, ptotal = 0;

@@ -42,8 +42,6 @@
 #define FS_SVCAP 384         // survivors of a column parked in LDS until its tiles are done (more: resolved on the spot)
 #define FS_MAX_TILE_BITS 12  // candidate ranks per tile <= 4096 (8-byte accumulators in LDS)
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 // LDS carve-up, in 32-bit words from the start of the dynamic region (every section starts 8-byte aligned)
 struct fs_layout {
     int words;      // bitmap words, a multiple of 1024
@@ -111,21 +109,9 @@ struct fs_params {
 #define FS_EMIT 1             // write every candidate (and its score)
 #define FS_COUNT 2            // count the candidates per column
 
-// Wave-wide inclusive scans on the DPP path (row shifts inside the 16-lane rows, then the two row broadcasts): six
-// VALU instructions, no LDS traffic.  Lanes a shift does not reach add 0 (values are non-negative for the max form).
-__device__ __forceinline__ int fs_wave_incl_scan(int x, int)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);   // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);   // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
 __device__ __forceinline__ int fs_max(int a, int b) { return a > b ? a : b; }
 
+// eps_wave_incl_scan_dpp's ladder with max for + (lanes a shift does not reach contribute 0: values are non-negative)
 __device__ __forceinline__ int fs_wave_incl_max(int x, int)
 {
     x = fs_max(x, __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false));
@@ -137,10 +123,8 @@ __device__ __forceinline__ int fs_wave_incl_max(int x, int)
     return x;
 }
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter, which would
-// end every global load a wave keeps in flight across the barrier (record and row prefetches); all hand-offs between the
-// waves of this kernel go through LDS except one (bucket records: D1 -> D2), which keeps __syncthreads().
-__device__ __forceinline__ void fs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (eps_lds_barrier: all hand-offs between the waves of this kernel go through LDS except one -- bucket records: D1 -> D2 --
+// which keeps __syncthreads().)
 
 // 16-byte store to a dword-aligned address (global memory takes unaligned vector stores)
 typedef uint32_t fs_u4a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -214,7 +198,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
     float *__restrict__ out_val = MODE == FS_SCAN ? p.out->val : nullptr;
     uint32_t *__restrict__ my_scratch = p.scratch + (size_t)blockIdx.x * ((size_t)p.cap_records + 64);   // + a trash line
     long long *__restrict__ my_gfix = p.gfix + (size_t)blockIdx.x * (size_t)p.max_degree;
-    const __amdgpu_buffer_rsrc_t col_rs = __builtin_amdgcn_make_buffer_rsrc((void *)p.col, 0, p.col_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t col_rs = eps_raw_rsrc(p.col, p.col_bytes);
 
     for (int i = tid; i < words; i += FS_THREADS) bm[i] = 0u;
     for (int i = tid; i < TILE; i += FS_THREADS) acc[i] = 0ull;
@@ -332,7 +316,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 nun = (int)((rl + 63u) >> 6);
                 if (tid == 0) nun -= c0;
             }
-            int incl = fs_wave_incl_scan(nun, lane);
+            int incl = eps_wave_incl_scan_dpp(nun);
             if (lane == 63) s_wtot[wib] = incl;
             ((uint32_t *)ulist)[tid] = 0u;
             if (tid < FS_UPAD / 2) ((uint32_t *)ulist)[FS_UR / 2 + tid] = (uint32_t)(FS_RC + 1) * 0x10001u;
@@ -340,7 +324,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 s_done = 0;
                 s_next_c = 0;
             }
-            fs_barrier();
+            eps_lds_barrier();
             int woff = 0, total = 0;
 #pragma unroll
             for (int i = 0; i < FS_RC / 64; ++i) {
@@ -363,7 +347,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             const unsigned long long dm = __ballot(row_ok && incl <= FS_UR);
             if (lane == 0 && dm) atomicAdd(&s_done, __popcll(dm));
             if (row_ok && incl > FS_UR && excl <= FS_UR) s_next_c = (FS_UR - excl) + (tid == 0 ? c0 : 0);
-            fs_barrier();
+            eps_lds_barrier();
             // unit -> row: the last row that starts at or before the unit (block-wide inclusive max-scan, 2 units per thread)
             {
                 const uint32_t pr = ((uint32_t *)ulist)[tid];
@@ -373,7 +357,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 if (lane == 63) s_wtot[wib] = inc;
                 int prev = __shfl_up(inc, 1);
                 if (lane == 0) prev = 0;
-                fs_barrier();
+                eps_lds_barrier();
                 int carry = 0;
 #pragma unroll
                 for (int i = 0; i < FS_WAVES; ++i) {
@@ -388,7 +372,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 if (2 * tid + 1 >= n_units) b = FS_RC + 1;
                 ((uint32_t *)ulist)[tid] = (uint32_t)a | ((uint32_t)b << 16);
             }
-            fs_barrier();
+            eps_lds_barrier();
             return total < FS_UR ? total : FS_UR;
         };
 
@@ -457,10 +441,10 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             j = nj;
             c = nc;
             if (j >= dv) break;
-            fs_barrier();       // the next round overwrites the descriptors this walk reads
+            eps_lds_barrier();       // the next round overwrites the descriptors this walk reads
         }
         if (staged < 2) stage2();
-        fs_barrier();
+        eps_lds_barrier();
         for (int k = tid; k < dv; k += FS_THREADS) {   // known edges out (the diagonal is not below v)
             const uint32_t u = (uint32_t)(vcol[k] - win_lo);
             if (u < (uint32_t)vlim) atomicAnd(&bm[u >> 5], ~(1u << (u & 31)));
@@ -469,7 +453,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             const uint32_t u = (uint32_t)(v - win_lo);
             if (u < (uint32_t)vlim) atomicAnd(&bm[u >> 5], ~(1u << (u & 31)));
         }
-        fs_barrier();
+        eps_lds_barrier();
 
         // ---- B. rank tables: exclusive prefix of the per-word popcounts over the words below v -------------------------
         // Thread t owns the 8-word groups t, t + 1024, ... (two 16-byte reads per group, consecutive threads on consecutive
@@ -497,16 +481,16 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
         for (int i = 0; i < 4; ++i) {
             ginc[i] = 0;
             if (i < trips) {
-                ginc[i] = fs_wave_incl_scan(gcnt[i], lane);
+                ginc[i] = eps_wave_incl_scan_dpp(gcnt[i]);
                 if (lane == 63) s_wtot[i * FS_WAVES + wib] = ginc[i];
             }
         }
-        fs_barrier();
+        eps_lds_barrier();
         int total;
         {
             // exclusive prefix over the (trip, wave) totals, in every wave: lane l holds total l
             const int tv = lane < trips * FS_WAVES ? s_wtot[lane] : 0;
-            const int tinc = fs_wave_incl_scan(tv, lane);
+            const int tinc = eps_wave_incl_scan_dpp(tv);
             total = __builtin_amdgcn_readlane(tinc, 63);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -531,7 +515,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 listed = true;
             } else {
                 // the list: thread per bitmap word (neighbouring lanes -> neighbouring ranks), ascending u
-                fs_barrier();                             // rank tables complete
+                eps_lds_barrier();                             // rank tables complete
                 for (int wi = tid; wi < words_v; wi += FS_THREADS) {
                     uint32_t bits = bm[wi];
                     if (bits) {
@@ -549,14 +533,14 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
         }
         col_off += total;
         if (total == 0 || listed) {          // nothing to score (SCAN: every endpoint is a neighbour of v)
-            if (MODE == FS_EMIT && total) fs_barrier();      // (the list pass read the bitmap)
+            if (MODE == FS_EMIT && total) eps_lds_barrier();      // (the list pass read the bitmap)
             if (tid < n_ranges) hist[tid] = 0u;
             for (int i = tid; i < words_v; i += FS_THREADS) bm[i] = 0u;
             if (!WINDOWED || seg_overflow) break;
-            fs_barrier();              // (the next window marks into the words other threads just cleared)
+            eps_lds_barrier();              // (the next window marks into the words other threads just cleared)
             continue;
         }
-        fs_barrier();
+        eps_lds_barrier();
 
         // ---- plan: tiles of TILE consecutive candidate ranks (the last one partial); bucket room from the path histogram ----
         // A path's tile is its rank >> tile_bits.  The paths per id range are known (pass A), the paths per TILE are not -- a range
@@ -573,9 +557,9 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             const uint32_t tile = rs >> p.tile_bits;
             const bool straddle = re > rs && ((re - 1u) >> p.tile_bits) != tile;
             const uint32_t room = straddle ? 2u * paths : paths;
-            const int pin = fs_wave_incl_scan((int)room, lane);
+            const int pin = eps_wave_incl_scan_dpp((int)room);
             if (lane == 63) s_wtot[wib] = pin;
-            fs_barrier();
+            eps_lds_barrier();
             uint32_t pbase = 0, ptotal = 0;
 #pragma unroll
             for (int i = 0; i < FS_WAVES; ++i) {
@@ -592,7 +576,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 s_ntiles = nt;
                 tile_base[nt] = ptotal;
             }
-            fs_barrier();
+            eps_lds_barrier();
         }
         const int n_tiles = s_ntiles;
         uint32_t *ginfo = base32;
@@ -672,7 +656,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 while (t_hi < n_tiles && tile_base[t_hi + 1] - tile_base[t_lo] <= p.cap_records) ++t_hi;
                 s_thi = t_hi;
             }
-            fs_barrier();
+            eps_lds_barrier();
             const int t_hi = s_thi;
             const bool direct = t_hi - t_lo == 1;
             const uint32_t win_base = tile_base[t_lo];
@@ -683,7 +667,7 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
             c = 0;
             for (;;) {
                 if (!single) n_units = build_round(j, c);
-                else fs_barrier();
+                else eps_lds_barrier();
                 const int nj = single ? dv : j + s_done, nc = single ? 0 : s_next_c;
                 const int j_round = j;
                 // per entry: is it a candidate of the window, and its rank inside its tile.  No branch per entry: an entry
@@ -755,11 +739,11 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                 j = nj;
                 c = nc;
                 if (j >= dv) break;
-                fs_barrier();
+                eps_lds_barrier();
             }
             if (direct) {
                 if (tid == 0) reserve_out(t_lo);
-                fs_barrier();
+                eps_lds_barrier();
                 scan_tile(t_lo);
             } else {
                 // per tile: records -> sums in LDS -> scan.  The first four records per thread of the NEXT tile are
@@ -792,26 +776,26 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
                         add4(*(const uint4 *)(my_scratch + cb0 + i0), i0, cn);
                     if (t + 1 < t_hi) request(t + 1);
                     if (tid == 0) reserve_out(t);
-                    fs_barrier();               // sums complete
+                    eps_lds_barrier();               // sums complete
                     scan_tile(t);
-                    fs_barrier();               // accumulators zero again
+                    eps_lds_barrier();               // accumulators zero again
                 }
             }
-            fs_barrier();           // scans done: the parked survivors are all in
+            eps_lds_barrier();           // scans done: the parked survivors are all in
             {
                 const uint32_t nsv = s_nsv < FS_SVCAP ? s_nsv : FS_SVCAP;
                 if (nsv) {             // (uniform) resolve them, one per thread; room was reserved with the tiles
                     if ((uint32_t)tid < nsv) resolve(sv_rank[tid], sv_val[tid]);
-                    fs_barrier();
+                    eps_lds_barrier();
                     if (tid == 0) s_nsv = 0u;
-                    fs_barrier();
+                    eps_lds_barrier();
                 }
             }
             t_lo = t_hi;
         }
         for (int i = tid; i < words_v; i += FS_THREADS) bm[i] = 0u;
         if (!WINDOWED) break;
-        fs_barrier();                  // the next window marks into the words other threads just cleared
+        eps_lds_barrier();                  // the next window marks into the words other threads just cleared
         }
         }
         if (MODE != FS_SCAN) {
@@ -825,10 +809,10 @@ __global__ __launch_bounds__(FS_THREADS) void filter_scan_kernel(fs_params p)
         }
         if (staged == 0) {             // (a column without work: the stages still have to run)
             stage1();
-            fs_barrier();              // every thread has read the previous ticket
+            eps_lds_barrier();              // every thread has read the previous ticket
             stage2();
         }
-        fs_barrier();                  // thread 0's ticket is in LDS; the column's LDS state is clean
+        eps_lds_barrier();                  // thread 0's ticket is in LDS; the column's LDS state is clean
         t_nx2 = __builtin_amdgcn_readfirstlane(s_tq);
         v_cur = v_nx;
         vb_cur = vb_nx;
@@ -853,12 +837,8 @@ __global__ void reverse_positions_kernel(const int64_t *__restrict__ rowptr, con
         bool odd = false;                    // an entry (v, w) without its mirror (w, v)
         for (int64_t i = b + lane; i < e; i += 64) {
             const int32_t w = col[i];
-            int64_t lo = rowptr[w], hi = rowptr[w + 1];
-            const int64_t wb = lo, we = hi;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (col[mid] < (int32_t)v) lo = mid + 1; else hi = mid;
-            }
+            const int64_t wb = rowptr[w], we = rowptr[w + 1];
+            const int64_t lo = eps_lower_bound(col, wb, we, (int32_t)v);
             revpos[i] = (int32_t)(lo - wb);
             below += lo - wb;
             odd |= lo >= we || col[lo] != (int32_t)v;
@@ -880,13 +860,8 @@ __global__ void row_window_splits_kernel(const int64_t *__restrict__ rowptr, con
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes * n_cuts; i += stride) {
         const int64_t w = i % n_nodes, k = i / n_nodes;
         const int64_t bound = (k + 1) * win_ids;
-        int64_t lo = rowptr[w], hi = rowptr[w + 1];
-        const int64_t wb = lo;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (col[mid] < bound) lo = mid + 1; else hi = mid;
-        }
-        splits[i] = (int32_t)(lo - wb);
+        const int64_t wb = rowptr[w];
+        splits[i] = (int32_t)(eps_lower_bound(col, wb, rowptr[w + 1], bound) - wb);      // (ids compare as int64_t: the bound may pass 2^31)
     }
 }
 

@@ -31,15 +31,7 @@
 #define GA_TILE_LD 65       // tile[head][entry] row length: 64 entries + 1 (a wave's reads for one entry then fall on distinct banks)
 #define GA_WAVES 4          // waves per workgroup
 
-__device__ __forceinline__ void ga_fma(float4 &a, float s, const float4 &x)
-{
-    a.x = fmaf(s, x.x, a.x);
-    a.y = fmaf(s, x.y, a.y);
-    a.z = fmaf(s, x.z, a.z);
-    a.w = fmaf(s, x.w, a.w);
-}
 __device__ __forceinline__ float ga_leaky(float raw, float slope) { return raw > 0.f ? raw : raw * slope; }
-__device__ __forceinline__ float ga_dot(const float4 &a, const float4 &b) { return ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w; }
 
 // Per-head sums of one value per lane (lane L holds columns c0 + 4L ..): lane h < heads adds, in ascending lane order, the lanes
 // whose columns belong to head h, and returns the sum (other lanes: 0).  ``strip``: 64 wave-private floats.
@@ -79,9 +71,9 @@ __device__ __forceinline__ void ga_gather(const float *__restrict__ x, int64_t l
 #pragma unroll
         for (int q = 0; q < GA_FLIGHT; ++q) {
             if (!G || j + q < nk) {
-                ga_fma(acc, w1[j + q], xv[q]);
+                eps_fma(acc, w1[j + q], xv[q]);
                 if (NACC == 2) {
-                    ga_fma(acc2, w2[j + q], xv[q]);
+                    eps_fma(acc2, w2[j + q], xv[q]);
                     l += w3[j + q];
                 } else {
                     l += w1[j + q];
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gat_aggregate_kernel(
             // the self loop first
             float l = expf(ga_leaky(ss_self[hl] + sd[hl], slope) - mx[hl]);
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), none = acc;
-            if (act) ga_fma(acc, l, *reinterpret_cast<const float4 *>(z + self * ldz + c));
+            if (act) eps_fma(acc, l, *reinterpret_cast<const float4 *>(z + self * ldz + c));
             for (int64_t k0 = b; k0 < e; k0 += 64) {
                 const int nk = (e - k0) < 64 ? (int)(e - k0) : 64;
                 const int my_col = lane < nk ? col[k0 + lane] : 0;
@@ -192,7 +184,7 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gat_backward_dst_kernel(
             float l = raw0 > 0.f ? a0 : a0 * slope;   // sum_j w_ij of this lane's head, the self loop first
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), none = acc, go = acc, ob = acc;
             if (act) {
-                ga_fma(acc, l, *reinterpret_cast<const float4 *>(z + r * ldz + c));
+                eps_fma(acc, l, *reinterpret_cast<const float4 *>(z + r * ldz + c));
                 go = *reinterpret_cast<const float4 *>(gout + r * ldg + c);
                 ob = *reinterpret_cast<const float4 *>(outnb + r * ldo + c);
             }
@@ -213,8 +205,8 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gat_backward_dst_kernel(
                 lds_wave_sync();
                 ga_gather<1>(z, ldz, c, act, my_col, nk, w, w, w, acc, none, l);
             }
-            dsum += ga_head_sum(ga_dot(go, ob), strip, lane, c0, f, heads, C);
-            tsum += ga_head_sum(ga_dot(go, acc), strip, lane, c0, f, heads, C);
+            dsum += ga_head_sum(eps_dot(go, ob), strip, lane, c0, f, heads, C);
+            tsum += ga_head_sum(eps_dot(go, acc), strip, lane, c0, f, heads, C);
             lds_wave_sync();
             if (act && c % C == 0) wsum[hl] = l;      // (every lane of a head holds the same l)
             lds_wave_sync();
@@ -258,8 +250,8 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gat_backward_src_kernel(
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), acc2 = acc, zr = acc;
             if (act) {
                 const float4 g0 = *reinterpret_cast<const float4 *>(gout + r * ldg + c);
-                ga_fma(acc, a0, g0);
-                ga_fma(acc2, w0, g0);
+                eps_fma(acc, a0, g0);
+                eps_fma(acc2, w0, g0);
                 zr = *reinterpret_cast<const float4 *>(z + r * ldz + c);
             }
             for (int64_t k0 = b; k0 < e; k0 += 64) {
@@ -284,7 +276,7 @@ __global__ __launch_bounds__(64 * GA_WAVES) void gat_backward_src_kernel(
                              tile_wd + hl * GA_TILE_LD, acc, acc2, l);
             }
             if (act) *reinterpret_cast<float4 *>(gz + r * ldgz + c) = acc;
-            tsum += ga_head_sum(ga_dot(zr, acc2), strip, lane, c0, f, heads, C);
+            tsum += ga_head_sum(eps_dot(zr, acc2), strip, lane, c0, f, heads, C);
             lds_wave_sync();
             if (act && c % C == 0) wsum[hl] = l;
             lds_wave_sync();

@@ -14,8 +14,6 @@
 // bank slots.  Global->register->LDS double buffering, one barrier per K-chunk.
 #include "eps_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 #define G_BM 128
 #define G_BN 128
 #define G_BK 16  // 40 KiB of LDS per workgroup -> four resident workgroups per CU on the aligned path (128 VGPRs); 32 and 64 measured slower
@@ -23,8 +21,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define G_F4 (G_BK / 4)          // float4 per tile row
 #define G_NLD (G_BM * G_F4 / 256)  // float4 per thread and operand
 #define G_NJ (G_BK / 8)
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // One float4 of an operand tile through a raw buffer descriptor that covers rows [row0, nrows) of the matrix:
 // rows past the end fall outside the descriptor and read as zeros (no exec-mask branch), the K tail is pushed out
@@ -58,7 +54,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const float *base, i
     const int64_t cap = (int64_t)G_BM * ld * 4 + 64;  // ... so the descriptor never needs to exceed one tile (+ slack)
     if (bytes > cap) bytes = cap;
     if (bytes < 0) bytes = 0;
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(base + row0 * ld), 0, (int)bytes, 0x00020000);
+    return eps_raw_rsrc(base + row0 * ld, (int)bytes);
 }
 
 // ALIGNED: every operand row and the C rows are 16-byte aligned and K % 4 == 0 (every layer of the recipes): no

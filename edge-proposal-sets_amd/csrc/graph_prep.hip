@@ -130,12 +130,8 @@ __global__ __launch_bounds__(256) void gp_revpos_half_kernel(const int64_t *__re
                 revpos[i] = (int32_t)(i - b);
                 continue;
             }
-            int64_t lo = rowptr[w], hi = rowptr[w + 1];
-            const int64_t wb = lo, we = hi;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (col[mid] < (int32_t)v) lo = mid + 1; else hi = mid;
-            }
+            const int64_t wb = rowptr[w], we = rowptr[w + 1];
+            const int64_t lo = eps_lower_bound(col, wb, we, (int32_t)v);
             revpos[i] = (int32_t)(lo - wb);                    // entries of row w below v: the position of v in row w
             if (lo < we && col[lo] == (int32_t)v)
                 revpos[lo] = (int32_t)(i - b);                 // ... and there sits the mirror entry: w is at position i - b of row v

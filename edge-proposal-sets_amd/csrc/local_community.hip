@@ -72,18 +72,6 @@ __device__ __forceinline__ int64_t lc_shfl64(int64_t x, int l)
     return ((int64_t)hi << 32) | (uint32_t)lo;
 }
 
-// Entries of the ascending a[0..n) below t; n differs from lane to lane.
-__device__ __forceinline__ int lc_lower_bound(const int32_t *__restrict__ a, int n, int t)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // Segment p of ptr clamped into [0, total]; `bad` when it had to be.
 __device__ __forceinline__ void lc_segment(const int64_t *__restrict__ ptr, int64_t p, int64_t total, int64_t &sb, int64_t &se, bool &bad)
 {
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                 const int wi = w[bs + i], z = w[bs + j];
                 const int64_t rb = rowptr[wi];
                 const int d = (int)(rowptr[wi + 1] - rb);
-                const int pos = lc_lower_bound(col + rb, d, z);
+                const int pos = eps_lower_bound(col + rb, 0, d, z);
                 found = pos < d && col[rb + pos] == z;
             }
             const uint64_t m = __ballot(found);
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
         for (int j = 0; j < group; ++j) {
             const int cj = __builtin_amdgcn_readlane(c, j);
             if (cj <= LC_SHORT) continue;                    // wave-uniform
-            const int64_t bj = bcast64(sb, j);
+            const int64_t bj = eps_bcast64(sb, j);
             const int32_t *__restrict__ seg = w + bj;
             int32_t *__restrict__ gseg = gamma + bj;
             bool seg_bad = false;
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_degrees_kernel(
                         todo &= todo - 1;
                         const int dm = __builtin_amdgcn_readlane(d, m);
                         const int wm = __builtin_amdgcn_readlane(wi, m);
-                        const int32_t *__restrict__ row = col + bcast64(rb, m);
+                        const int32_t *__restrict__ row = col + eps_bcast64(rb, m);
                         int cnt = 0;
                         for (int k0 = 0; k0 < n; k0 += 64) {
                             const int k = k0 + lane;
@@ -322,7 +310,7 @@ __global__ __launch_bounds__(LC_WAVES * 64) void local_community_scores_kernel(
         for (int j = 0; j < 64; ++j) {                       // the whole wave: blocks of 64 entries, first to last
             const int cj = __builtin_amdgcn_readlane(wide, j);
             if (cj == 0) continue;
-            const int64_t bj = bcast64(sb, j);
+            const int64_t bj = eps_bcast64(sb, j);
             int64_t gj = 0;
             double sj = 0.0;
             for (int k0 = 0; k0 < cj; k0 += 64) {

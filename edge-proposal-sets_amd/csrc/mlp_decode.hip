@@ -27,10 +27,6 @@
 // bf16/"xf32" shortcuts (and gfx950 has no xf32).
 #include "eps_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (HIP's float4 struct copies lower to memcpy -> scratch)
-
 #define D_BM 64        // edges per tile
 #define D_HMAX 256     // widest hidden size of mlp_decode_kernel (wider: mlp_decode_wide_kernel)
 #define D_XLD (D_HMAX + 4)
@@ -136,7 +132,7 @@ __global__ __launch_bounds__(D_THREADS, 4) void mlp_decode_kernel(const float *_
         for (int l = 0; l + 1 < n_layers; ++l) {
             const float *__restrict__ W = pick(prm.w, l);
             const float *__restrict__ Bv = pick(prm.b, l);
-            const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)W, 0, H * H * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t wr = eps_raw_rsrc(W, H * H * 4);
             f32x16 acc[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -296,7 +292,7 @@ __global__ __launch_bounds__(D_THREADS, 4) void mlp_decode_wide_kernel(const flo
         for (int l = 0; l + 1 < n_layers; ++l) {
             const float *__restrict__ W = pick(prm.w, l);
             const float *__restrict__ Bv = pick(prm.b, l);
-            const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)W, 0, H * H * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t wr = eps_raw_rsrc(W, H * H * 4);
             f32x16 acc[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)

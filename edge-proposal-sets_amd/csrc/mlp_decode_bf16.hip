@@ -26,9 +26,6 @@
 // H % 32 == 16 reads zeros past the end of W through the buffer descriptor and writes nothing.
 #include "eps_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(B_THREADS, 2 * B_WG_PER_CU) void mlp_decode_bf16_ke
         for (int l = 0; l + 1 < n_layers; ++l) {
             const bool last_hidden = l + 2 == n_layers;
             const float *__restrict__ Bv = pick(prm.b, l);
-            const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)pick(prm.w, l), 0, H * H * 2, 0x00020000);
+            const __amdgpu_buffer_rsrc_t wr = eps_raw_rsrc(pick(prm.w, l), H * H * 2);
             f32x16 acc[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j)

@@ -25,9 +25,6 @@
 // the same bits.  (An H x H accumulator per hidden layer would be 128 registers per lane at H = 256, hence the spills.)
 #include "eps_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 #define T_BM 64        // edges per tile
 #define T_HMAX 256
 #define T_HMIN 32      // at least one whole 32-column MFMA tile (narrower widths stay on the torch route)
@@ -94,7 +91,7 @@ __device__ __forceinline__ void t_matmul(f32x16 (&acc)[2], const float (*Xs)[T_X
                                          int r, int hh)
 {
     const int nk = ((H + 31) & ~31) / T_BK;
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)M, 0, H * H * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = eps_raw_rsrc(M, H * H * 4);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -774,7 +771,7 @@ __global__ __launch_bounds__(T_THREADS, 4) void mlp_decode_bn_dgamma_kernel(int3
         const int nv = n_pairs - e0 < T_BM ? (int)(n_pairs - e0) : T_BM;      // rows of the tile that are edges
         const double bm = okc ? (double)b0[cc] - (double)mean[cc] : 0.0;
         const double isig = okc ? 1.0 / sqrt((double)var[cc] + (double)eps) : 0.0;
-        const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc((void *)(dZ + e0 * H), 0, T_BM * H * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t dyr = eps_raw_rsrc(dZ + e0 * H, T_BM * H * 4);
         if (has0) {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -845,8 +842,8 @@ __global__ __launch_bounds__(T_THREADS, 2) void mlp_decode_bn_dz_kernel(int32_t 
             dgB = dgamma[cc] / (double)n_pairs;
         }
         // (the tile's rows of dy / dx0 through buffer descriptors: one 32-bit offset per element, not a 64-bit address)
-        const __amdgpu_buffer_rsrc_t dyr = __builtin_amdgcn_make_buffer_rsrc((void *)(dZ + e0 * H), 0, T_BM * H * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t dxr = __builtin_amdgcn_make_buffer_rsrc((void *)(dx0 + e0 * H), 0, T_BM * H * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t dyr = eps_raw_rsrc(dZ + e0 * H, T_BM * H * 4);
+        const __amdgpu_buffer_rsrc_t dxr = eps_raw_rsrc(dx0 + e0 * H, T_BM * H * 4);
         if (has0) {
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)

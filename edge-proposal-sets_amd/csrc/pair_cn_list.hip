@@ -57,8 +57,8 @@ __global__ __launch_bounds__(CL_WAVES * 64) void pair_cn_list_kernel(
             const int32_t dju = __builtin_amdgcn_readlane(du, j);
             const int32_t djv = __builtin_amdgcn_readlane(dv, j);
             if (dju <= 0 || djv <= 0) continue;              // wave-uniform (also: lanes past the end of the list, ids out of range)
-            const int64_t bju = bcast64(ub, j), bjv = bcast64(vb, j);
-            const int64_t ob = FILL ? bcast64(seg_b, j) : 0, oe = FILL ? bcast64(seg_e, j) : 0;
+            const int64_t bju = eps_bcast64(ub, j), bjv = eps_bcast64(vb, j);
+            const int64_t ob = FILL ? eps_bcast64(seg_b, j) : 0, oe = FILL ? eps_bcast64(seg_e, j) : 0;
             const bool swapped = dju > djv;                  // short row = v
             const int32_t slen = swapped ? djv : dju, llen = swapped ? dju : djv;
             const int64_t sbase = swapped ? bjv : bju, lbase = swapped ? bju : bjv;
@@ -168,13 +168,8 @@ __global__ void cn_list_tptr_kernel(const int32_t *__restrict__ w_sorted, int64_
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w <= n_rows; w += stride) {
-        int64_t lo = 0, hi = m;                              // entries of w_sorted below w
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)w_sorted[mid] < w) lo = mid + 1;
-            else hi = mid;
-        }
-        tptr[w] = w == n_rows ? m : lo;
+        const int64_t below = eps_lower_bound(w_sorted, (int64_t)0, m, w);      // entries of w_sorted below w
+        tptr[w] = w == n_rows ? m : below;
     }
 }
 

@@ -2,13 +2,6 @@
 #pragma once
 #include "eps_common.h"
 
-__device__ __forceinline__ int64_t bcast64(int64_t x, int j)
-{
-    int lo = __builtin_amdgcn_readlane((int)(x & 0xffffffffll), j);
-    int hi = __builtin_amdgcn_readlane((int)(x >> 32), j);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
-}
-
 // Number of elements of the ascending array a[0..n) that are < t.  Same trip count in every
 // lane (n is wave-uniform), no divergent branches.
 template <typename P>
@@ -38,15 +31,8 @@ __device__ __forceinline__ void pair_products(const float *__restrict__ val, con
     if (HAS_W) acc_ws += (WT)va * ((WT)vbv * node_w[t]);  // A_ entry rounded first (adamic_utils.py:17)
 }
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// Buffer resource over one adjacency row: raw (stride 0) descriptor with num_records = row bytes, so a
-// dwordx4 load needs no exec masking and no bounds branch -- out-of-range dwords come back as 0 (probed on
-// gfx950: per-dword range check, 4-byte-aligned bases are fine; tools/probe_bufload.hip).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const int32_t *row, int32_t len)
-{
-    return __builtin_amdgcn_make_buffer_rsrc((void *)row, 0, len * 4, 0x00020000);
-}
+// Buffer resource over one adjacency row (eps_raw_rsrc: entries past the row's end read as 0)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const int32_t *row, int32_t len) { return eps_raw_rsrc(row, len * 4); }
 
 // Sum over the (few) lanes whose flag is set, in ascending lane order: deterministic, and cheaper than a
 // 6-step butterfly when 1-3 lanes hold a contribution (mean CN of a candidate pair is ~1.3).
@@ -57,10 +43,7 @@ __device__ __forceinline__ float lane_get(float x, int l)
 }
 __device__ __forceinline__ double lane_get(double x, int l)
 {
-    const long long b = __builtin_bit_cast(long long, x);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+    return __builtin_bit_cast(double, eps_bcast64(__builtin_bit_cast(int64_t, x), l));
 }
 template <typename T>
 __device__ __forceinline__ T sparse_lane_sum(uint64_t mask, T x)

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(PG_THREADS) void pair_scores_grouped_kernel(
             v4i ring0[PG_RING], ring1[PG_RING];
 #pragma unroll
             for (int r = 0; r < PG_RING; ++r) {
-                const __amdgpu_buffer_rsrc_t r0 = row_rsrc(col + bcast64(ub, r), __builtin_amdgcn_readlane(du, r));
+                const __amdgpu_buffer_rsrc_t r0 = row_rsrc(col + eps_bcast64(ub, r), __builtin_amdgcn_readlane(du, r));
                 ring0[r] = __builtin_amdgcn_raw_buffer_load_b128(r0, lane * 16, 0, 0);
                 ring1[r] = __builtin_amdgcn_raw_buffer_load_b128(r0, lane * 16 + 1024, 0, 0);
             }
@@ -239,13 +239,13 @@ __global__ __launch_bounds__(PG_THREADS) void pair_scores_grouped_kernel(
                 for (int r = 0; r < PG_RING; ++r) {
                     const int j = jb + r;
                     const int32_t dju = __builtin_amdgcn_readlane(du, j);   // 0 for lanes past the end of the chunk
-                    const int64_t bju = bcast64(ub, j);
+                    const int64_t bju = eps_bcast64(ub, j);
                     const __amdgpu_buffer_rsrc_t rj = row_rsrc(col + bju, dju);
                     const v4i cur0 = ring0[r], cur1 = ring1[r];
                     {
                         const int jn = (j + PG_RING) & 63;
                         const int32_t dn = (j + PG_RING) < 64 ? __builtin_amdgcn_readlane(du, jn) : 0;
-                        const __amdgpu_buffer_rsrc_t rn = row_rsrc(col + bcast64(ub, jn), dn);
+                        const __amdgpu_buffer_rsrc_t rn = row_rsrc(col + eps_bcast64(ub, jn), dn);
                         ring0[r] = __builtin_amdgcn_raw_buffer_load_b128(rn, lane * 16, 0, 0);
                         ring1[r] = __builtin_amdgcn_raw_buffer_load_b128(rn, lane * 16 + 1024, 0, 0);
                     }
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(PG_THREADS) void pair_scores_grouped_kernel(
                         if (djv != 0) {
                             float acc_cn = 0.0f;
                             WT acc_ws = 0;
-                            score_pair_inplace<HAS_VAL, HAS_W, WT>(col, val, node_w, bju, dju, bcast64(vb2, j), djv, lane,
+                            score_pair_inplace<HAS_VAL, HAS_W, WT>(col, val, node_w, bju, dju, eps_bcast64(vb2, j), djv, lane,
                                                                    cnt, acc_cn, acc_ws);
                             if (cnt != 0) {
                                 r_cn = HAS_VAL ? eps_wave_sum(acc_cn) : (float)cnt;

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pair_scores_kernel(
             const int32_t dju = __builtin_amdgcn_readlane(du_left, j);
             const int32_t djv = __builtin_amdgcn_readlane(dv_left, j);
             if (dju == 0 || djv == 0) continue;  // wave-uniform (also: lanes past the end of the list)
-            const int64_t bju = bcast64(ub, j), bjv = bcast64(vb, j);
+            const int64_t bju = eps_bcast64(ub, j), bjv = eps_bcast64(vb, j);
             const bool swapped = dju > djv;  // short row = v
             const int32_t slen = swapped ? djv : dju, llen = swapped ? dju : djv;
             const int64_t sbase = swapped ? bjv : bju, lbase = swapped ? bju : bjv;

@@ -8,7 +8,6 @@
 // multiples of 2^-40 below 2^12, so the float64 sum is exact whatever the order: (float)sum is eps_filter_scan's score, bit
 // for bit (adamic_utils.py:13-25 / train_and_eval.py:195-216 / models.py:536-542 with the engine's fixed-point definition).
 #include "eps_common.h"
-#include "scan_common.h"      // (sp_v4i)
 
 #define RS_THREADS 1024
 #define RS_CHUNK 256
@@ -39,7 +38,7 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
     constexpr int W = RS_THREADS / 64;
     const int words = (n_nodes < RS_BITS ? (n_nodes + 31) >> 5 : RS_BITS >> 5);
     // (one descriptor over all of col[]: 16-byte loads at 4-byte-aligned offsets, out-of-range lanes read zeros at a far offset)
-    const __amdgpu_buffer_rsrc_t col_rs = __builtin_amdgcn_make_buffer_rsrc((void *)col, 0, (int)(uint32_t)(rowptr[n_nodes] * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t col_rs = eps_raw_rsrc(col, (int)(uint32_t)(rowptr[n_nodes] * 4));
     for (int i = tid; i < words; i += RS_THREADS) bm[i] = 0u;
     const int64_t n_chunks = (n + RS_CHUNK - 1) / RS_CHUNK;
     // XCD-aware hand-out (r05).  The pairs come sorted by (block of 2^9 consecutive v, u, v): neighbouring chunks stream the rows of
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
                     // (16-byte loads, four entries a lane: a quarter of the vector-memory instructions of one-entry loads for the
                     //  same bytes -- the rows are what this kernel streams, 8.8 GB per step on the bench graph)
                     for (uint32_t off = 0; off < longest; off += 32 * RS_NB) {     // (uniform trip count over the wave)
-                        sp_v4i wv[RS_NB / 4];
+                        v4i wv[RS_NB / 4];
 #pragma unroll
                         for (int b = 0; b < RS_NB / 4; ++b) {
                             const uint32_t i = vb + off + (uint32_t)(b * 128 + 4 * hl);
@@ -259,11 +258,7 @@ __global__ __launch_bounds__(256) void rescore_weighted_kernel(const int64_t *__
         long long acc = 0ll;
         for (int64_t i = sb + lane; i < se; i += 64) {
             const int32_t w = col[i];
-            int64_t lo = lb, hi = le;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (col[mid] < w) lo = mid + 1; else hi = mid;
-            }
+            const int64_t lo = eps_lower_bound(col, lb, le, w);
             if (lo < le && col[lo] == w) {
                 const float term = (val[i] * val[lo]) * node_w[w];
                 acc += __double2ll_rn((double)term * (double)(1ll << 40));

@@ -57,11 +57,11 @@ __global__ __launch_bounds__(RBS_T) void rbs_cut_kernel(const float *__restrict_
     float cut = -__builtin_inff();
     int64_t n_sel = n_live;
     if (k2 != 0 && (uint64_t)n_live >= k2) {
-        const uint32_t ob = ts_ordered(floor_v), o = ts_ordered(s[k2 - 1]);
+        const uint32_t ob = eps_ordered_bits(floor_v), o = eps_ordered_bits(s[k2 - 1]);
         const uint32_t b = ts_bucket(o > ob ? o - ob : 0u);
         if (b != 0u) {                                        // (bucket 0 also holds what lies below the base: its lower edge is "anything")
             const uint64_t e = (uint64_t)ob + ts_bucket_floor(b);
-            cut = ts_unordered(e > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)e);
+            cut = eps_unordered_bits(e > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)e);
             n_sel = rbs_prefix_len(s, n_live, [=](float x) { return x >= cut; });
         }
     }

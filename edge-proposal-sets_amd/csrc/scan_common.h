@@ -1,7 +1,6 @@
 // What the one-pass scan's translation units share, each thing defined once: scan_pieces.hip (the piece kernel, its planner and
-// the launch), scan_tables.hip (the per-graph and per-weight-table builders), scan_heads.hip (skipped heads -- the head table, the
-// hub adjacency bitmaps, the completion of the walked sums) and rescore.hip (the exact re-scoring of the survivors: the vector
-// type only).  The layouts of the tables the builders write and the piece kernel reads (cuts, row records, plan records, the
+// the launch), scan_tables.hip (the per-graph and per-weight-table builders) and scan_heads.hip (skipped heads -- the head table,
+// the hub adjacency bitmaps, the completion of the walked sums).  The layouts of the tables the builders write and the piece kernel reads (cuts, row records, plan records, the
 // column pack) are told where sp_params names them, in scan_pieces.hip.
 #pragma once
 #include "eps_common.h"
@@ -10,21 +9,7 @@
 #define SP_FLAG 0x80000000u      // value word of a KNOWN EDGE's endpoint (put in before the walk): sums stay below 2^31, so the bit survives them
                                  // (not in sketch pieces: they put no flags in, their estimates may reach 2^32 - 1 and are compared unsigned)
 
-typedef int sp_v4i __attribute__((ext_vector_type(4)));      // (what a 16-byte raw buffer load returns)
-
 #if defined(__HIPCC__)
-// Inclusive prefix sum over the wave's 64 lanes in DPP steps (VALU rate, no LDS traffic): lane 63 holds the total.
-__device__ __forceinline__ int sp_wave_incl_scan(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);   // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);   // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
 // The bar in the table's domain.  filter_scan.hip keeps a candidate when its 2^-40 fixed-point sum a satisfies
 // float(a * 2^-40) > threshold, i.e. a >= thr_fix (monotone: found by bisection); a screening sum s >= a / 2^(40 - shift),
 // so s >= floor(thr_fix / 2^(40 - shift)) holds for every such candidate.  Any bar <= 0 (or -inf): every candidate (1).

@@ -103,9 +103,6 @@ struct sp_params {
                                 //        hubs-first labels); heads[v].y = the sum of their screening weights.  See eps_scan_heads.
 };
 
-__device__ __forceinline__ void sp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-typedef float sp_v4f __attribute__((ext_vector_type(4)));
 typedef short sp_v2s __attribute__((ext_vector_type(2)));
 
 // Hash of an id: Fibonacci hashing.  The table index is taken from the TOP of the 32-bit product, the probe step from the
@@ -119,8 +116,8 @@ __device__ __forceinline__ uint32_t sp_mix2(uint32_t x) { return x * 0x85EBCA6Bu
 typedef unsigned short sp_v2us __attribute__((ext_vector_type(2)));
 
 struct sp_unit {
-    sp_v4i u4;
-    sp_v4f a4;                  // weighted graphs: the entries' stored values
+    v4i u4;
+    v4f a4;                  // weighted graphs: the entries' stored values
     uint32_t fx;
     int nvalid;
 };
@@ -132,7 +129,7 @@ template <class Emit>
 __device__ __forceinline__ int sp_plan_column(const sp_params &p, int32_t v, int32_t dv, int lane, int32_t my_bound, uint32_t pwk,
                                               int32_t nbk, uint32_t direct_ids, Emit emit)
 {
-    const uint32_t ek = (uint32_t)sp_wave_incl_scan((int)pwk) - pwk;      // paths in the windows before k (lane 32: all)
+    const uint32_t ek = (uint32_t)eps_wave_incl_scan_dpp((int)pwk) - pwk;      // paths in the windows before k (lane 32: all)
     const bool pk_on = p.ssum != nullptr;      // (weighted graphs come without)
     // (what the column's walked rows can add up to: its row sum without the skipped head)
     const uint32_t sv = pk_on ? p.ssum[v] - (p.heads ? (p.heads[v].y < p.ssum[v] ? p.heads[v].y : p.ssum[v]) : 0u) : 0u;
@@ -269,9 +266,8 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
     int64_t *__restrict__ out_key = p.out->key;
     float *__restrict__ out_val = p.out->val;
     const uint32_t *__restrict__ rowptr_lo = (const uint32_t *)p.rowptr;     // nnz < 2^30: the low words suffice
-    const __amdgpu_buffer_rsrc_t col_rs = __builtin_amdgcn_make_buffer_rsrc((void *)p.col, 0, p.col_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t val_rs = __builtin_amdgcn_make_buffer_rsrc((void *)(HV ? (const void *)p.val : (const void *)p.col), 0,
-                                                                            p.col_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t col_rs = eps_raw_rsrc(p.col, p.col_bytes);
+    const __amdgpu_buffer_rsrc_t val_rs = eps_raw_rsrc(HV ? (const void *)p.val : (const void *)p.col, p.col_bytes);
     const uint32_t thr32 = sp_bar_units(p.out->threshold, p.shift, HV);      // (stored values: rounded up -- every survivor's score exceeds the bar)
     const uint32_t direct_ids = 2u * (uint32_t)slots;
     // Survivor slots are reserved in chunks (one global atomic each).  Without a bar every candidate of a piece survives: the
@@ -304,7 +300,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
     auto first_of = [&](unsigned int tk) { return tk < batch_from ? tk : batch_from + (tk - batch_from) * SP_BATCH; };
     unsigned int t = blockIdx.x < batch_from ? blockIdx.x : first_of(blockIdx.x);
     unsigned int t_end = t + (blockIdx.x < batch_from ? 1u : SP_BATCH);
-    sp_barrier();
+    eps_lds_barrier();
 
     while (t < ncol) {
         const bool last_of_ticket = t + 1u >= t_end || t + 1u >= ncol;
@@ -409,7 +405,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                 }
                 if (tid == 0) s_np = np;
             }
-            sp_barrier();
+            eps_lds_barrier();
             const int np = s_np;
             // A column of one round keeps its rows in registers, and its pieces are consecutive runs of windows: a row's segment
             // starts where its segment in the previous piece ended (runs that were skipped hold no entry of any row), and the
@@ -577,7 +573,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                         const int units = (int)((len + 3u) >> 2);
                         const int flag = units > 0 ? 1 : 0;
                         // (one wave scan for both: a row has < 2^14 units, a wave < 2^20; the non-empty flags count in bits 24 up)
-                        const int incl_c = sp_wave_incl_scan(units | (flag << 24));
+                        const int incl_c = eps_wave_incl_scan_dpp(units | (flag << 24));
                         const int incl = incl_c & 0xFFFFFF, incl_f = (int)((uint32_t)incl_c >> 24);
                         // Each wave takes its range of unit numbers AND of dense row indices with one 64-bit LDS add: whatever
                         // order the waves arrive in, both ranges are handed out in that same order -- a row that starts at a
@@ -592,7 +588,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             r_desc[d] = make_uint4(base + a, len, quant ? (fx + ((1u << pk_d) - 1u)) >> pk_d : fx, a_u);
                             if (a_u < (uint32_t)SP_UBITS) atomicOr(&ubits[a_u >> 5], 1u << (a_u & 31u));      // (the first range's start bits)
                         }
-                        sp_barrier();
+                        eps_lds_barrier();
                         if (s_fill_hi > s_fill_lo) {                     // (uniform; rare: one reservation in ~a thousand pieces)
                             const uint32_t f0 = s_fill_lo, f1 = s_fill_hi;
                             for (uint32_t i = f0 + (uint32_t)tid; i < f1; i += T) {
@@ -606,20 +602,20 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             if (ulo > 0u) {
                                 for (int i = tid; i < SP_UBITS / 32; i += T) ubits[i] = 0u;
                                 if (tid == 0) s_rbase = 0;
-                                sp_barrier();
+                                eps_lds_barrier();
                                 const unsigned long long before = __ballot(flag && a_u + (uint32_t)units <= ulo);
                                 if (lane == 0 && before) atomicAdd(&s_rbase, __popcll(before));
                                 if (flag && a_u + (uint32_t)units > ulo && a_u < uhi) {
                                     const uint32_t pos = (a_u > ulo ? a_u : ulo) - ulo;
                                     atomicOr(&ubits[pos >> 5], 1u << (pos & 31));
                                 }
-                                sp_barrier();
+                                eps_lds_barrier();
                             }
                             const int rbase = ulo > 0u ? s_rbase : 0;
                             {   // rank of every word's first bit: every wave computes all of them (identical values: no barrier)
                                 const uint4 b4 = *(const uint4 *)(ubits + 4 * lane);
                                 const int c0 = __popc(b4.x), c1 = c0 + __popc(b4.y), c2 = c1 + __popc(b4.z), c3 = c2 + __popc(b4.w);
-                                const int ex = sp_wave_incl_scan(c3) - c3;
+                                const int ex = eps_wave_incl_scan_dpp(c3) - c3;
                                 uint2 pk;
                                 pk.x = (uint32_t)ex | ((uint32_t)(ex + c0) << 16);
                                 pk.y = (uint32_t)(ex + c1) | ((uint32_t)(ex + c2) << 16);
@@ -655,7 +651,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 f[q].nvalid = left < 0 ? 0 : (left > 4 ? 4 : left);
                                 const uint32_t at = in ? rs + (uint32_t)off : (p.col_bytes >> 2);
                                 f[q].u4 = __builtin_amdgcn_raw_buffer_load_b128(col_rs, (int)(at * 4u), 0, 0);
-                                if (HV) f[q].a4 = __builtin_bit_cast(sp_v4f, __builtin_amdgcn_raw_buffer_load_b128(val_rs, (int)(at * 4u), 0, 0));
+                                if (HV) f[q].a4 = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(val_rs, (int)(at * 4u), 0, 0));
                             }
                         };
                         auto path_fx = [&](const sp_unit &f, int e) -> uint32_t {
@@ -855,7 +851,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             // the second look (one range: a piece of <= packed_paths paths has fewer than SP_UBITS units)
                             if (tid == 0 && !sketch_seen) atomicOr(p.status, 16u);      // (informational: sketch pieces ran in this launch)
                             sketch_seen = true;
-                            sp_barrier();
+                            eps_lds_barrier();
                             const uint32_t half = 1u << (bits - 1);
                             // An id's estimate is at most its slot in the FIRST half table: when no slot there reaches the bar -- the
                             // usual case in the tail: survivors are a handful per thousand pieces -- nothing needs a second look.
@@ -869,7 +865,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 }
                                 if (__ballot(mx >= thr_v) && lane == 0) s_hot = 1u;
                             }
-                            sp_barrier();
+                            eps_lds_barrier();
                             if (s_hot) {
                             const int n_iter = (int)(uhi - ulo + T - 1) / T;
                             auto report = [&](uint32_t u, uint32_t est) {
@@ -918,9 +914,9 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             }
                             }
                         }
-                            if (uhi < (uint32_t)total) sp_barrier();       // (the next range rewrites the start bits)
+                            if (uhi < (uint32_t)total) eps_lds_barrier();       // (the next range rewrites the start bits)
                         }
-                        sp_barrier();        // the next round / the scan follows: descriptors and table updates are complete
+                        eps_lds_barrier();        // the next round / the scan follows: descriptors and table updates are complete
                         // (leave the start bits and the hand-out counter clean for the next describe; a barrier separates them from
                         //  it: the sweep's own, or -- columns of several rounds -- one more)
                         for (int i = tid; i < SP_UBITS / 32; i += T) ubits[i] = 0u;
@@ -928,7 +924,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             s_alloc = 0ull;
                             s_fill_hi = 0u;
                         }
-                        if (r + 1 < rounds) sp_barrier();
+                        if (r + 1 < rounds) eps_lds_barrier();
                     }
                     // ---- scan the table: count the candidates, report the survivors, leave it clean --------------------------
                     // (the sweeps read in batches of SP_SB uint4 per thread before they look at any of them: one LDS round trip per
@@ -1067,22 +1063,22 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                         }
                     }
                     {
-                        const uint32_t upto = (uint32_t)sp_wave_incl_scan((int)new_keys);      // (lane 63: the wave's count)
+                        const uint32_t upto = (uint32_t)eps_wave_incl_scan_dpp((int)new_keys);      // (lane 63: the wave's count)
                         if (lane == 63 && upto) atomicAdd(&s_ncand, (unsigned long long)upto);
                     }
-                    sp_barrier();
+                    eps_lds_barrier();
                 }
             }
         }
         if (!last_of_ticket) {
             ++t;
-            sp_barrier();                    // (a column without pieces has no barrier of its own: s_np and the piece arrays change hands here)
+            eps_lds_barrier();                    // (a column without pieces has no barrier of its own: s_np and the piece arrays change hands here)
             continue;
         }
         if (tid == 0) s_ticket = t_next;
-        sp_barrier();
+        eps_lds_barrier();
         const unsigned int tk = s_ticket;
-        sp_barrier();
+        eps_lds_barrier();
         t = first_of(tk);
         t_end = t + (tk < batch_from ? 1u : SP_BATCH);
     }

@@ -7,7 +7,7 @@
 
 __device__ __forceinline__ uint32_t sp_wave_sum(uint32_t x)
 {
-    return (uint32_t)__builtin_amdgcn_readlane(sp_wave_incl_scan((int)x), 63);
+    return (uint32_t)__builtin_amdgcn_readlane(eps_wave_incl_scan_dpp((int)x), 63);
 }
 
 extern "C" int32_t eps_scan_windows(void) { return SP_M; }
@@ -58,13 +58,8 @@ __global__ void sp_cuts_kernel(const int64_t *__restrict__ rowptr, const int32_t
         const int64_t w = i / SP_M;
         const int k = (int)(i % SP_M);
         const int32_t bound = bounds[k + 1];
-        int64_t lo = rowptr[w], hi = rowptr[w + 1];
-        const int64_t wb = lo;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (col[mid] < bound) lo = mid + 1; else hi = mid;
-        }
-        cuts[i] = (uint16_t)(lo - wb);
+        const int64_t wb = rowptr[w];
+        cuts[i] = (uint16_t)(eps_lower_bound(col, wb, rowptr[w + 1], bound) - wb);
     }
 }
 

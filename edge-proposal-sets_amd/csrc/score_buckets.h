@@ -2,22 +2,11 @@
 // rows_by_score.hip: the cut read off a sorted list).  A bucket is a minifloat of a score's distance to a base score, in steps of the
 // ordered bit pattern: 2^-TS_MB of that distance per bucket.  One definition: a cut derived in two places must be the same bits.
 #pragma once
-#include <stdint.h>
+#include "eps_common.h"
 
 #define TS_MB 8                                   // mantissa bits of the bucket minifloat
 #define TS_BINS ((32 - TS_MB + 1) << TS_MB)       // 6400
 
-__device__ __forceinline__ uint32_t ts_ordered(float f)
-{
-    f = f + 0.0f;
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ts_unordered(uint32_t o)
-{
-    const uint32_t b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __builtin_bit_cast(float, b);
-}
 // bucket of a distance d >= 0 (in steps of the ordered bit pattern): d itself below 2^MB, else exponent | top MB mantissa bits
 __device__ __forceinline__ uint32_t ts_bucket(uint32_t d)
 {

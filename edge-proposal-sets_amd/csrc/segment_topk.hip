@@ -2,7 +2,7 @@
 //
 // The list kernels deliver a block's candidates column-major -- column v, u ascending, one score each -- so "node v's k best
 // proposals" (filter.py --keep_per_node k) is a top-k per SEGMENT of the block's score array.  The order is the declared one:
-// ordered_bits(score) descending (csrc/topk_keys.hip: -0.0 ties +0.0, NaN where its bit pattern puts it), then position ascending.
+// eps_ordered_bits(score) descending (csrc/eps_common.h: -0.0 ties +0.0, NaN where its bit pattern puts it), then position ascending.
 //
 // Selection by threshold, not by heap, so no resource depends on k:
 //   1. the k-th largest key T of the segment by radix select (four rounds of a 256-bin LDS histogram over the keys that still
@@ -31,13 +31,6 @@
 #define SEG_WAVE_U (SEG_WAVE_MAX / 64)
 #define SEG_LDS_MAX 8192         // one workgroup, keys in LDS (32 KiB: four workgroups per CU)
 #define SEG_CHUNK (SEG_THREADS * 4)   // entries per compaction step: four consecutive ones per thread
-
-__device__ __forceinline__ uint32_t seg_ordered_bits(float f)     // == ordered_bits of csrc/topk_keys.hip
-{
-    f = f + 0.0f;  // -0.0 -> +0.0: the two zeros tie
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 struct seg_range {
     int64_t start, len, out, room;
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_wave_kernel(const int64_t *__
             for (int j = 0; j < SEG_WAVE_U; ++j) {
                 const int p = j * 64 + lane;
                 live[j] = p < len;
-                key[j] = live[j] ? seg_ordered_bits(score[r.start + p]) : 0u;
+                key[j] = live[j] ? eps_ordered_bits(score[r.start + p]) : 0u;
             }
             // the k-th largest key, bit by bit from the top: how many live keys carry the prefix found so far with this bit set
             uint32_t prefix = 0u, t = k;
@@ -207,9 +200,9 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_group_kernel(const int64_t *_
                         const int64_t p = base + j * SEG_THREADS + tid;
                         live[j] = p < len;
                         if (STREAM) {
-                            key[j] = live[j] ? seg_ordered_bits(x[p]) : 0u;
+                            key[j] = live[j] ? eps_ordered_bits(x[p]) : 0u;
                         } else if (round == 0) {
-                            key[j] = live[j] ? seg_ordered_bits(x[p]) : 0u;
+                            key[j] = live[j] ? eps_ordered_bits(x[p]) : 0u;
                             if (live[j]) s_key[p] = key[j];
                         } else {
                             key[j] = live[j] ? s_key[p] : 0u;
@@ -256,14 +249,14 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_group_kernel(const int64_t *_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t p = 4 * tid + j;
-                cur[j] = p < len ? (STREAM ? seg_ordered_bits(x[p]) : s_key[p]) : 0u;
+                cur[j] = p < len ? (STREAM ? eps_ordered_bits(x[p]) : s_key[p]) : 0u;
             }
             for (int64_t base = 0; base < len; base += SEG_CHUNK) {
                 if (STREAM) {                                      // (the next chunk's loads are under way while this one is placed)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int64_t p = base + SEG_CHUNK + 4 * tid + j;
-                        nxt[j] = p < len ? seg_ordered_bits(x[p]) : 0u;
+                        nxt[j] = p < len ? eps_ordered_bits(x[p]) : 0u;
                     }
                 }
                 uint32_t own = 0u;

@@ -15,28 +15,6 @@
 
 #define SP_FLIGHT 32   // neighbour rows in flight per wave (2: 7.3 ms, 4: 6.6, 8: 6.5, 16: 6.3, 32: 6.0 per ppa-like layer)
 
-template <int VEC>
-struct VecT;
-template <>
-struct VecT<4> {
-    using type = float4;
-};
-template <>
-struct VecT<1> {
-    using type = float;
-};
-
-__device__ __forceinline__ void fma_vec(float4 &a, float s, const float4 &x)
-{
-    a.x = fmaf(s, x.x, a.x);
-    a.y = fmaf(s, x.y, a.y);
-    a.z = fmaf(s, x.z, a.z);
-    a.w = fmaf(s, x.w, a.w);
-}
-__device__ __forceinline__ void fma_vec(float &a, float s, const float &x) { a = fmaf(s, x, a); }
-__device__ __forceinline__ float4 vzero(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float vzero(float) { return 0.f; }
-
 template <int VEC, bool HAS_VAL>
 __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict__ rowptr,
                                                        const int32_t *__restrict__ col,
@@ -45,7 +23,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict
                                                        const float *__restrict__ bias, int relu, int mean,
                                                        float *__restrict__ y, int64_t ldy)
 {
-    using V = typename VecT<VEC>::type;
+    using V = typename eps_vec<VEC>::type;
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -56,7 +34,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict
         for (int32_t c0 = 0; c0 < f; c0 += 64 * VEC) {
             const int32_t c = c0 + lane * VEC;
             const bool act = c < f;
-            V acc = vzero(V());
+            V acc = eps_zero(V());
             for (int64_t k0 = b; k0 < e; k0 += 64) {
                 const int nk = (e - k0) < 64 ? (int)(e - k0) : 64;
                 const int my_col = lane < nk ? col[k0 + lane] : 0;
@@ -73,7 +51,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict
                     for (int q = 0; q < SP_FLIGHT; ++q) cj[q] = __builtin_amdgcn_readlane(my_col, (j + q) & 63);
 #pragma unroll
                     for (int q = 0; q < SP_FLIGHT; ++q) {
-                        xv[q] = vzero(V());
+                        xv[q] = eps_zero(V());
                         if ((!G || j + q < nk) && act) xv[q] = *reinterpret_cast<const V *>(x + (int64_t)cj[q] * ldx + c);
                     }
 #pragma unroll
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict
                     }
 #pragma unroll
                     for (int q = 0; q < SP_FLIGHT; ++q)
-                        if (!G || j + q < nk) fma_vec(acc, vj[q], xv[q]);
+                        if (!G || j + q < nk) eps_fma(acc, vj[q], xv[q]);
                 };
                 int j = 0;
                 for (; j + SP_FLIGHT <= nk; j += SP_FLIGHT) group(j, std::false_type{});

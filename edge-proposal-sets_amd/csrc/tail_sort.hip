@@ -68,7 +68,7 @@ __global__ __launch_bounds__(TS_T) void ts_hist_kernel(const int64_t *__restrict
     }
     for (int i = tid; i < TS_BINS; i += TS_T) h[i] = 0u;
     __syncthreads();
-    const uint32_t ob = ts_ordered(*base);
+    const uint32_t ob = eps_ordered_bits(*base);
     const float floor_v = above ? *above : -__builtin_inff();
     const int64_t stride = (int64_t)gridDim.x * TS_T;
     // (whole waves run the loop: the ballots need every lane)
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(TS_T) void ts_hist_kernel(const int64_t *__restrict
         const float x = i < n ? vals[i] : -__builtin_inff();
         bool live = i < n && x > floor_v && x > -__builtin_inff();
         if (live && keys) live = keys[i] >= 0;
-        const uint32_t o = ts_ordered(x);
+        const uint32_t o = eps_ordered_bits(x);
         const uint32_t bin = live ? ts_bucket(o > ob ? o - ob : 0u) : 0u;
         const unsigned long long m = __ballot(live);
         if (m) {                                               // (a wave whose live lanes agree adds their count once)
@@ -208,12 +208,12 @@ __global__ __launch_bounds__(TS_T) void ts_deal_plan_kernel(const uint32_t *__re
         for (int q = 1; q < world; ++q)
             if (s_edge[q] > s_edge[q - 1]) s_edge[q] = s_edge[q - 1];
         s_edge[world] = lowest;
-        const uint32_t ob = ts_ordered(*base);
+        const uint32_t ob = eps_ordered_bits(*base);
         auto edge_value = [&](uint32_t b) -> float {
             if (b == 0u) return -__builtin_inff();
             if (b >= (uint32_t)TS_BINS) return __builtin_inff();
             const uint64_t o = (uint64_t)ob + ts_bucket_floor(b);
-            return ts_unordered(o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o);
+            return eps_unordered_bits(o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o);
         };
         *cut = none ? -__builtin_inff() : edge_value(bstar);
         for (int q = 1; q < world; ++q) splitters[q - 1] = edge_value(s_edge[q]);
@@ -309,18 +309,18 @@ __global__ __launch_bounds__(TS_T) void ts_pick_compact_kernel(const int64_t *__
     __syncthreads();
     const uint32_t bstar = s_bstar;
     const bool none = bstar == 0xFFFFFFFFu;                  // fewer than k values (or k == 0): -inf, everything live is kept
-    const uint32_t ob = ts_ordered(*base);
+    const uint32_t ob = eps_ordered_bits(*base);
     float kth = -__builtin_inff();
     if (!none) {
         const uint64_t o = (uint64_t)ob + ts_bucket_floor(bstar);
         // (bucket 0 also holds what lies below the base: its lower edge is "anything")
-        kth = bstar == 0u ? -__builtin_inff() : ts_unordered(o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o);
+        kth = bstar == 0u ? -__builtin_inff() : eps_unordered_bits(o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o);
     }
     float thr = kth;
     if (kth > -__builtin_inff()) {
         if (mode == 1) {
-            const uint32_t o = ts_ordered(kth);
-            thr = ts_unordered(o == 0x80000000u ? o - 2u : o - 1u);
+            const uint32_t o = eps_ordered_bits(kth);
+            thr = eps_unordered_bits(o == 0x80000000u ? o - 2u : o - 1u);
         } else if (mode == 2) {
             const float low = kth - pa, rel = kth * pb;
             thr = (low > rel ? low : rel) - __builtin_fabsf(kth) * pc;
@@ -457,18 +457,6 @@ struct ts_sort_params {
     ts_sort_state *st;
 };
 
-__device__ __forceinline__ void ts_grid_sync(uint32_t *arrive, uint32_t target)
-{
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(arrive, 1u);
-        while (__atomic_load_n(arrive, __ATOMIC_RELAXED) < target) __builtin_amdgcn_s_sleep(1);
-        __threadfence();
-    }
-    __syncthreads();
-}
-
 // lanes of the wave whose (live) digit equals this lane's
 __device__ __forceinline__ unsigned long long ts_match8(uint32_t digit, bool live)
 {
@@ -540,7 +528,7 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
                 // row of proposal (u, v) sorts by (v, u): the direct row has v = large, the mirrored one v = small
                 const uint64_t vv = i < n_in ? large : small, uu = i < n_in ? small : large;
                 key = (vv << p.id_bits) | uu;
-                val = ~ts_ordered(p.in_vals[j]);                          // ascending in this = descending in the score
+                val = ~eps_ordered_bits(p.in_vals[j]);                          // ascending in this = descending in the score
                 p.buf_k[0][i] = key;
                 p.buf_v[0][i] = val;
             }
@@ -560,7 +548,7 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
     bool blocked = false;
     bool decided = false;
     epoch += 1;
-    ts_grid_sync(&st->arrive, epoch * G);
+    eps_grid_sync<1>(&st->arrive, epoch * G);
     for (int i = tid; i < p.n_pass * 256; i += TS_T) (&s_tot[0][0])[i] = __atomic_load_n(&(&st->totals[0][0])[i], __ATOMIC_RELAXED);
     __syncthreads();
 
@@ -578,7 +566,7 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
             for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
             if (lane == 0 && c) atomicAdd(&st->runs, (unsigned long long)c);
             epoch += 1;
-            ts_grid_sync(&st->arrive, epoch * G);
+            eps_grid_sync<1>(&st->arrive, epoch * G);
             blocked = __atomic_load_n(&st->runs, __ATOMIC_RELAXED) * 64ull <= (unsigned long long)n;
             decided = true;
         }
@@ -690,7 +678,7 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
         }
         cur ^= 1;
         epoch += 1;
-        ts_grid_sync(&st->arrive, epoch * G);
+        eps_grid_sync<1>(&st->arrive, epoch * G);
     }
 
     // ---- the output transform -------------------------------------------------------------------------------------------------
@@ -706,7 +694,7 @@ __global__ __launch_bounds__(TS_T) void ts_sort_kernel(ts_sort_params p)
                 const uint64_t k = src_k[i];
                 p.out_pairs[i] = (int64_t)(k & idm);                            // u
                 p.out_pairs[p.out_ld + i] = (int64_t)(k >> p.id_bits);          // v
-                p.out_scores[i] = ts_unordered(~src_v[i]);
+                p.out_scores[i] = eps_unordered_bits(~src_v[i]);
             }
             if (b == 0 && tid == 0 && p.n_rows_out) *p.n_rows_out = take;
         }

@@ -4,23 +4,11 @@
 // rows rank.py ever consumes (rank.py:294).  The reference's torch.sort is unstable on ties
 // (SURVEY 8 trap 9), so the order is DECLARED: score descending, then candidate id ascending
 // (== torch.sort(descending=True, stable=True) over the reference's candidate order).
-// key (int64, SIGNED order) = (ordered_bits(score) ^ 0x80000000) << 32 | (0xFFFFFFFF - id); a plain descending sort of the keys
+// key (int64, SIGNED order) = (eps_ordered_bits(score) ^ 0x80000000) << 32 | (0xFFFFFFFF - id); a plain descending sort of the keys
 // (any algorithm, any sharding) then yields exactly that order, which is what makes the
 // multi-GPU top-K merge shard-count invariant.
 #include "eps_common.h"
 #include <stdlib.h>
-
-__device__ __forceinline__ uint32_t ordered_bits(float f)
-{
-    f = f + 0.0f;  // -0.0 -> +0.0 so that the two zeros tie, as they do in torch.sort
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unordered_bits(uint32_t o)
-{
-    const uint32_t b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    return __builtin_bit_cast(float, b);
-}
 
 __global__ void pack_keys_kernel(const float *__restrict__ score, const int64_t *__restrict__ id, int64_t id_base,
                                  int64_t n, int64_t *__restrict__ keys)
@@ -28,7 +16,7 @@ __global__ void pack_keys_kernel(const float *__restrict__ score, const int64_t 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t gid = (uint64_t)(id ? id[i] : id_base + i);
-        keys[i] = (int64_t)(((uint64_t)(ordered_bits(score[i]) ^ 0x80000000u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)gid));
+        keys[i] = (int64_t)(((uint64_t)(eps_ordered_bits(score[i]) ^ 0x80000000u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)gid));
     }
 }
 
@@ -38,7 +26,7 @@ __global__ void unpack_keys_kernel(const int64_t *__restrict__ keys, int64_t n, 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint64_t k = (uint64_t)keys[i];
-        if (score) score[i] = unordered_bits((uint32_t)(k >> 32) ^ 0x80000000u);
+        if (score) score[i] = eps_unordered_bits((uint32_t)(k >> 32) ^ 0x80000000u);
         if (id) id[i] = (int64_t)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFu));
     }
 }
@@ -79,7 +67,7 @@ extern "C" int eps_unpack_keys(const int64_t *keys, int64_t n, float *score, int
 // the values that still match the prefix found so far, then the bin that holds the k-th largest.  4 reads of the array
 // instead of a sort; everything stays on the device (state: prefix, remaining k).
 struct kth_state {
-    uint32_t prefix, mask;     // bits decided so far (in ordered_bits space) and which bits those are
+    uint32_t prefix, mask;     // bits decided so far (in eps_ordered_bits space) and which bits those are
     uint64_t k;                // rank (1-based, from the top) still to find inside the matching values
     uint32_t hist[256];
 };
@@ -96,7 +84,7 @@ __global__ void kth_hist_kernel(const float *__restrict__ x, int64_t n, kth_stat
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t n_up = (n + 63) & ~63ll;                    // (whole waves run the loop: the ballots below need every lane)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_up; i += stride) {
-        const uint32_t o = i < n ? ordered_bits(x[i]) : 0u;
+        const uint32_t o = i < n ? eps_ordered_bits(x[i]) : 0u;
         // (-inf is "no value": an untouched survivor slot.  Left out of the histogram, a list of 2^32 slots times any number of
         //  ranks cannot wrap the 32-bit bins, and "fewer than k values" still answers -inf -- which is what counting them gave)
         const bool live = i < n && o != 0x007FFFFFu && (o & mask) == prefix;
@@ -142,7 +130,7 @@ __global__ void kth_pick_kernel(kth_state *__restrict__ st, int shift, float *__
     if (mask != 0xFFFFFFFFu) {
         if (shift == 24 && (k == 0 || k > total)) {
             if (lane == 0) {
-                st->prefix = ordered_bits(-__builtin_inff());
+                st->prefix = eps_ordered_bits(-__builtin_inff());
                 st->mask = 0xFFFFFFFFu;
             }
         } else {
@@ -162,11 +150,11 @@ __global__ void kth_pick_kernel(kth_state *__restrict__ st, int shift, float *__
                 st->k = kk;
                 st->prefix = prefix | ((uint32_t)b << shift);
                 st->mask = mask | (255u << shift);
-                if (shift == 0 && out) *out = unordered_bits(prefix | (uint32_t)b);
+                if (shift == 0 && out) *out = eps_unordered_bits(prefix | (uint32_t)b);
             }
         }
     }
-    if (mask == 0xFFFFFFFFu && shift == 0 && out && lane == 0) *out = unordered_bits(prefix);
+    if (mask == 0xFFFFFFFFu && shift == 0 && out && lane == 0) *out = eps_unordered_bits(prefix);
 }
 
 extern "C" int64_t eps_kth_largest_workspace_bytes(void) { return (int64_t)sizeof(kth_state); }
@@ -259,18 +247,6 @@ struct fsel_state {
     unsigned long long n_out;
 };
 
-__device__ __forceinline__ void fsel_grid_sync(uint32_t *arrived, uint32_t target)
-{
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicAdd(arrived, 1u);
-        while (__atomic_load_n(arrived, __ATOMIC_RELAXED) < target) __builtin_amdgcn_s_sleep(2);
-        __threadfence();
-    }
-    __syncthreads();
-}
-
 #define FSEL_T 1024
 #define FSEL_U 8        // independent loads a thread has in flight per trip
 
@@ -309,7 +285,7 @@ __global__ __launch_bounds__(FSEL_T) void fsel_kernel(const int64_t *__restrict_
             }
 #pragma unroll
             for (int j = 0; j < FSEL_U; ++j) {
-                const uint32_t o = ordered_bits(x[j]);
+                const uint32_t o = eps_ordered_bits(x[j]);
                 const bool live = o != 0x007FFFFFu && (o & mask) == prefix;
                 const uint32_t bin = (o >> shift) & 255u;
                 const unsigned long long m = __ballot(live);
@@ -325,7 +301,7 @@ __global__ __launch_bounds__(FSEL_T) void fsel_kernel(const int64_t *__restrict_
         }
         __syncthreads();
         if (tid < 256 && h[tid]) atomicAdd(&st->hist[r][tid], h[tid]);
-        fsel_grid_sync(&st->arrived, (uint32_t)(r + 1) * gridDim.x);
+        eps_grid_sync<2>(&st->arrived, (uint32_t)(r + 1) * gridDim.x);
         if (tid < 64) {            // wave 0: lane l owns bins 255 - 4 l .. 252 - 4 l (from the top)
             uint32_t c[4];
 #pragma unroll
@@ -366,12 +342,12 @@ __global__ __launch_bounds__(FSEL_T) void fsel_kernel(const int64_t *__restrict_
         kk = s_k;
         __syncthreads();
     }
-    const float kth = none ? -__builtin_inff() : unordered_bits(prefix);
+    const float kth = none ? -__builtin_inff() : eps_unordered_bits(prefix);
     float thr = kth;
     if (!none && mode == 1) {
         // the largest float below kth (kth is finite here): one step down in the ordered bit pattern
-        const uint32_t ob = ordered_bits(kth);
-        thr = unordered_bits(ob == 0x80000000u ? ob - 2u : ob - 1u);       // (below +0.0 comes -0.0 == 0: one more step)
+        const uint32_t ob = eps_ordered_bits(kth);
+        thr = eps_unordered_bits(ob == 0x80000000u ? ob - 2u : ob - 1u);       // (below +0.0 comes -0.0 == 0: one more step)
     } else if (!none && mode == 2) {
         const float low = kth - pa, rel = kth * pb;
         thr = (low > rel ? low : rel) - __builtin_fabsf(kth) * pc;

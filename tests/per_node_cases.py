@@ -7,7 +7,7 @@ import torch
 def segment_topk_ref(colptr, score, k, counts=None):
     """Positions (int64, ascending within each segment, segments in order) of the k best entries of every segment: per segment
     ``np.argsort(-score, kind="stable")[:k]``, sorted ascending, offset by the segment's start.  (-score: -0.0 and +0.0 compare
-    equal in the sort, as the two zeros tie under ordered_bits; no NaN in the cases.)"""
+    equal in the sort, as the two zeros tie under eps_ordered_bits; no NaN in the cases.)"""
     colptr, score = np.asarray(colptr, dtype=np.int64), np.asarray(score, dtype=np.float32)
     out = []
     for s in range(len(colptr) - 1):

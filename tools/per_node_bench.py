@@ -53,7 +53,7 @@ def tensor_op_cut(colptr, score, k):
     import torch
     n = score.numel()
     seg = torch.searchsorted(colptr[1:].contiguous(), torch.arange(n, device=score.device), right=True)
-    by_score = torch.sort(score + 0.0, descending=True, stable=True).indices       # (+ 0.0: the two zeros tie, as under ordered_bits)
+    by_score = torch.sort(score + 0.0, descending=True, stable=True).indices       # (+ 0.0: the two zeros tie, as under eps_ordered_bits)
     by_seg = torch.sort(seg[by_score], stable=True)
     pos = by_score[by_seg.indices]                                                 # segment by segment, each in the declared order
     rank = torch.arange(n, device=score.device) - colptr[by_seg.values]
