@@ -14,12 +14,60 @@
 #define RS_BITS (1 << 20)       // ids per bitmap window: 128 KiB of LDS
 #define RS_SHORT 512            // rows up to this long go through rescore_short_kernel
 #define RS_GROUP 128            // consecutive 256-pair chunks that go to the same XCD (32 k pairs: most of a block of 2^9 v)
-#define RS_GB 4                 // weight gathers of a trip issued together (r06: 16 x 64-bit partial sums in flight were 32 of the kernel's 94 VGPRs)
 #define RS_MINW 8               // waves per SIMD the kernel is compiled for: 8 = two 1024-thread workgroups per CU (<= 64 VGPRs)
-#define RS_NB 8                 // entries of N(v) a lane has in flight per trip: a trip is three dependent latencies (row, bitmap,
-                                // weights) and the survivors' rows are long (~1100 entries on the ppa-like graph: 2.2 G entries to stream
-                                // for 2 M pairs -- 4 / 8 / 12 / 16 in flight: 6.4 / 5.5 / 5.4 / 5.1 ms for all 4.85 M pairs)
+#define RS_NB 8                 // entries of N(v) a lane takes per trip: two 16-byte row loads issued together, then eight bitmap
+                                // words read together (the survivors' rows are long, ~1100 entries on the ppa-like graph: 2.3 G
+                                // entries to stream for 2 M pairs)
 
+// One trip of a lane: the eight entries of its two row loads against the bitmap of N(u), the weights of the hits summed.
+//  * The eight bitmap words are read unconditionally, all before the first wait: an entry beyond the row's end or outside the id
+//    window reads some valid word and its predicate drops the bit.  (The empty asm keeps the word index and the scaled add of the
+//    LDS address apart: shift + v_lshl_add, where the compiler otherwise makes shift, mask and add of them.)
+//  * A weight is loaded only by the lanes that hit, each entry under its own exec mask, and nothing waits before the last of the
+//    eight is issued: the adds come at the end.  The straight-line form -- every lane loads, a lane without a hit from an offset
+//    beyond the descriptor -- measured 340 us SLOWER per call on the bench graph (1645 against 1305 us; NOTES, "Re-scoring
+//    trips"): it seems a buffer load whose lanes are all out of range still costs its slot in the vector-memory pipeline, and
+//    most of a trip's entries do not hit.
+//  * rem = the entries the row has left from the lane's first one.  A lane beyond the end got zeros from the col descriptor,
+//    i.e. id 0 -- the heaviest hub, which IS in most N(u) -- so rem stays in the hit.
+//  * fix_rs: a descriptor over the weights of the id window, so a hit's byte offset is x * 8 < 2^23 whatever n_nodes is.
+// WIN = the id space is wider than one window (otherwise x = w, and the window subtraction, clamp and test are dead).
+template <bool WIN>
+static __device__ __forceinline__ long long rs_trip(const uint32_t *bm, __amdgpu_buffer_rsrc_t fix_rs, int32_t wlo, v4i w0, v4i w1,
+                                                    int rem)
+{
+    uint32_t x[RS_NB], word[RS_NB];
+#pragma unroll
+    for (int b = 0; b < RS_NB; ++b) {
+        const int32_t w = b < 4 ? w0[b & 3] : w1[b & 3];
+        x[b] = WIN ? (uint32_t)(w - wlo) : (uint32_t)w;
+        const uint32_t xa = WIN ? (x[b] < (uint32_t)RS_BITS ? x[b] : (uint32_t)RS_BITS - 1u) : x[b];
+        uint32_t wi = xa >> 5;
+        asm("" : "+v"(wi));                // (see above: not volatile, it only pins the value)
+        word[b] = bm[wi];
+    }
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    v2i add[RS_NB];
+#pragma unroll
+    for (int b = 0; b < RS_NB; ++b) {
+        bool hit = (((word[b] >> (x[b] & 31u)) & 1u) != 0u) & (rem > (b >> 2) * 128 + (b & 3));
+        if (WIN) hit &= x[b] < (uint32_t)RS_BITS;
+        add[b] = v2i{0, 0};
+        if (hit) add[b] = __builtin_amdgcn_raw_buffer_load_b64(fix_rs, (int)(x[b] * 8u), 0, 0);
+    }
+    long long acc = 0ll;
+#pragma unroll
+    for (int b = 0; b < RS_NB; ++b) acc += (long long)(((unsigned long long)(uint32_t)add[b][1] << 32) | (uint32_t)add[b][0]);
+    return acc;
+}
+
+// A lane's 16-byte row load at byte offset ofs of col[], if the row has entries left there (otherwise zeros, no bytes moved).
+static __device__ __forceinline__ v4i rs_row_load(__amdgpu_buffer_rsrc_t col_rs, uint32_t ofs, bool inside)
+{
+    return __builtin_amdgcn_raw_buffer_load_b128(col_rs, (int)(inside ? ofs : 0xFFFFFFF0u), 0, 0);
+}
+
+template <bool WIN>
 __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                  const int64_t *__restrict__ fixw, int32_t n_nodes,
                                                                  const int64_t *__restrict__ keys, int64_t n,
@@ -33,6 +81,7 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
     extern __shared__ __attribute__((aligned(16))) uint32_t bm[];          // RS_BITS / 32 words
     __shared__ unsigned long long s_starts[RS_CHUNK / 64];
     __shared__ long long s_sum[RS_CHUNK];
+    __shared__ uint32_t s_vb[RS_CHUNK], s_vl[RS_CHUNK];                    // the chunk's rows N(v): first entry, length
     __shared__ unsigned int s_c;
     const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
     constexpr int W = RS_THREADS / 64;
@@ -68,11 +117,27 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
         if (c >= n_chunks) break;
         const int64_t c0 = c * RS_CHUNK;
         const int cn = (int)(n - c0 < RS_CHUNK ? n - c0 : RS_CHUNK);
-        // run starts inside the chunk
+        // The chunk's descriptors, once: thread t loads key t and the rowptr words of its v and its u -- 256 chains of two
+        // latencies side by side -- and leaves (first entry, length) of N(v) in LDS, so that a pair's first row load starts from
+        // two LDS words.  The same key gives the run starts, and the thread remembers whether its pair is this kernel's.
+        bool my_long = false;
         if (tid < RS_CHUNK) {
             s_sum[tid] = 0ll;
-            bool start = false;
-            if (tid < cn) start = tid == 0 || (keys[c0 + tid] >> 32) != (keys[c0 + tid - 1] >> 32);
+            const bool have = tid < cn;
+            const int64_t key = keys[c0 + (have ? tid : 0)];
+            const int32_t u = (int32_t)(key >> 32), v = (int32_t)(key & 0xFFFFFFFFll);
+            int32_t pu = __shfl_up(u, 1);                    // (the wave's first lane reads its predecessor's key itself)
+            if (lane == 0 && tid > 0 && have) pu = (int32_t)(keys[c0 + tid - 1] >> 32);
+            const bool start = have && (tid == 0 || u != pu);
+            uint32_t vb = 0u, vl = 0u;
+            if (have) {
+                // (32-bit entry indices: nnz < 2^30)
+                vb = (uint32_t)rowptr[v];
+                vl = (uint32_t)rowptr[v + 1] - vb;
+                my_long = rowptr[u + 1] - rowptr[u] > RS_SHORT;
+            }
+            s_vb[tid] = vb;
+            s_vl[tid] = vl;
             const unsigned long long m = __ballot(start);
             if (lane == 0) s_starts[wib] = m;
         }
@@ -96,73 +161,55 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void rescore_runs_kernel(const
                 s = e;
                 continue;
             }
-            for (int32_t wlo = 0; wlo < n_nodes; wlo += RS_BITS) {
+            for (int32_t wlo = 0; wlo < (WIN ? n_nodes : 1); wlo += RS_BITS) {
                 // N(u) inside the id window -> bits (rows ascend; a plain scan of the row is cheap next to the pairs)
-                for (int64_t i = ub + tid; i < ue; i += RS_THREADS) {
+                for (uint32_t i = (uint32_t)ub + tid; i < (uint32_t)ue; i += RS_THREADS) {     // (nnz < 2^30)
                     const uint32_t x = (uint32_t)(col[i] - wlo);
-                    if (x < (uint32_t)RS_BITS) atomicOr(&bm[x >> 5], 1u << (x & 31));
+                    if (!WIN || x < (uint32_t)RS_BITS) atomicOr(&bm[x >> 5], 1u << (x & 31));
                 }
                 __syncthreads();
-                // two pairs per wave, one per half: the rows N(v) are short (a few hundred entries), so half a wave with four
-                // loads in flight per lane covers a row in two or three trips, and twice as many pairs are in flight per CU
+                // (the window's weights: at most RS_BITS * 8 bytes)
+                const int32_t wn = n_nodes - wlo < RS_BITS ? n_nodes - wlo : RS_BITS;
+                const __amdgpu_buffer_rsrc_t fix_rs = eps_raw_rsrc(fixw + wlo, wn * 8);
+                // two pairs per wave, one per half: a half wave covers 256 entries of its row N(v) per trip -- two 16-byte loads a
+                // lane (a quarter of the vector-memory instructions of one-entry loads for the same bytes: the rows are what this
+                // kernel streams, 8.8 GB per step on the bench graph) -- and the trip count is the longer row's, wave-uniform.
+                // A trip is three dependent latencies (rows, bitmap words, weights); the other waves of the CU hide them.  Loading
+                // the next trip's rows under the current trip's look-ups needs more than 64 VGPRs without scratch, and measured
+                // slower where it was tried (NOTES, "Re-scoring trips").
                 for (int p0 = s + 2 * wib; p0 < e; p0 += 2 * W) {
                     const int pi = p0 + (lane >> 5);
                     const bool live = pi < e;
-                    const int32_t v = live ? (int32_t)(keys[c0 + pi] & 0xFFFFFFFFll) : 0;
-                    // (32-bit entry indices: nnz < 2^30 -- r06: the 64-bit index arithmetic and sixteen 64-bit partial sums per lane
-                    //  had the kernel at 94 VGPRs = ONE 1024-thread workgroup per CU; at <= 64 two are resident and the waves that
-                    //  hide this kernel's three dependent latencies per trip double)
-                    const uint32_t vb = live ? (uint32_t)rowptr[v] : 0u, ve = live ? (uint32_t)rowptr[v + 1] : 0u;
                     const int hl = lane & 31;
+                    const uint32_t vb = s_vb[live ? pi : s], vl = live ? s_vl[pi] : 0u;
+                    // (the longer of the wave's two rows, as a scalar: the trip loop is a uniform one and says so to the compiler)
+                    const uint32_t vl_a = (uint32_t)__builtin_amdgcn_readlane((int)vl, 0), vl_b = (uint32_t)__builtin_amdgcn_readlane((int)vl, 32);
+                    const uint32_t longest = vl_a > vl_b ? vl_a : vl_b;
+                    // rem: entries the row has from this lane's first one of the trip on; ofs: that entry's byte offset in col[]
+                    int rem = (int)vl - 4 * hl;
+                    uint32_t ofs = (vb + 4u * (uint32_t)hl) * 4u;
                     long long acc = 0ll;
-                    uint32_t longest = ve - vb;
-                    {
-                        const uint32_t o = (uint32_t)__shfl_xor((int)longest, 32);
-                        longest = o > longest ? o : longest;
-                    }
-                    // (16-byte loads, four entries a lane: a quarter of the vector-memory instructions of one-entry loads for the
-                    //  same bytes -- the rows are what this kernel streams, 8.8 GB per step on the bench graph)
                     for (uint32_t off = 0; off < longest; off += 32 * RS_NB) {     // (uniform trip count over the wave)
-                        v4i wv[RS_NB / 4];
-#pragma unroll
-                        for (int b = 0; b < RS_NB / 4; ++b) {
-                            const uint32_t i = vb + off + (uint32_t)(b * 128 + 4 * hl);
-                            wv[b] = __builtin_amdgcn_raw_buffer_load_b128(col_rs, (int)(i < ve ? i * 4u : 0xFFFFFFF0u), 0, 0);
-                        }
-                        // (the weight gathers of a trip in batches of RS_GB: all of a batch's loads issued before any is added)
-#pragma unroll
-                        for (int h = 0; h < RS_NB / RS_GB; ++h) {
-                            long long add[RS_GB];
-#pragma unroll
-                            for (int bb = 0; bb < RS_GB; ++bb) {
-                                const int b = h * RS_GB + bb;
-                                const uint32_t i = vb + off + (uint32_t)((b >> 2) * 128 + 4 * hl + (b & 3));
-                                const int32_t w = wv[b >> 2][b & 3];
-                                const uint32_t x = (uint32_t)(w - wlo);
-                                const bool hit = i < ve && x < (uint32_t)RS_BITS && ((bm[x >> 5] >> (x & 31)) & 1u);
-                                add[bb] = hit ? (long long)fixw[w] : 0ll;
-                            }
-#pragma unroll
-                            for (int bb = 0; bb < RS_GB; ++bb) acc += add[bb];
-                        }
+                        const v4i w0 = rs_row_load(col_rs, ofs, rem > 0), w1 = rs_row_load(col_rs, ofs + 512u, rem > 128);
+                        __builtin_amdgcn_sched_barrier(0);     // (both loads issue before the first one's look-ups start)
+                        acc += rs_trip<WIN>(bm, fix_rs, wlo, w0, w1, rem);
+                        rem -= 32 * RS_NB;
+                        ofs += 32 * RS_NB * 4;
                     }
 #pragma unroll
                     for (int d = 16; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
                     if (hl == 0 && live) s_sum[pi] += acc;
                 }
                 __syncthreads();
-                for (int64_t i = ub + tid; i < ue; i += RS_THREADS) {
+                for (uint32_t i = (uint32_t)ub + tid; i < (uint32_t)ue; i += RS_THREADS) {
                     const uint32_t x = (uint32_t)(col[i] - wlo);
-                    if (x < (uint32_t)RS_BITS) bm[x >> 5] = 0u;
+                    if (!WIN || x < (uint32_t)RS_BITS) bm[x >> 5] = 0u;
                 }
                 __syncthreads();
             }
             s = e;
         }
-        if (tid < cn) {
-            const int32_t u = (int32_t)(keys[c0 + tid] >> 32);
-            if (rowptr[u + 1] - rowptr[u] > RS_SHORT) out[c0 + tid] = (float)((double)s_sum[tid] * (1.0 / (double)(1ll << 40)));
-        }
+        if (tid < cn && my_long) out[c0 + tid] = (float)((double)s_sum[tid] * (1.0 / (double)(1ll << 40)));
         __syncthreads();
     }
 }
@@ -283,16 +330,19 @@ static int rescore_runs_launch(const int64_t *rowptr, const int32_t *col, const 
     const int rc = eps_take_counters8(&counter, s, "eps_rescore_runs");
     if (rc) return rc;
     const size_t lds = (size_t)(n_nodes < RS_BITS ? ((n_nodes + 31) >> 5) : (RS_BITS >> 5)) * 4 + 16;
-    if (hipFuncSetAttribute((const void *)rescore_runs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    // (two instantiations: an id space of one bitmap window needs no window arithmetic per entry)
+    auto kernel = n_nodes > RS_BITS ? rescore_runs_kernel<true> : rescore_runs_kernel<false>;
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         eps_set_error("eps_rescore_runs: cannot reserve %zu bytes of LDS", lds);
         return EPS_ELAUNCH;
     }
     int64_t blocks = (n + RS_CHUNK - 1) / RS_CHUNK;
-    const int64_t per_cu = (160 * 1024 - 2048) / (int64_t)(lds + 2560);            // workgroups the LDS lets a CU hold
+    // workgroups the LDS lets a CU hold: next to the bitmap a workgroup has 4.2 KB of its own (sums, chunk descriptors, run starts)
+    const int64_t per_cu = (160 * 1024 - 2048) / (int64_t)(lds + 4608);
     const int64_t cap = (int64_t)eps_num_cus() * (per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(rescore_runs_kernel, dim3((unsigned)blocks), dim3(RS_THREADS), lds, s, rowptr, col, fixw, (int32_t)n_nodes, keys,
-                       n, out, counter, n_dev);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RS_THREADS), lds, s, rowptr, col, fixw, (int32_t)n_nodes, keys, n, out, counter,
+                       n_dev);
     {
         // (a wave per RSS_TRIPS windows of 64 keys: a short list does not start waves that find no window)
         const int64_t per_block = (int64_t)(RSS_THREADS / 64) * 64 * RSS_TRIPS;
