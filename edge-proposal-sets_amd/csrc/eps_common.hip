@@ -100,7 +100,7 @@ int eps_take_counters8(unsigned int **counters, hipStream_t stream, const char *
 // The units, once: every source of the library but this one (csrc/Makefile: SRCS) defines eps_warm_<unit>; the declarations
 // and the calls below both come from this list (tests/test_abi.py holds it to SRCS).
 #define EPS_UNITS(X) \
-    X(graph_prep) X(csr_merge) X(scan_pieces) X(scan_tables) X(scan_heads) X(rescore) \
+    X(graph_prep) X(csr_merge) X(scan_pieces) X(scan_light) X(scan_tables) X(scan_heads) X(rescore) \
     X(pair_intersect) X(pair_grouped) X(expand_score) X(filter_scan) X(spmm_csr) \
     X(gemm_f32) X(dense_cn) X(mlp_decode) X(mlp_decode_bf16) X(mlp_decode_train) X(topk_keys) X(topk_select) X(segment_topk) \
     X(tail_sort) X(rows_by_score) X(katz_pairs) X(katz_columns) X(local_index) X(cosine_cn) X(cosine_cn_bwd) X(pair_cn_list) X(local_community) X(sketch) \

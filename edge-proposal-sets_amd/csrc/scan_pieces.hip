@@ -52,66 +52,9 @@
 #define SP_MODE_RATIO 2270u     // fixed cost of a piece in hashed-path units (the planner's direct-vs-packed choice); r05: 1000 / 4000 re-measured
 #define SP_MODE_RATIO_WIDE 8000u   // ... in a plan for sketch launches (eps_scan_plan, variant bit 24)
 #define SP_BATCH 8              // columns per ticket in the light tail of the column order
-#define SP_EM 128               // slots of the per-workgroup set of ids a SKETCH piece has reported (a power of two)
 #define SP_G 1                  // units (of 4 entries) a lane looks up, loads and inserts together
 
-struct sp_params {
-    const int64_t *rowptr;
-    const int32_t *col;
-    const int32_t *revpos;
-    const uint32_t *fx32;       // screening weight per node (>= 1); weighted graphs: unused
-    const float *val;           // stored values A[.,.] (weighted graphs: HV) or NULL
-    const float *node_w;        // float node weights (weighted graphs): a path's term is (A[u,w] * A[v,w]) * node_w[w]
-    float up;                   // weighted graphs: 2^shift * (1 + 2^-20), the scale of the per-row factor
-    const uint16_t *cuts;       // [n_nodes][SP_M]
-    const uint32_t *wpaths;     // [n_nodes][SP_M] two-hop half paths of column v per id window (per-graph table) or NULL
-    const int32_t *bounds;      // [SP_M + 1]
-    const int32_t *columns;
-    int32_t n_columns;
-    int32_t n_nodes;
-    uint32_t col_bytes;
-    int32_t table_bits;         // slots = 1 << table_bits (keys) + as many values
-    uint32_t piece_paths;       // a hash piece holds at most this many paths (<= slots / 2)
-    const uint32_t *ssum;       // [n_nodes] sum of fx32 over the node's neighbours (an upper bound of any of its pairs' sums) or NULL
-    const uint32_t *smax;       // [SP_M + 1] largest ssum among the ids >= bounds[k] (0 for k = SP_M); NULL with ssum
-    uint32_t packed_paths;      // a PACKED hash piece holds at most this many paths (<= slots: key and sum share a word)
-    int32_t packed_dmax;        // ... and may drop at most this many low bits of the screening weights
-    const uint32_t *pptr;       // [n_nodes + 1] first plan record of column v (per-graph plan table) or NULL: the kernel plans itself
-    const uint4 *plan;          // one record per piece: x = paths | kind bits, y = k0 | k1 << 8 | pq << 16, z = na | nb << 16, w = lo
-    uint32_t mode_ratio;        // fixed cost of a piece in units of (a hashed path's cost - a direct path's cost)
-    int32_t shift;              // screening fixed point: 2^-shift
-    float scale;                // 2^-shift: screening sum -> approximate score
-    unsigned int *next_col;
-    eps_survivors *out;
-    unsigned int *status;       // bit 1: a hash table filled up (cannot happen within the piece limits; backstop); bit 2: a column's
-                                //        skipped head weighs as much as the bar (the head table was built for a higher bar: nothing valid);
-                                //        bit 3: a sketch piece's set of reported ids filled up (the launch is void); bit 4: sketch pieces ran
-    const uint4 *colrec;        // [n_columns][2] or NULL: what a column's set-up reads of five tables, in hand-out order (one 32-byte load
-                                //        at the ticket's index instead of a chain id -> row start / head / row sum / plan pointer):
-                                //        {v, rowptr[v], degree, head rows | head weight, row sum, first plan record, pieces}
-    const uint32_t *rowrec;     // [n_nodes][32] or NULL: per node ONE 128-byte line with everything the walk wants of a row -- words
-                                //        0..15 its 32 cuts, word 16 its first entry (rowptr), word 17 its screening weight (eps_scan_row_records)
-    uint32_t wide_paths;        // r06, plans for sketch launches: a packed piece of a column of <= wide_rows rows may hold this many paths (it will
-    int32_t wide_rows;          //      run as a sketch piece: no keys, no sum field -- only the unit bitmap's range bounds it); 0 = off
-    uint32_t sketch;            // r06: PACKED pieces of single-round columns under a bar keep no keys (see SP_EM): 0 = off
-    uint32_t batch_from;        // tickets below stand for one column, tickets from here on for SP_BATCH consecutive ones (>= n_columns: none)
-    const uint4 *pack;          // [nnz][2] or NULL (r06; with plan + row records): per stored entry (v, j), in CSR order, everything a
-                                //        single-round column's set-up gathers for it: {w, rowptr[w], fx32[w], revpos | cut of v's FIRST piece in
-                                //        row w << 16} {cuts of v's pieces 1..8 in row w, 16 bits each} -- one contiguous stream per column
-                                //        instead of neighbour ids -> one 128-byte row-record line per neighbour (eps_scan_column_pack)
-    const uint2 *heads;         // [n_nodes] or NULL: column v does NOT walk its first heads[v].x rows (its heaviest hub neighbours under
-                                //        hubs-first labels); heads[v].y = the sum of their screening weights.  See eps_scan_heads.
-};
-
 typedef short sp_v2s __attribute__((ext_vector_type(2)));
-
-// Hash of an id: Fibonacci hashing.  The table index is taken from the TOP of the 32-bit product, the probe step from the
-// middle, the pass of a partitioned window from the bottom.  (A full-rate 24 x 24-bit multiply was measured instead of the
-// quarter-rate 32-bit one: its weaker mixing lengthens the probe sequences -- 38.0 vs 30.7 ms per launch.)
-__device__ __forceinline__ uint32_t sp_mix(uint32_t x) { return x * 0x9E3779B1u; }
-__device__ __forceinline__ uint32_t sp_mix2(uint32_t x) { return x * 0x85EBCA6Bu; }      // (the sketch pieces' second table)
-// (2026-10-20: both slot indices of a sketch piece from ONE full-rate 24 x 24-bit multiply -- top bits and the bits below them -- were
-//  measured against these two quarter-rate products: the main launch 6394 vs 6377 us, NOTES "Scan sweeps")
 
 typedef unsigned short sp_v2us __attribute__((ext_vector_type(2)));
 
@@ -1256,7 +1199,7 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
                      const float *node_w, const uint16_t *cuts, const uint32_t *wpaths, const uint32_t *ssum, const uint32_t *smax,
                      const uint32_t *pptr, const uint32_t *plan, const uint32_t *heads, const uint32_t *rowrec, const uint32_t *pack,
                      const int32_t *bounds, int64_t n_nodes, int64_t nnz, const int32_t *columns, const uint32_t *colrec, int64_t n_columns, int64_t batch_from,
-                     int32_t shift, int32_t variant, eps_survivors *out, uint32_t *status, void *stream)
+                     int64_t light_from, int32_t shift, int32_t variant, eps_survivors *out, uint32_t *status, void *stream)
 {
     EPS_REQUIRE(n_nodes >= 0 && n_columns >= 0 && nnz >= 0, "eps_scan_screen: negative size");
     EPS_REQUIRE(status, "eps_scan_screen: null pointer");
@@ -1280,6 +1223,10 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
     EPS_REQUIRE(!colrec || plan, "eps_scan_screen: column records come with the plan table they were built from");
     EPS_REQUIRE((pptr == nullptr) == (plan == nullptr) && ((uintptr_t)plan & 15) == 0, "eps_scan_screen: pptr and plan come together, 16-byte aligned");
     const int T = sp_threads_of[variant], bits = sp_bits_of[variant];
+    // The light zone (scan_light.hip): columns[light_from, n_columns) go one per wave through the lean kernel, on tables of 4096
+    // words; the piece kernel runs columns[0, light_from) as ever.
+    if (light_from < 0 || light_from > n_columns) light_from = n_columns;
+    const int64_t n_main = light_from;
     unsigned int *counter = nullptr;
     const int rc = eps_take_counter(&counter, s, "eps_scan_screen");
     if (rc) return rc;
@@ -1300,8 +1247,8 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
     p.pack = (const uint4 *)pack;
     p.colrec = (const uint4 *)colrec;
     p.columns = columns;
-    p.n_columns = (int32_t)n_columns;
-    p.batch_from = batch_from < 0 || batch_from > n_columns ? (uint32_t)n_columns : (uint32_t)batch_from;
+    p.n_columns = (int32_t)n_main;
+    p.batch_from = batch_from < 0 || batch_from > n_main ? (uint32_t)n_main : (uint32_t)batch_from;
     p.sketch = val || !(sketch_arg & 1u) ? 0u : sketch_arg;
     p.col_bytes = (uint32_t)(nnz * 4);
     p.scale = ldexpf(1.0f, -shift);
@@ -1309,7 +1256,7 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
     p.out = out;
     p.status = status;
     int64_t blocks = (int64_t)eps_num_cus() * sp_per_cu[variant];
-    if (blocks > n_columns) blocks = n_columns;
+    if (blocks > n_main) blocks = n_main;
     const size_t lds = ((size_t)(2 << bits) + 4 * (size_t)(T + 1) + 8) * 4 + (SP_UBITS / 32) * 6 + 32;
     void (*kern)(sp_params) =
         val ? (variant == 0 ? scan_piece_kernel<512, true, false, false> : variant == 1 ? scan_piece_kernel<1024, true, false, false>
@@ -1329,9 +1276,15 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
         eps_set_error("eps_scan_screen: cannot reserve %zu bytes of LDS", lds);
         return EPS_ELAUNCH;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(T), lds, s, p);
-    EPS_CHECK_LAUNCH("eps_scan_screen");
-    return EPS_OK;
+    EPS_REQUIRE(n_main == n_columns || (full && pack && p.sketch),
+                "eps_scan_screen: a light zone comes with the main launch's tables (plan, records, heads, pack) and sketch pieces (bit 16)");
+    if (n_main > 0) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(T), lds, s, p);
+        EPS_CHECK_LAUNCH("eps_scan_screen");
+    }
+    // (same stream, same list, same status word; the light kernel draws its tickets on a counter of its own)
+    p.n_columns = (int32_t)n_columns;
+    return sl_launch(p, (uint32_t)light_from, (uint32_t)n_columns, 12, s);
 }
 
 extern "C" int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const int32_t *revpos, const uint32_t *fx32,
@@ -1339,8 +1292,8 @@ extern "C" int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const 
                                const uint32_t *smax_or_null, const uint32_t *pptr_or_null, const uint32_t *plan_or_null,
                                const uint32_t *heads_or_null, const uint32_t *rowrec_or_null, const uint32_t *pack_or_null,
                                const int32_t *bounds, int64_t n_nodes, int64_t nnz,
-                               const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from, int32_t shift,
-                               int32_t variant,
+                               const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from,
+                               int64_t light_from, int32_t shift, int32_t variant,
                                eps_survivors *out, uint32_t *status, void *stream)
 {
     EPS_REQUIRE(!pack_or_null || (plan_or_null && rowrec_or_null && ((uintptr_t)pack_or_null & 15) == 0),
@@ -1350,7 +1303,7 @@ extern "C" int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const 
     EPS_REQUIRE(!heads_or_null || plan_or_null, "eps_scan_screen: a head table comes with the plan table built for it");
     return sp_launch(rowptr, col, nullptr, revpos, fx32, nullptr, cuts, wpaths, ssum_or_null, smax_or_null, pptr_or_null,
                      plan_or_null, heads_or_null, rowrec_or_null, pack_or_null, bounds, n_nodes, nnz, columns, colrec_or_null, n_columns,
-                     batch_from, shift, variant, out, status, stream);
+                     batch_from, light_from, shift, variant, out, status, stream);
 }
 
 // The same scan on a SYMMETRIC adjacency with stored values (val[e] == val[mirror of e]); node_w = the float node weights.
@@ -1362,7 +1315,7 @@ extern "C" int eps_scan_screen_weighted(const int64_t *rowptr, const int32_t *co
 {
     EPS_REQUIRE(n_columns == 0 || n_nodes == 0 || (val && node_w), "eps_scan_screen_weighted: null pointer");
     return sp_launch(rowptr, col, val, revpos, nullptr, node_w, cuts, wpaths, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     bounds, n_nodes, nnz, columns, nullptr, n_columns, n_columns, shift, variant, out, status, stream);
+                     bounds, n_nodes, nnz, columns, nullptr, n_columns, n_columns, n_columns, shift, variant, out, status, stream);
 }
 
 // (one empty kernel per translation unit: launching it makes the HIP runtime load this unit's code object -- eps_warm_up)

@@ -66,6 +66,9 @@ SKETCH_MIN_PATHS = 1.5        # ... when the bar is at least this many of the HE
 SKETCH_SET = 0                # slots of a sketch piece's set of reported ids (a power of two <= 64; 0 = the kernel's 128): tests shrink it
 LAZY_PLAN = True              # the whole-graph plan table (no skipped heads) is built when a launch first wants it; the bar sample plans itself
 BATCH_MIN_COLUMNS = 1 << 16   # lists shorter than this are handed out one column at a time throughout
+LIGHT_COLUMNS = True          # the main launch hands its light single-piece columns to the lean kernel (csrc/scan_light.hip; see light_split)
+LIGHT_ROWS = 64               # ... columns of at most this many rows (one lane per row)
+LIGHT_KEYS = 2048             # ... whose one piece holds at most this many paths + known edges (a table of <= 4096 words per wave)
 BATCH_PATHS = 1 << 13      # columns of a heaviest-first list with fewer half paths are handed out eight per ticket (see batch_from)
 
 
@@ -436,7 +439,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
 class HeadTables:
     """What a launch with skipped heads brings (one set per budget): the head table, the window paths and the plan of the rows
     that are still walked, and that plan's dropped weight bits."""
-    __slots__ = ("budget", "heads", "wpaths", "plan", "d_used", "live", "n_hub", "pack", "wide")
+    __slots__ = ("budget", "heads", "wpaths", "plan", "d_used", "live", "n_hub", "pack", "wide", "light")
 
     def __init__(self, budget, heads, wpaths, plan, d_used, n_hub=0, wide=False):
         self.budget, self.heads, self.wpaths, self.plan, self.d_used = budget, heads, wpaths, plan, d_used
@@ -444,6 +447,7 @@ class HeadTables:
         self.n_hub = n_hub           # hub rows the heads were cut from (a graph's second scan widens the table: rebuilt then)
         self.pack = None             # ops.scan_column_pack of this plan (see column_pack)
         self.live = {}               # (rank, world) -> this rank's columns without the DEAD ones (see live_columns)
+        self.light = {}              # column list -> its partition into main and light zones (see light_split)
 
 
 HUB_TABLE_BYTES = 2 << 30   # the hub row bitmaps of a graph take at most this much (ppa-like: 16384 rows x 72 KB = 1.2 GB of 288)
@@ -553,6 +557,48 @@ def column_pack(g: CSRGraph, screen: Screen, ht: HeadTables) -> Optional[torch.T
     return ht.pack
 
 
+class LightSplit:
+    """A launch's column list as the main launch takes it: ``columns`` = the list's main columns, order kept (heaviest first),
+    then its light ones, order kept as well; ``main`` = the view ``columns[:light_from]`` (one object: batch_from memoises per
+    list object); ``light_from`` = where the light zone begins."""
+    __slots__ = ("source", "columns", "main", "light_from")
+
+    def __init__(self, source, columns, light_from):
+        self.source, self.columns = source, columns
+        self.main = columns if light_from >= columns.numel() else columns[:light_from]
+        self.light_from = int(light_from)
+
+
+def light_split(g: CSRGraph, screen: Screen, ht: HeadTables, columns: torch.Tensor, sketch: bool) -> LightSplit:
+    """Which columns of ``columns`` the lean kernel takes (csrc/scan_light.hip: one wave per column, no workgroup barrier), decided
+    once per head table and list on the host and cached on the head table: a column is LIGHT when the launch runs sketch pieces and
+    brings plan, column and row records and the pack, and the column has exactly one plan record, of the packed kind, at most
+    LIGHT_ROWS rows and at most LIGHT_KEYS paths + known edges -- the piece kernel's rule bits = smallest b with 2^b >= 2 x (paths +
+    known edges) then gives a table of at most 4096 words.  Anything else (a graph's first scan: no pack; a retry without sketch
+    pieces; stored values; no bar; LIGHT_COLUMNS off): no light zone, light_from = len(columns), the list as it is."""
+    on = bool(LIGHT_COLUMNS and sketch and columns.numel() and variant_is_main(g, screen) and column_pack(g, screen, ht) is not None)
+    key = (columns.data_ptr(), columns.numel(), on, LIGHT_ROWS, LIGHT_KEYS)
+    hit = ht.light.get(key)
+    if hit is None or hit.source is not columns:
+        while len(ht.light) >= 8:
+            ht.light.pop(next(iter(ht.light)))
+        if not on:
+            hit = LightSplit(columns, columns, columns.numel())
+        else:
+            c = columns.long()
+            pptr = ht.plan[0].to(torch.int64).bitwise_and(0xFFFFFFFF)
+            first = pptr[c]
+            one = (pptr[c + 1] - first) == 1
+            rec = ht.plan[1][first.clamp(max=ht.plan[1].shape[0] - 1)].to(torch.int64).bitwise_and(0xFFFFFFFF)
+            keys = (rec[:, 0] & 0x3FFFFFFF) + (rec[:, 2] >> 16) - (rec[:, 2] & 0xFFFF)
+            light = one & ((rec[:, 0] >> 30) == 1) & ((g.rowptr[c + 1] - g.rowptr[c]) <= min(LIGHT_ROWS, 64)) & (keys <= min(LIGHT_KEYS, 2048))
+            order = torch.sort(light.to(torch.int64), stable=True)[1]            # (a STABLE sort keeps each zone's order)
+            n_main = int(columns.numel() - light.sum().item())                  # (one host read, once per head table and list)
+            hit = LightSplit(columns, columns[order].contiguous(), n_main)
+        ht.light[key] = hit
+    return hit
+
+
 def _heads_for(g: CSRGraph, screen: Screen, bar, wide_for=None) -> Optional[HeadTables]:
     """The head tables for a launch under ``bar`` (1-element device tensor): the set the last launch used, without looking at the
     bar -- the kernel itself refuses a head as heavy as the bar (status bit 2), and scan_topk compares budget and bar after
@@ -634,12 +680,14 @@ def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, bo
         if screen is not None and heads is not None:
             bounds, cuts = screen_tables(g)
             walked = ops.Survivors(walked_capacity, threshold, g.device, prefill=False)
+            split = light_split(g, screen, heads, columns, sketch)
+            columns = split.columns
             ops.scan_screen(g.rowptr, g.col, reverse_positions(g), screen.fx32, cuts, bounds, g.n_rows, columns, screen.shift, walked,
                             out.status, screen_variant(g) | ((ops.SCAN_SKETCH | SKETCH_SET << 17) if sketch else 0) | (ops.SCAN_WIDE if heads.wide else 0), None, None, heads.wpaths, screen.ssum, screen.smax,
                             heads.plan, heads.heads,
-                            batch_from(g, columns), screen.rowrec,
+                            batch_from(g, split.main), screen.rowrec,
                             column_records(g, screen, columns, heads.plan, heads.heads, heads.live, ("colrec", columns.data_ptr(), columns.numel())),
-                            column_pack(g, screen, heads) if variant_is_main(g, screen) else None)
+                            column_pack(g, screen, heads) if variant_is_main(g, screen) else None, split.light_from)
             # (the refine kernel hands the walk's candidate counter on to `out` itself: no copy launch)
             ops.scan_refine(walked, heads.heads, hub_rows(g), screen.fx32, g.rowptr, g.col, g.n_rows, screen.shift, out)
             out.walked_slots = walked.rec[1:2]

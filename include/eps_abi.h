@@ -256,6 +256,7 @@ int eps_filter_scan(const int64_t *rowptr, const int32_t *col, const int32_t *re
 
 /* ---- the same threshold scan in ONE pass over the two-hop paths (r03) ------------------------------------------------------
  * csrc/scan_pieces.hip: the piece kernel, its planner and the launch (eps_scan_screen[_weighted], eps_scan_plan[_rewalk]);
+ * csrc/scan_light.hip: the lean kernel of the main launch's light single-piece columns (launched by eps_scan_screen: light_from);
  * csrc/scan_tables.hip: the builders of the tables a launch reads (eps_scan_windows / _bounds / _cuts / _window_paths[_columns] /
  * _screen_weights / _row_sums / _row_records / _column_pack); csrc/rescore.hip: the exact re-scoring of the survivors
  * (eps_rescore_runs[_dev], eps_rescore_weighted).
@@ -334,8 +335,14 @@ int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const int32_t *re
                     const uint32_t *smax_or_null, const uint32_t *pptr_or_null, const uint32_t *plan_or_null,
                     const uint32_t *heads_or_null, const uint32_t *rowrec_or_null, const uint32_t *pack_or_null, const int32_t *bounds,
                     int64_t n_nodes, int64_t nnz,
-                    const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from, int32_t shift,
+                    const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from,
+                    int64_t light_from, int32_t shift,
                     int32_t variant, eps_survivors *out, uint32_t *status, void *stream);
+/* light_from (csrc/scan_light.hip; n_columns or more, or negative: no light zone): columns[light_from, n_columns) are LIGHT --
+ * exactly one plan record, of the packed kind, at most 64 rows, paths + known edges <= 2048 -- and go one per WAVE through a lean kernel launched by the same call on the same stream, after the piece
+ * kernel has run columns[0, light_from): the same sketch-piece semantics, the same list and status word, tickets of eight columns on
+ * a counter of its own.  Only with the main launch's tables (plan, records, heads, pack) and bit 16 of `variant`; batch_from counts
+ * within columns[0, light_from).  A column that does not meet the bounds sets status bit 1 and is left out (a backstop). */
 /* pack (optional, r06; the main launch only: variant 2 with plan table, row / column records, heads and sum bounds; 16-byte
  * aligned): eps_scan_column_pack's table -- 32 bytes per stored entry (v, j) in CSR order: {col, rowptr[col] (low word), fx32[col],
  * revpos | cut of column v's FIRST piece in row col << 16} {the cuts of v's pieces 1..8 in that row, 16 bits each}.  A column of
