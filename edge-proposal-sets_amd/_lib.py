@@ -55,7 +55,8 @@ SIGNATURES = {
     "eps_scan_screen_weights": (_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "eps_scan_window_paths": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "eps_scan_window_paths_columns": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
-    "eps_scan_screen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "eps_scan_screen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "eps_scan_lean_blocks_per_cu": (_int, []),
     "eps_scan_column_pack": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "eps_scan_row_records": (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "eps_scan_heads": (_int, [_vp, _vp, _vp, _i64, _i32, _c.c_uint32, _i32, _vp, _vp]),

@@ -40,9 +40,15 @@
 // Four workgroups of 256 threads per CU (variant 2) is the measured best: independent workgroups overlap each other's
 // barrier-separated phases; __launch_bounds__(T, 4) keeps the fourth wave per SIMD (130 VGPRs instead of 128 cost 25-100 %).
 // Symmetry, the survivor record and the dynamic column hand-out are as in filter_scan.hip.
+// The step's main launch is three launches of one call (eps_amd.scan.light_split: GENERAL | LEAN | LIGHT): the generic body over the
+// columns of several rounds, the LEAN body (template flag below) over the single-round columns of direct and sketch pieces -- 75 % of
+// the bench graph's live columns, 77 % of its walked paths; compiled for those three piece kinds it has no scratch and a third of the
+// scalar spills, and spends the freed registers on a second unit in flight per lane -- and scan_light.hip's kernel over the light
+// single-piece columns.  Same stream, same list, same status word, a ticket counter each.
 #include "eps_common.h"
 #include "scan_common.h"
 #include <string.h>
+#include <atomic>
 
 #define SP_EMPTY 0u             // an empty key word; a key is stored as id + 1, so a clean table is all zeros in BOTH modes
 #define SP_MAXP (SP_M + 1)
@@ -53,6 +59,10 @@
 #define SP_MODE_RATIO_WIDE 8000u   // ... in a plan for sketch launches (eps_scan_plan, variant bit 24)
 #define SP_BATCH 8              // columns per ticket in the light tail of the column order
 #define SP_G 1                  // units (of 4 entries) a lane looks up, loads and inserts together
+#define SP_LEAN_ROWS 256        // rows of a column of the lean body at most: one round at the 256-thread geometry
+#define SP_LEAN_T 256           // ... threads of its workgroup (320, five waves per SIMD at 96 registers: 5340 against 4736 us for its zone)
+#define SP_LEAN_G 2             // ... units a lane keeps in flight there: the registers the lean body frees (105 -> 128, no scratch)
+#define SP_LEAN_CHUNK 2048u     // ... survivor slots per reservation there (survivors of these columns are rare: see the kernel)
 
 typedef short sp_v2s __attribute__((ext_vector_type(2)));
 
@@ -174,19 +184,29 @@ __device__ __forceinline__ int sp_plan_column(const sp_params &p, int32_t v, int
 // and none of the branches on them -- scalar registers, which the generic body spills by the hundred (111 in r05).
 // SK (r06): the launch may run packed pieces as SKETCH pieces (p.sketch); without it that code is compiled out -- it costs the
 // other pieces registers (VGPR spills 0 -> 4, SGPR 40 -> 75: a hashed-only launch 8.96 -> 9.1 ms).
-template <int T, bool HV, bool FULL, bool PACK, bool SK = false>
+// LEAN: the body for the main launch's single-round columns (eps_amd.scan.lean_columns: at most SP_LEAN_ROWS rows, every plan record
+// direct or packed, every piece within one range of the unit bitmap; FULL, PACK and SK, under a bar).  Such a column keeps its rows
+// in registers and runs three kinds of piece -- direct 16-bit, direct 32-bit, sketch -- so the rounds loop and the gathering
+// describe, the packed walk with its straggler loop, the two-word hash walk with its partitioned passes and its sweep, and the loop
+// over the ranges of the unit bitmap are compiled out: what they cost the columns that never run them is registers (see the
+// resource table in profiles/scan_single/kernel_resources.txt).  A column or piece the host's rule excludes is left out and says so
+// in the status word (bit 1, as in scan_light.hip): scan_topk repeats such a launch without zones.
+template <int T, bool HV, bool FULL, bool PACK, bool SK = false, bool LEAN = false>
 __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (4 waves per SIMD: <= 128 VGPRs, the LDS share decides the rest)
 {
+    static_assert(!LEAN || (!HV && FULL && PACK && SK), "the lean body serves the main launch's tables only");
+    constexpr int G = LEAN ? SP_LEAN_G : SP_G;            // units a lane looks up, loads and inserts together
+    constexpr int ROWS = LEAN ? SP_LEAN_ROWS : T;          // rows of a round at most (the row descriptors)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int slots = 1 << p.table_bits;
     uint32_t *tkey = lds;                    // [slots]  hash mode: key (node id) or SP_EMPTY
     uint32_t *tval = lds + slots;            // [slots]  hash mode: screening sum.  Direct mode: lds[0 .. 2 slots) are the sums
     // row descriptors of the round, one uint4 per (dense) row: x = first entry of the row's segment (index into col[]),
     // y = entries of the segment, z = screening weight of the row's node, w = first 4-entry unit of the row
-    uint4 *r_desc = (uint4 *)(lds + 2 * slots);          // [T + 1]
+    uint4 *r_desc = (uint4 *)(lds + 2 * slots);          // [ROWS + 1]
     // (offsets in words off `lds`, never through an integer cast: a pointer that loses the LDS address space turns its reads
     //  into FLAT loads, which count on vmcnt and make every look-up drain the row loads in flight)
-    uint32_t *ubits = lds + ((2 * slots + 4 * (T + 1) + 3) & ~3);      // [SP_UBITS / 32] bit s: a row starts at unit s (of the range)
+    uint32_t *ubits = lds + ((2 * slots + 4 * (ROWS + 1) + 3) & ~3);      // [SP_UBITS / 32] bit s: a row starts at unit s (of the range)
     uint16_t *wrank = (uint16_t *)(ubits + SP_UBITS / 32);               // [SP_UBITS / 32] rows that start before the word
     __shared__ unsigned long long s_alloc;   // units << 32 | rows handed out to the waves of a round (one 64-bit LDS add per wave)
     __shared__ int s_rbase;
@@ -220,8 +240,14 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
     //  constant there; a caller that passes heads without a bar still gets every survivor, through single slots)
     const bool no_bar = !FULL && thr32 <= 1u;
     const bool raw_sums = FULL || p.heads != nullptr;
-    const uint32_t chunk = no_bar && direct_ids > 8192u ? direct_ids : 8192u;
+    // (LEAN: a second launch's workgroups take a first reservation each, most of which stays empty -- 8192 slots each were 8.4 M
+    //  more slots for eps_scan_refine to read, 0.11 ms of the step; a piece asks for at most 1024)
+    const uint32_t chunk = LEAN ? SP_LEAN_CHUNK : no_bar && direct_ids > 8192u ? direct_ids : 8192u;
     const int32_t my_bound = p.bounds[lane <= SP_M ? lane : SP_M];      // lane k holds window boundary k (the plan runs in wave 0)
+    if (LEAN && thr32 >= SP_FLAG) {          // (backstop: a lean zone comes under a bar -- without one a packed record is no sketch piece)
+        if (tid == 0) atomicOr(p.status, 2u);
+        return;
+    }
 
     for (int i = tid; i < 2 * slots; i += T) lds[i] = 0u;
     for (int i = tid; i < SP_UBITS / 32; i += T) ubits[i] = 0u;
@@ -265,8 +291,8 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
         }
         const int32_t *__restrict__ vcol = p.col + vb;
         const int32_t *__restrict__ vrev = p.revpos + vb;
-        const int rounds = (dv + T - 1) / T;
-        const bool single = rounds == 1;
+        const int rounds = LEAN ? 1 : (dv + T - 1) / T;
+        const bool single = LEAN || rounds == 1;
         // Skipped head (eps_scan_heads): the first xv rows of the column are not walked; whatever they could add to a pair of
         // this column is at most tv, so a slot passes at thr32 - tv and eps_scan_refine adds the exact head term afterwards.
         // (the plan table that comes with a head table counts the walked rows only: the two are used together or not at all, so a
@@ -286,6 +312,10 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
             // this column can pass (a quarter of the ppa-like graph's columns at K = 4 M: a tenth of the pieces, 4 % of the paths.
             // Launches with heads only: a plain launch counts every candidate of its columns)
             if ((FULL || p.ssum) && thr32 < SP_FLAG && ((FULL || p.colrec) ? crb.y : p.ssum[v]) < thr32) bad_head = true;
+        }
+        if (LEAN && dv > ROWS) {                 // (backstop: the host's split sends single-round columns only)
+            if (tid == 0) atomicOr(p.status, 2u);
+            bad_head = true;
         }
         if (dv > 0 && v > 0 && !bad_head) {
             uint32_t my_w = 0, my_rev = 0, my_base = 0, my_fx = 0;      // this thread's row (of the last round)
@@ -364,6 +394,10 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                 const int k0 = s_pk0[pi], k1 = s_pk1[pi];
                 const int na = s_pna[pi], nb = s_pnb[pi];
                 const uint32_t info = s_pinfo[pi];
+                if (LEAN && (info >> 30) == 0u) {            // (backstop, uniform: a two-word hash piece is not for this body)
+                    if (tid == 0) atomicOr(p.status, 2u);
+                    continue;
+                }
                 const bool direct = (info >> 31) != 0u;                                   // direct, either kind
                 const bool d16 = !HV && (info >> 30) == 3u;
                 // r06 -- SKETCH: a packed piece of a single-round column under a bar keeps NO keys.  What a packed piece pays is not the
@@ -376,8 +410,8 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                 // reports the ids whose estimate reaches the bar, once each (s_em), unless they are neighbours of v.  Exact
                 // re-scoring follows as for every survivor.  Such a piece does not count its candidates.
                 const bool packed_kind = !HV && (info >> 30) == 1u;
-                const bool sketch = SK && packed_kind && single && p.sketch != 0u && thr_v < SP_FLAG;      // (uniform)
-                const bool packed = packed_kind && !sketch;
+                const bool sketch = LEAN ? packed_kind : SK && packed_kind && single && p.sketch != 0u && thr_v < SP_FLAG;      // (uniform)
+                const bool packed = !LEAN && packed_kind && !sketch;
                 const bool quant = packed || d16;                                        // weights drop pk_d low bits
                 const uint32_t ppaths = info & 0x3FFFFFFFu;
                 const uint32_t pq = quant ? s_pq[pi] : 0u;
@@ -389,11 +423,11 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                 const uint32_t pkeys = ppaths + (uint32_t)(nb - na);           // slots the piece can need: paths + known edges
                 // (closed forms, no loops: hipcc unrolls and vectorises even a three-trip scalar loop into a hundred instructions)
                 int plog = 0;                                            // parts = 2^plog
-                if (!direct && !packed && !sketch && pkeys > p.piece_paths) {
+                if (!LEAN && !direct && !packed && !sketch && pkeys > p.piece_paths) {
                     const uint32_t q = (pkeys + p.piece_paths - 1u) / p.piece_paths;      // >= 2 (piece_paths is a power of two: a shift)
                     plog = 32 - __clz((int)(q - 1u)) + 1;                // next power of two, doubled (random split: aim at a quarter load)
                 }
-                const uint32_t parts = 1u << plog;
+                const uint32_t parts = LEAN ? 1u : 1u << plog;
                 int bits;
                 {
                     const uint32_t per = (pkeys + parts - 1u) >> plog;
@@ -472,7 +506,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                     if (atomicCAS(&lds[h], 0u, word) == 0u) break;
                                     h = (h + st) & mask;
                                 }
-                            } else {
+                            } else if (!LEAN) {
                                 const uint32_t mix = sp_mix(u);
                                 if ((mix & (parts - 1u)) == part) {
                                     uint32_t h = mix >> (32 - bits);
@@ -539,8 +573,12 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 out_val[i] = -__builtin_inff();
                             }
                         }                                                // (tid 0 closes the range after the walk's barrier)
-                        const int total = (int)(s_alloc >> 32);
-                        for (uint32_t ulo = 0; ulo < (uint32_t)total; ulo += SP_UBITS) {       // (one range unless > 32 k paths)
+                        int total = (int)(s_alloc >> 32);
+                        if (LEAN && total > SP_UBITS) {                  // (backstop, uniform: one range by the host's rule)
+                            if (tid == 0) atomicOr(p.status, 2u);
+                            total = SP_UBITS;
+                        }
+                        for (uint32_t ulo = 0; ulo < (uint32_t)total && (!LEAN || ulo == 0u); ulo += SP_UBITS) {       // (one range unless > 32 k paths)
                             const uint32_t uhi = ulo + SP_UBITS < (uint32_t)total ? ulo + SP_UBITS : (uint32_t)total;
                             if (ulo > 0u) {
                                 for (int i = tid; i < SP_UBITS / 32; i += T) ubits[i] = 0u;
@@ -565,13 +603,13 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 *(uint2 *)(wrank + 4 * lane) = pk;
                                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                             }
-                        // ---- walk: lane = one 4-entry unit.  A GROUP of SP_G units per lane is looked up, loaded and inserted
-                        // together: its look-ups run side by side, its loads are in flight together, and its 4 x SP_G table updates
+                        // ---- walk: lane = one 4-entry unit.  A GROUP of G units per lane is looked up, loaded and inserted
+                        // together: its look-ups run side by side, its loads are in flight together, and its 4 x G table updates
                         // share the probing loop (a trip costs one LDS round trip however many of them are still pending).
-                        auto fetch_group = [&](int it0, sp_unit (&f)[SP_G]) {
-                            int lo[SP_G];
+                        auto fetch_group = [&](int it0, sp_unit (&f)[G]) {
+                            int lo[G];
 #pragma unroll
-                            for (int q = 0; q < SP_G; ++q) {
+                            for (int q = 0; q < G; ++q) {
                                 const uint32_t sr = (uint32_t)((it0 + q) * T + tid);       // unit, relative to the range
                                 const uint32_t wd = sr < SP_UBITS ? sr >> 5 : 0u;
                                 const uint32_t bits = ubits[wd];
@@ -580,7 +618,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 lo[q] = lo[q] < 0 ? 0 : lo[q];
                             }
 #pragma unroll
-                            for (int q = 0; q < SP_G; ++q) {
+                            for (int q = 0; q < G; ++q) {
                                 // (every LDS read unconditional, the range test a select: a read inside a branch makes hipcc
                                 //  drain the loads in flight at the branch)
                                 const int s = (int)ulo + (it0 + q) * T + tid;
@@ -601,11 +639,11 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                             if (!HV) return f.fx;
                             return (uint32_t)__builtin_ceilf(f.a4[e] * __builtin_bit_cast(float, f.fx)) + 1u;
                         };
-                        auto consume_group = [&](const sp_unit (&f)[SP_G]) {
+                        auto consume_group = [&](const sp_unit (&f)[G]) {
                             if (sketch) {
                                 const uint32_t half = 1u << (bits - 1);
 #pragma unroll
-                                for (int q = 0; q < SP_G; ++q)
+                                for (int q = 0; q < G; ++q)
 #pragma unroll
                                     for (int e = 0; e < 4; ++e)
                                         if (e < f[q].nvalid) {
@@ -615,7 +653,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                         }
                             } else if (d16) {
 #pragma unroll
-                                for (int q = 0; q < SP_G; ++q)
+                                for (int q = 0; q < G; ++q)
 #pragma unroll
                                     for (int e = 0; e < 4; ++e)
                                         if (e < f[q].nvalid) {
@@ -624,7 +662,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                         }
                             } else if (direct) {
 #pragma unroll
-                                for (int q = 0; q < SP_G; ++q)
+                                for (int q = 0; q < G; ++q)
 #pragma unroll
                                     for (int e = 0; e < 4; ++e)
                                         if (e < f[q].nvalid) atomicAdd(&lds[(uint32_t)(f[q].u4[e] - lo_id)], path_fx(f[q], e));
@@ -633,11 +671,11 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 // left -- an entry in six at load 1/2 -- is finished ONE entry per lane and trip: the trips a wave
                                 // needs are set by its unluckiest entry (the longest probe sequence among 256), and a trip that
                                 // looks at one entry costs a quarter of one that steps through four mostly idle ones.
-                                constexpr int E = 4 * SP_G;
+                                constexpr int E = 4 * G;
                                 uint32_t lid[E], h[E], mixv[E], old[E];
                                 uint32_t pend = 0u;
 #pragma unroll
-                                for (int q = 0; q < SP_G; ++q) pend |= ((1u << f[q].nvalid) - 1u) << (4 * q);
+                                for (int q = 0; q < G; ++q) pend |= ((1u << f[q].nvalid) - 1u) << (4 * q);
 #pragma unroll
                                 for (int i = 0; i < E; ++i) {
                                     const uint32_t id = (uint32_t)f[i >> 2].u4[i & 3];
@@ -703,12 +741,12 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                         pend = 0u;
                                     }
                                 }
-                            } else {
-                                constexpr int E = 4 * SP_G;
+                            } else if (!LEAN) {
+                                constexpr int E = 4 * G;
                                 uint32_t key[E], h[E], mixv[E];
                                 uint32_t pend = 0u;
 #pragma unroll
-                                for (int q = 0; q < SP_G; ++q) pend |= ((1u << f[q].nvalid) - 1u) << (4 * q);
+                                for (int q = 0; q < G; ++q) pend |= ((1u << f[q].nvalid) - 1u) << (4 * q);
 #pragma unroll
                                 for (int i = 0; i < E; ++i) {
                                     const uint32_t id = (uint32_t)f[i >> 2].u4[i & 3];
@@ -775,17 +813,17 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                         };
                         {
                             const int n_iter = (int)(uhi - ulo + T - 1) / T;      // uniform over the workgroup
-                            sp_unit fa[SP_G], fb[SP_G];
+                            sp_unit fa[G], fb[G];
                             fetch_group(0, fa);
-                            if (n_iter <= SP_G) {          // one group (every hash piece: <= piece_paths / 4 units): nothing to overlap
+                            if (n_iter <= G) {          // one group (every hash piece: <= piece_paths / 4 units): nothing to overlap
                                 consume_group(fa);
                             } else {
                                 // (refills are unconditional -- a group past the end is empty units at an out-of-range address:
                                 //  no traffic -- because a conditional refill becomes a phi copy and hipcc then drains vmcnt)
-                                for (int it0 = 0; it0 < n_iter; it0 += 2 * SP_G) {
-                                    fetch_group(it0 + SP_G, fb);
+                                for (int it0 = 0; it0 < n_iter; it0 += 2 * G) {
+                                    fetch_group(it0 + G, fb);
                                     consume_group(fa);
-                                    fetch_group(it0 + 2 * SP_G, fa);
+                                    fetch_group(it0 + 2 * G, fa);
                                     consume_group(fb);
                                 }
                             }
@@ -831,33 +869,33 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 }
                                 atomicOr(p.status, 8u);                   // the set is full: the launch is void (the host repeats it without sketch pieces)
                             };
-                            auto look = [&](const sp_unit (&f)[SP_G]) {
-                                uint32_t est[4 * SP_G];
+                            auto look = [&](const sp_unit (&f)[G]) {
+                                uint32_t est[4 * G];
 #pragma unroll
-                                for (int i = 0; i < 4 * SP_G; ++i) {
+                                for (int i = 0; i < 4 * G; ++i) {
                                     const uint32_t id = (uint32_t)f[i >> 2].u4[i & 3];
                                     const uint32_t ea = lds[sp_mix(id) >> (33 - bits)], eb = lds[half + (sp_mix2(id) >> (33 - bits))];
                                     est[i] = ea < eb ? ea : eb;
                                 }
 #pragma unroll
-                                for (int i = 0; i < 4 * SP_G; ++i)
+                                for (int i = 0; i < 4 * G; ++i)
                                     if ((i & 3) < f[i >> 2].nvalid && est[i] >= thr_v) report((uint32_t)f[i >> 2].u4[i & 3], est[i]);
                             };
-                            sp_unit fa[SP_G], fb[SP_G];
+                            sp_unit fa[G], fb[G];
                             fetch_group(0, fa);
-                            if (n_iter <= SP_G) {
+                            if (n_iter <= G) {
                                 look(fa);
                             } else {
-                                for (int it0 = 0; it0 < n_iter; it0 += 2 * SP_G) {
-                                    fetch_group(it0 + SP_G, fb);
+                                for (int it0 = 0; it0 < n_iter; it0 += 2 * G) {
+                                    fetch_group(it0 + G, fb);
                                     look(fa);
-                                    fetch_group(it0 + 2 * SP_G, fa);
+                                    fetch_group(it0 + 2 * G, fa);
                                     look(fb);
                                 }
                             }
                             }
                         }
-                            if (uhi < (uint32_t)total) eps_lds_barrier();       // (the next range rewrites the start bits)
+                            if (!LEAN && uhi < (uint32_t)total) eps_lds_barrier();       // (the next range rewrites the start bits)
                         }
                         eps_lds_barrier();        // the next round / the scan follows: descriptors and table updates are complete
                         // (leave the start bits and the hand-out counter clean for the next describe; a barrier separates them from
@@ -979,7 +1017,7 @@ __global__ __launch_bounds__(T, 4) void scan_piece_kernel(sp_params p)      // (
                                 }
                             }
                         }
-                    } else {
+                    } else if (!LEAN) {
                         // (the candidates were counted when their keys went in; the key words are only read for a survivor)
                         for (uint32_t i0 = 0; i0 < scan_slots; i0 += 4u * SP_SB * T) {
                             uint4 s4[SP_SB];
@@ -1189,6 +1227,28 @@ extern "C" int eps_scan_plan_rewalk(const uint32_t *plan, int64_t n_rec, int32_t
     return EPS_OK;
 }
 
+// Dynamic LDS of the piece kernel (its layout is told at the top of the kernel): both halves of the 2^bits-slot table, the descriptors
+// of `rows` rows + 1 (the generic body: its threads; the lean body: SP_LEAN_ROWS whatever its threads), start bits and word ranks.
+static size_t sp_lds_bytes(int bits, int rows) { return ((size_t)(2 << bits) + 4 * (size_t)(rows + 1) + 8) * 4 + (SP_UBITS / 32) * 6 + 32; }
+
+// Workgroups of the lean body a CU holds, as the runtime counts them (4 = what the LDS share allows; asked once), or a negative error.
+extern "C" int eps_scan_lean_blocks_per_cu(void)
+{
+    static std::atomic<int> cached{0};
+    int per_cu = cached.load();
+    if (per_cu < 1) {
+        const void *lean = (const void *)scan_piece_kernel<SP_LEAN_T, false, true, true, true, true>;
+        const size_t lds = sp_lds_bytes(sp_bits_of[2], SP_LEAN_ROWS);
+        if (hipFuncSetAttribute(lean, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lean, SP_LEAN_T, lds) != hipSuccess || per_cu < 1) {
+            eps_set_error("eps_scan_screen: no occupancy figure for the lean body at %zu bytes of LDS", lds);
+            return EPS_ELAUNCH;
+        }
+        cached.store(per_cu);
+    }
+    return per_cu;
+}
+
 // ---- launch -------------------------------------------------------------------------------------------------------------
 // variant: 0 = 512 threads, 8192-slot table (two workgroups per CU); 1 = 1024 threads, 16384 slots (one per CU);
 //          2 = 256 threads, 4096 slots (four per CU).  Also measured (27.8 ms for variant 2 at the time): 256 threads / 8192 slots
@@ -1199,7 +1259,8 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
                      const float *node_w, const uint16_t *cuts, const uint32_t *wpaths, const uint32_t *ssum, const uint32_t *smax,
                      const uint32_t *pptr, const uint32_t *plan, const uint32_t *heads, const uint32_t *rowrec, const uint32_t *pack,
                      const int32_t *bounds, int64_t n_nodes, int64_t nnz, const int32_t *columns, const uint32_t *colrec, int64_t n_columns, int64_t batch_from,
-                     int64_t light_from, int32_t shift, int32_t variant, eps_survivors *out, uint32_t *status, void *stream)
+                     int64_t lean_from, int64_t lean_batch_from, int64_t light_from, int32_t shift, int32_t variant, eps_survivors *out,
+                     uint32_t *status, void *stream)
 {
     EPS_REQUIRE(n_nodes >= 0 && n_columns >= 0 && nnz >= 0, "eps_scan_screen: negative size");
     EPS_REQUIRE(status, "eps_scan_screen: null pointer");
@@ -1225,8 +1286,11 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
     const int T = sp_threads_of[variant], bits = sp_bits_of[variant];
     // The light zone (scan_light.hip): columns[light_from, n_columns) go one per wave through the lean kernel, on tables of 4096
     // words; the piece kernel runs columns[0, light_from) as ever.
+    // The lean zone: columns[lean_from, light_from) are single-round columns of direct and sketch pieces and go through the LEAN body,
+    // in a launch of its own between the two; the generic body runs columns[0, lean_from).
     if (light_from < 0 || light_from > n_columns) light_from = n_columns;
-    const int64_t n_main = light_from;
+    if (lean_from < 0 || lean_from > light_from) lean_from = light_from;
+    const int64_t n_main = lean_from, n_lean = light_from - lean_from;
     unsigned int *counter = nullptr;
     const int rc = eps_take_counter(&counter, s, "eps_scan_screen");
     if (rc) return rc;
@@ -1257,7 +1321,7 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
     p.status = status;
     int64_t blocks = (int64_t)eps_num_cus() * sp_per_cu[variant];
     if (blocks > n_main) blocks = n_main;
-    const size_t lds = ((size_t)(2 << bits) + 4 * (size_t)(T + 1) + 8) * 4 + (SP_UBITS / 32) * 6 + 32;
+    const size_t lds = sp_lds_bytes(bits, T);
     void (*kern)(sp_params) =
         val ? (variant == 0 ? scan_piece_kernel<512, true, false, false> : variant == 1 ? scan_piece_kernel<1024, true, false, false>
                                                                                        : scan_piece_kernel<256, true, false, false>)
@@ -1277,9 +1341,31 @@ static int sp_launch(const int64_t *rowptr, const int32_t *col, const float *val
         return EPS_ELAUNCH;
     }
     EPS_REQUIRE(n_main == n_columns || (full && pack && p.sketch),
-                "eps_scan_screen: a light zone comes with the main launch's tables (plan, records, heads, pack) and sketch pieces (bit 16)");
+                "eps_scan_screen: a lean or light zone comes with the main launch's tables (plan, records, heads, pack) and sketch pieces (bit 16)");
     if (n_main > 0) {
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(T), lds, s, p);
+        EPS_CHECK_LAUNCH("eps_scan_screen");
+    }
+    if (n_lean > 0) {
+        // (same stream, same list, same status word, a ticket counter of its own; the zone's columns and records start at lean_from)
+        sp_params q = p;
+        const int rc2 = eps_take_counter(&q.next_col, s, "eps_scan_screen");
+        if (rc2) return rc2;
+        q.columns = columns + lean_from;
+        q.colrec = (const uint4 *)colrec + 2 * lean_from;
+        q.n_columns = (int32_t)n_lean;
+        q.batch_from = lean_batch_from < 0 || lean_batch_from > n_lean ? (uint32_t)n_lean : (uint32_t)lean_batch_from;
+        void (*lean)(sp_params) = scan_piece_kernel<SP_LEAN_T, false, true, true, true, true>;
+        const size_t lds_lean = sp_lds_bytes(bits, SP_LEAN_ROWS);
+        const int per_cu = eps_scan_lean_blocks_per_cu();      // (the figure is asked once; the LDS limit is set per call, as above)
+        if (per_cu < 1) return per_cu;
+        if (hipFuncSetAttribute((const void *)lean, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lean) != hipSuccess) {
+            eps_set_error("eps_scan_screen: cannot reserve %zu bytes of LDS", lds_lean);
+            return EPS_ELAUNCH;
+        }
+        int64_t nb = (int64_t)eps_num_cus() * (per_cu < sp_per_cu[variant] ? per_cu : sp_per_cu[variant]);
+        if (nb > n_lean) nb = n_lean;
+        hipLaunchKernelGGL(lean, dim3((unsigned)nb), dim3(SP_LEAN_T), lds_lean, s, q);
         EPS_CHECK_LAUNCH("eps_scan_screen");
     }
     // (same stream, same list, same status word; the light kernel draws its tickets on a counter of its own)
@@ -1293,7 +1379,7 @@ extern "C" int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const 
                                const uint32_t *heads_or_null, const uint32_t *rowrec_or_null, const uint32_t *pack_or_null,
                                const int32_t *bounds, int64_t n_nodes, int64_t nnz,
                                const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from,
-                               int64_t light_from, int32_t shift, int32_t variant,
+                               int64_t lean_from, int64_t lean_batch_from, int64_t light_from, int32_t shift, int32_t variant,
                                eps_survivors *out, uint32_t *status, void *stream)
 {
     EPS_REQUIRE(!pack_or_null || (plan_or_null && rowrec_or_null && ((uintptr_t)pack_or_null & 15) == 0),
@@ -1303,7 +1389,7 @@ extern "C" int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const 
     EPS_REQUIRE(!heads_or_null || plan_or_null, "eps_scan_screen: a head table comes with the plan table built for it");
     return sp_launch(rowptr, col, nullptr, revpos, fx32, nullptr, cuts, wpaths, ssum_or_null, smax_or_null, pptr_or_null,
                      plan_or_null, heads_or_null, rowrec_or_null, pack_or_null, bounds, n_nodes, nnz, columns, colrec_or_null, n_columns,
-                     batch_from, light_from, shift, variant, out, status, stream);
+                     batch_from, lean_from, lean_batch_from, light_from, shift, variant, out, status, stream);
 }
 
 // The same scan on a SYMMETRIC adjacency with stored values (val[e] == val[mirror of e]); node_w = the float node weights.
@@ -1315,7 +1401,7 @@ extern "C" int eps_scan_screen_weighted(const int64_t *rowptr, const int32_t *co
 {
     EPS_REQUIRE(n_columns == 0 || n_nodes == 0 || (val && node_w), "eps_scan_screen_weighted: null pointer");
     return sp_launch(rowptr, col, val, revpos, nullptr, node_w, cuts, wpaths, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     bounds, n_nodes, nnz, columns, nullptr, n_columns, n_columns, n_columns, shift, variant, out, status, stream);
+                     bounds, n_nodes, nnz, columns, nullptr, n_columns, n_columns, n_columns, 0, n_columns, shift, variant, out, status, stream);
 }
 
 // (one empty kernel per translation unit: launching it makes the HIP runtime load this unit's code object -- eps_warm_up)

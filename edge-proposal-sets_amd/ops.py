@@ -966,7 +966,8 @@ def scan_screen(rowptr, col, revpos, fx32, cuts, bounds, n_nodes: int, columns: 
                 node_w: Optional[torch.Tensor] = None, wpaths: Optional[torch.Tensor] = None,
                 ssum: Optional[torch.Tensor] = None, smax: Optional[torch.Tensor] = None, plan=None,
                 heads: Optional[torch.Tensor] = None, batch_from: Optional[int] = None, rowrec: Optional[torch.Tensor] = None,
-                colrec: Optional[torch.Tensor] = None, pack: Optional[torch.Tensor] = None, light_from: Optional[int] = None) -> None:
+                colrec: Optional[torch.Tensor] = None, pack: Optional[torch.Tensor] = None, light_from: Optional[int] = None,
+                lean_from: Optional[int] = None, lean_batch_from: Optional[int] = None) -> None:
     """Launch eps_scan_screen over ``columns``; survivors (screening scores) accumulate in ``out``.  ``val`` / ``node_w``
     (float32 stored values / node weights): the weighted flavour (eps_scan_screen_weighted; ``fx32`` unused).
     ``ssum`` / ``smax`` (int32-bits [N] / [M + 1]; unit-valued graphs): per-node sums of fx32 over the row and their
@@ -980,7 +981,10 @@ def scan_screen(rowptr, col, revpos, fx32, cuts, bounds, n_nodes: int, columns: 
     ``pack`` (``scan_column_pack``; main launch only): the per-column pack built from this plan table and these row records.
     ``light_from`` (``scan.light_split``; main launch with sketch pieces only): ``columns[light_from:]`` are single sketch pieces of
     at most 64 rows and 2048 paths + known edges and take the lean kernel of
-    csrc/scan_light.hip, one column per wave; ``batch_from`` then counts within ``columns[:light_from]``."""
+    csrc/scan_light.hip, one column per wave.
+    ``lean_from`` (``scan.light_split``; under the same conditions): ``columns[lean_from:light_from]`` are single-round columns of direct
+    and sketch pieces and take the piece kernel's LEAN body in a launch of their own; ``lean_batch_from`` counts within that zone as
+    ``batch_from`` does within ``columns[:lean_from]``.  None: no lean zone."""
     pptr, recs = plan if plan is not None else (None, None)
     dev = _need_gpu(rowptr, col, revpos, fx32, cuts, bounds, columns, status, val, node_w, wpaths, ssum, smax, pptr, recs, heads,
                     rowrec, colrec, pack)
@@ -1006,6 +1010,7 @@ def scan_screen(rowptr, col, revpos, fx32, cuts, bounds, n_nodes: int, columns: 
     if val is None:
         _call("eps_scan_screen", dev, rowptr, col, revpos, fx32, cuts, wpaths, ssum, smax, pptr, recs, heads, rowrec, pack,
               bounds, n_nodes, col.numel(), columns, colrec, columns.numel(), -1 if batch_from is None else int(batch_from),
+              -1 if lean_from is None else int(lean_from), -1 if lean_batch_from is None else int(lean_batch_from),
               -1 if light_from is None else int(light_from), int(shift), variant, out.rec, status, timed=timed)
     else:
         _call("eps_scan_screen_weighted", dev, rowptr, col, val, revpos, node_w, cuts, wpaths, bounds, n_nodes, col.numel(),

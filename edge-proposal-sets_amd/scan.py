@@ -69,6 +69,9 @@ BATCH_MIN_COLUMNS = 1 << 16   # lists shorter than this are handed out one colum
 LIGHT_COLUMNS = True          # the main launch hands its light single-piece columns to the lean kernel (csrc/scan_light.hip; see light_split)
 LIGHT_ROWS = 64               # ... columns of at most this many rows (one lane per row)
 LIGHT_KEYS = 2048             # ... whose one piece holds at most this many paths + known edges (a table of <= 4096 words per wave)
+LEAN_COLUMNS = True           # ... and its single-round columns of direct and sketch pieces to the piece kernel's lean body (see lean_columns)
+LEAN_ROWS = 256               # ... columns of at most this many rows (one round of the 256-thread geometry: rows in registers)
+LEAN_UNITS = 8192             # ... whose every piece fits one range of the kernel's unit bitmap (csrc/scan_pieces.hip: SP_UBITS)
 BATCH_PATHS = 1 << 13      # columns of a heaviest-first list with fewer half paths are handed out eight per ticket (see batch_from)
 
 
@@ -439,7 +442,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
 class HeadTables:
     """What a launch with skipped heads brings (one set per budget): the head table, the window paths and the plan of the rows
     that are still walked, and that plan's dropped weight bits."""
-    __slots__ = ("budget", "heads", "wpaths", "plan", "d_used", "live", "n_hub", "pack", "wide", "light")
+    __slots__ = ("budget", "heads", "wpaths", "plan", "d_used", "live", "n_hub", "pack", "wide", "light", "lean_ok")
 
     def __init__(self, budget, heads, wpaths, plan, d_used, n_hub=0, wide=False):
         self.budget, self.heads, self.wpaths, self.plan, self.d_used = budget, heads, wpaths, plan, d_used
@@ -447,7 +450,8 @@ class HeadTables:
         self.n_hub = n_hub           # hub rows the heads were cut from (a graph's second scan widens the table: rebuilt then)
         self.pack = None             # ops.scan_column_pack of this plan (see column_pack)
         self.live = {}               # (rank, world) -> this rank's columns without the DEAD ones (see live_columns)
-        self.light = {}              # column list -> its partition into main and light zones (see light_split)
+        self.light = {}              # column list -> its partition into main, lean and light zones (see light_split)
+        self.lean_ok = None          # bool [N]: the node's column may run in the lean body (see lean_columns)
 
 
 HUB_TABLE_BYTES = 2 << 30   # the hub row bitmaps of a graph take at most this much (ppa-like: 16384 rows x 72 KB = 1.2 GB of 288)
@@ -558,15 +562,40 @@ def column_pack(g: CSRGraph, screen: Screen, ht: HeadTables) -> Optional[torch.T
 
 
 class LightSplit:
-    """A launch's column list as the main launch takes it: ``columns`` = the list's main columns, order kept (heaviest first),
-    then its light ones, order kept as well; ``main`` = the view ``columns[:light_from]`` (one object: batch_from memoises per
-    list object); ``light_from`` = where the light zone begins."""
-    __slots__ = ("source", "columns", "main", "light_from")
+    """A launch's column list as the main launch takes it, in three zones: ``columns`` = the list's general columns, order kept
+    (heaviest first), then its lean ones, then its light ones, order kept in each; ``main`` = the view ``columns[:lean_from]`` and
+    ``lean`` = the view ``columns[lean_from:light_from]`` (one object each: batch_from memoises per list object); ``lean_from`` /
+    ``light_from`` = where the lean / the light zone begins (no lean zone: lean_from = light_from)."""
+    __slots__ = ("source", "columns", "main", "lean", "lean_from", "light_from")
 
-    def __init__(self, source, columns, light_from):
+    def __init__(self, source, columns, light_from, lean_from=None):
         self.source, self.columns = source, columns
-        self.main = columns if light_from >= columns.numel() else columns[:light_from]
         self.light_from = int(light_from)
+        self.lean_from = self.light_from if lean_from is None else int(lean_from)
+        self.main = columns if self.lean_from >= columns.numel() else columns[:self.lean_from]
+        self.lean = columns[self.lean_from:self.light_from]
+
+
+def lean_columns(rows: torch.Tensor, pptr: torch.Tensor, recs: torch.Tensor) -> torch.Tensor:
+    """bool [N]: which nodes' columns the piece kernel's LEAN body can run (csrc/scan_pieces.hip), from the rows per node (int64
+    [N]), the plan pointers (int64 [N + 1]) and the plan records (int64 [P, 4], the words as unsigned numbers): at most LEAN_ROWS rows
+    -- one round, the rows in registers --, every plan record direct (kind bits 11 / 10) or packed (01: it runs as a sketch piece),
+    none a two-word hash piece (00), and every piece within one range of the unit bitmap: a row of a piece adds at most 3/4 of a
+    unit beyond its paths / 4, so paths + 3 x rows <= 4 x LEAN_UNITS is sufficient.  tests/scan_split_truth.py restates it."""
+    n = rows.numel()
+    owner = torch.repeat_interleave(torch.arange(n, device=rows.device), pptr[1:] - pptr[:-1])
+    bad = ((recs[:, 0] >> 30) == 0) | ((recs[:, 0] & 0x3FFFFFFF) + 3 * rows[owner] > 4 * LEAN_UNITS)
+    n_bad = torch.zeros(n, dtype=torch.int64, device=rows.device).index_add_(0, owner, bad.to(torch.int64))
+    return (rows <= LEAN_ROWS) & (n_bad == 0)
+
+
+def zone_order(light: torch.Tensor, lean: torch.Tensor):
+    """(order, lean_from, light_from) of a list whose columns are flagged light / lean (bool, light wins): general | lean | light, each
+    zone in the list's order (a STABLE sort by zone)."""
+    zone = torch.where(light, 2, torch.where(lean, 1, 0))
+    order = torch.sort(zone, stable=True)[1]
+    counts = torch.bincount(zone, minlength=3).tolist()          # (one host read, once per head table and list)
+    return order, counts[0], counts[0] + counts[1]
 
 
 def light_split(g: CSRGraph, screen: Screen, ht: HeadTables, columns: torch.Tensor, sketch: bool) -> LightSplit:
@@ -574,10 +603,12 @@ def light_split(g: CSRGraph, screen: Screen, ht: HeadTables, columns: torch.Tens
     once per head table and list on the host and cached on the head table: a column is LIGHT when the launch runs sketch pieces and
     brings plan, column and row records and the pack, and the column has exactly one plan record, of the packed kind, at most
     LIGHT_ROWS rows and at most LIGHT_KEYS paths + known edges -- the piece kernel's rule bits = smallest b with 2^b >= 2 x (paths +
-    known edges) then gives a table of at most 4096 words.  Anything else (a graph's first scan: no pack; a retry without sketch
-    pieces; stored values; no bar; LIGHT_COLUMNS off): no light zone, light_from = len(columns), the list as it is."""
-    on = bool(LIGHT_COLUMNS and sketch and columns.numel() and variant_is_main(g, screen) and column_pack(g, screen, ht) is not None)
-    key = (columns.data_ptr(), columns.numel(), on, LIGHT_ROWS, LIGHT_KEYS)
+    known edges) then gives a table of at most 4096 words.  Of the rest, the columns ``lean_columns`` admits form the LEAN zone in
+    front of the light one (LEAN_COLUMNS; the same conditions on the launch).  Anything else (a graph's first scan: no pack; a retry
+    without sketch pieces; stored values; no bar; both switches off): no zones, lean_from = light_from = len(columns), the list as it is."""
+    on = bool((LIGHT_COLUMNS or LEAN_COLUMNS) and sketch and columns.numel() and variant_is_main(g, screen)
+              and column_pack(g, screen, ht) is not None)
+    key = (columns.data_ptr(), columns.numel(), on, LIGHT_COLUMNS, LIGHT_ROWS, LIGHT_KEYS, LEAN_COLUMNS, LEAN_ROWS, LEAN_UNITS)
     hit = ht.light.get(key)
     if hit is None or hit.source is not columns:
         while len(ht.light) >= 8:
@@ -592,9 +623,17 @@ def light_split(g: CSRGraph, screen: Screen, ht: HeadTables, columns: torch.Tens
             rec = ht.plan[1][first.clamp(max=ht.plan[1].shape[0] - 1)].to(torch.int64).bitwise_and(0xFFFFFFFF)
             keys = (rec[:, 0] & 0x3FFFFFFF) + (rec[:, 2] >> 16) - (rec[:, 2] & 0xFFFF)
             light = one & ((rec[:, 0] >> 30) == 1) & ((g.rowptr[c + 1] - g.rowptr[c]) <= min(LIGHT_ROWS, 64)) & (keys <= min(LIGHT_KEYS, 2048))
-            order = torch.sort(light.to(torch.int64), stable=True)[1]            # (a STABLE sort keeps each zone's order)
-            n_main = int(columns.numel() - light.sum().item())                  # (one host read, once per head table and list)
-            hit = LightSplit(columns, columns[order].contiguous(), n_main)
+            if not LIGHT_COLUMNS:
+                light = torch.zeros_like(light)
+            if LEAN_COLUMNS:
+                if ht.lean_ok is None or ht.lean_ok[1] != (LEAN_ROWS, LEAN_UNITS):
+                    recs = ht.plan[1].to(torch.int64).bitwise_and(0xFFFFFFFF)
+                    ht.lean_ok = (lean_columns(g.rowptr[1:] - g.rowptr[:-1], pptr, recs), (LEAN_ROWS, LEAN_UNITS))
+                lean = ht.lean_ok[0][c]
+            else:
+                lean = torch.zeros_like(light)
+            order, lean_from, light_from = zone_order(light, lean)
+            hit = LightSplit(columns, columns[order].contiguous(), light_from, lean_from)
         ht.light[key] = hit
     return hit
 
@@ -664,14 +703,17 @@ def one_pass_available(g: CSRGraph) -> bool:
 
 
 def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, both: bool = False, screen=None,
-            heads: Optional[HeadTables] = None, walked_capacity: int = 0, sample_key=None, sketch: bool = False) -> ops.Survivors:
+            heads: Optional[HeadTables] = None, walked_capacity: int = 0, sample_key=None, sketch: bool = False,
+            zones: bool = True) -> ops.Survivors:
     """``screen`` (a Screen) -> the one-pass kernel (screening scores in ``val``), else eps_filter_scan (exact scores).
     ``heads``: the launch skips the columns' heads (its list -- ``walked_capacity`` slots -- holds walked sums) and
     eps_scan_refine completes them into the list that is returned: the same survivors and scores as without heads, compact;
-    ``walked_slots`` (device word) = slots the walked list handed out."""
+    ``walked_slots`` (device word) = slots the walked list handed out.  ``zones`` False: the list goes through the piece kernel's
+    generic body as it is (no lean, no light zone); ``zoned`` on the result = the launch had a zone."""
     # (the piece kernel marks the unused slots of its reservations itself: no fill, readers stop at the slot counter)
     out = ops.Survivors(capacity, threshold, g.device, scores_only, both, prefill=screen is None)
     out.walked_slots = None
+    out.zoned = False
     if screen is not None:
         out.status = torch.empty(1, dtype=torch.int32, device=g.device)      # (cleared by eps_scan_screen itself)
         if not columns.numel():
@@ -680,14 +722,16 @@ def _launch(g, fixw, columns, threshold, capacity, scores_only: bool = False, bo
         if screen is not None and heads is not None:
             bounds, cuts = screen_tables(g)
             walked = ops.Survivors(walked_capacity, threshold, g.device, prefill=False)
-            split = light_split(g, screen, heads, columns, sketch)
+            split = light_split(g, screen, heads, columns, sketch and zones)
+            out.zoned = split.lean_from < columns.numel()
             columns = split.columns
             ops.scan_screen(g.rowptr, g.col, reverse_positions(g), screen.fx32, cuts, bounds, g.n_rows, columns, screen.shift, walked,
                             out.status, screen_variant(g) | ((ops.SCAN_SKETCH | SKETCH_SET << 17) if sketch else 0) | (ops.SCAN_WIDE if heads.wide else 0), None, None, heads.wpaths, screen.ssum, screen.smax,
                             heads.plan, heads.heads,
                             batch_from(g, split.main), screen.rowrec,
                             column_records(g, screen, columns, heads.plan, heads.heads, heads.live, ("colrec", columns.data_ptr(), columns.numel())),
-                            column_pack(g, screen, heads) if variant_is_main(g, screen) else None, split.light_from)
+                            column_pack(g, screen, heads) if variant_is_main(g, screen) else None, split.light_from,
+                            split.lean_from, batch_from(g, split.lean))
             # (the refine kernel hands the walk's candidate counter on to `out` itself: no copy launch)
             ops.scan_refine(walked, heads.heads, hub_rows(g), screen.fx32, g.rowptr, g.col, g.n_rows, screen.shift, out)
             out.walked_slots = walked.rec[1:2]
@@ -1049,6 +1093,7 @@ def _capacity(slots_wanted: int, slack: Optional[int] = None) -> int:
 
 
 # kernel status bits (include/eps_abi.h, eps_scan_screen's *status) that the step looks at; any other bit is a full hash table
+_KS_BACKSTOP = 2                   # a table filled up -- or, in a launch with zones, a column outside its zone's rule (the zones' backstop)
 _KS_HEADS_HIGHER_BAR = 4           # some head is as heavy as the bar: the head table was built for a higher bar
 _KS_SKETCH_SET_FULL = 8            # a sketch piece had more ids to report than its set holds
 _KS_SKETCH_RAN = 16                # sketch pieces ran (informational)
@@ -1101,16 +1146,18 @@ class _Retry:
         self.launches, self.wanted = launches, wanted
         # the walked list holds head_list times the survivor list; whether launches under a bar skip heads / run sketch pieces
         self.head_list, self.use_heads, self.sketch = head_list, use_heads, sketch
+        self.zones = True                 # the main launch splits its list into zones (light_split) until a zone's backstop says no
         # this call's walked-list overflows, head tables built for another bar, launches voided by a full sketch set
         self.head_trouble, self.head_stale, self.sketch_void = head_trouble, head_stale, sketch_void
         # every survivor is re-scored (a pre-filter threshold lay above the job-wide cut); what "estimate" aims the new bar at (x K)
         self.rescore_all, self.safety = rescore_all, None
 
     def verdict(self, table, *, capacity: int, walked_cap: int, head_budget: Optional[int], shift: Optional[int], screened: bool,
-                k2: int, bar_set: bool) -> Verdict:
+                k2: int, bar_set: bool, zoned: bool = False) -> Verdict:
         """Whether a launch's selection IS the job's k2 best pairs ("done") or what the next launch changes, from the status ``table``
         (a StepStatus per rank); ``head_budget`` (table units), ``shift``: None without heads.  The first check that fails names the
-        action: a full sketch set "sketch off" (unknown status bits raise); a void head table "grow walked list" / "rebuild heads" /
+        action: a full sketch set "sketch off"; the backstop bit of a launch that had zones (``zoned``) "zones off" (unknown status
+        bits, and that bit without zones, raise); a void head table "grow walked list" / "rebuild heads" /
         "heads off"; an unsound pre-filter "rescore all" (these repeat the SAME launch); an overflowing list "rescan below cut" /
         "rescan wider" (-inf cut); too few "lower bar" / "drop bar"."""
         launches, head_trouble, head_stale = self.launches, self.head_trouble, self.head_stale
@@ -1124,6 +1171,10 @@ class _Retry:
         if any(t.kernel & _KS_SKETCH_SET_FULL for t in table):
             # (a bar far below what K asks for: the launch is void, the call goes on with hashed packed pieces)
             return again("sketch off", "launches with sketch pieces")
+        if zoned and any(t.kernel & _KS_BACKSTOP for t in table):
+            # (``zoned``: the launch had a lean or a light zone, whose kernels leave out a column the host's split should not have
+            #  sent them and raise the backstop bit: the launch is void, the call goes on with the list as it is)
+            return again("zones off", "launches with lean or light zones")
         if any(t.kernel & ~(_KS_HEADS_HIGHER_BAR | _KS_SKETCH_RAN) for t in table):
             raise ops._lib.EpsError("scan_topk: eps_scan_screen reported a full hash table (status %s)" % [t.kernel for t in table])
         drop_heads = False
@@ -1168,6 +1219,8 @@ class _Retry:
         self.launches, self.head_trouble, self.head_stale = v.launches, v.head_trouble, v.head_stale
         if v.action == "sketch off":
             self.sketch, self.sketch_void = False, self.sketch_void + 1
+        elif v.action == "zones off":
+            self.zones = False
         elif v.action == "grow walked list":
             self.head_list *= 2
         elif v.action == "heads off":
@@ -1370,7 +1423,7 @@ def _step_stats(stats: dict, g: CSRGraph, screen: Optional[Screen], fixw, table,
         g._cache.setdefault("n_candidates", n_cand)
     n_all = 2 * n_cand if ht is None else 2 * candidate_count(g, screen, fixw, rank, world) if stats.get("count", True) else None
     stats.update(candidates=n_all, touched=2 * n_cand, launches=state.launches, survivors=2 * n_sel, heads=ht is not None, shard=shard,
-                 sketch=any(t.kernel & _KS_SKETCH_RAN for t in table), sketch_void=state.sketch_void,
+                 sketch=any(t.kernel & _KS_SKETCH_RAN for t in table), sketch_void=state.sketch_void, zones_off=not state.zones,
                  head_budget=None if ht is None else ht.budget * 2.0 ** -screen.shift,
                  walked_slots=sum(t.walked for t in table) if ht is not None else None, rescored=n_rescored,
                  survivor_slots=sum(min(t.slots, capacity) for t in table), bar=bar)
@@ -1440,7 +1493,8 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
         ht = (_heads_for(g, screen, bar, sketch_for) if state.use_heads and bar is not None else None)
         walked_cap = max(1, min(int(state.head_list * capacity), ops.SURVIVOR_SLOTS_MAX)) if ht is not None else 0
         res = _launch(g, fixw, mine if ht is None else live_columns(g, screen, ht, rank, world), float("-inf") if bar is None else bar,
-                      capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap, sketch=ht is not None and sketch_for(ht.budget))
+                      capacity, both=True, screen=screen, heads=ht, walked_capacity=walked_cap, sketch=ht is not None and sketch_for(ht.budget),
+                      zones=state.zones)
         state.launches += 1
         rows = deal = None
         rows_path = "library"
@@ -1460,7 +1514,8 @@ def scan_topk(g: CSRGraph, node_w: torch.Tensor, k: int, rank: int = 0, world: i
                                               else _cut_from_scores(keys, vals, row, k2, room, world) if exchange
                                               else _cut_local(keys, vals, row, k2, screen is not None, world))
         v = state.verdict(table, capacity=capacity, walked_cap=walked_cap, head_budget=None if ht is None else ht.budget,
-                          shift=None if ht is None else screen.shift, screened=screen is not None, k2=k2, bar_set=bar is not None)
+                          shift=None if ht is None else screen.shift, screened=screen is not None, k2=k2, bar_set=bar is not None,
+                          zoned=res.zoned)
         new_bar = state.apply(v, total_half, world)
         if v.drop_heads:
             screen.head_cur = None

@@ -255,7 +255,8 @@ int eps_filter_scan(const int64_t *rowptr, const int32_t *col, const int32_t *re
                     int64_t workspace_bytes, void *stream);
 
 /* ---- the same threshold scan in ONE pass over the two-hop paths (r03) ------------------------------------------------------
- * csrc/scan_pieces.hip: the piece kernel, its planner and the launch (eps_scan_screen[_weighted], eps_scan_plan[_rewalk]);
+ * csrc/scan_pieces.hip: the piece kernel -- its generic body and the lean body of the main launch's single-round columns (lean_from) --,
+ * its planner and the launch (eps_scan_screen[_weighted], eps_scan_plan[_rewalk]);
  * csrc/scan_light.hip: the lean kernel of the main launch's light single-piece columns (launched by eps_scan_screen: light_from);
  * csrc/scan_tables.hip: the builders of the tables a launch reads (eps_scan_windows / _bounds / _cuts / _window_paths[_columns] /
  * _screen_weights / _row_sums / _row_records / _column_pack); csrc/rescore.hip: the exact re-scoring of the survivors
@@ -336,8 +337,18 @@ int eps_scan_screen(const int64_t *rowptr, const int32_t *col, const int32_t *re
                     const uint32_t *heads_or_null, const uint32_t *rowrec_or_null, const uint32_t *pack_or_null, const int32_t *bounds,
                     int64_t n_nodes, int64_t nnz,
                     const int32_t *columns, const uint32_t *colrec_or_null, int64_t n_columns, int64_t batch_from,
-                    int64_t light_from, int32_t shift,
+                    int64_t lean_from, int64_t lean_batch_from, int64_t light_from, int32_t shift,
                     int32_t variant, eps_survivors *out, uint32_t *status, void *stream);
+/* lean_from (csrc/scan_pieces.hip, the LEAN body; light_from or more, or negative: no lean zone): columns[lean_from, light_from) are
+ * SINGLE-ROUND columns -- at most 256 rows, every plan record direct (16- or 32-bit) or packed (it runs as a sketch piece), every
+ * piece within one range of the unit bitmap (paths + 3 x rows <= 4 x 8192) -- and go through a body of the piece kernel compiled for
+ * exactly that, in a launch of its own on the same stream between the piece kernel's over columns[0, lean_from) and the light
+ * kernel's: the same pieces, list and status word, a ticket counter of its own; lean_batch_from counts within the zone as batch_from
+ * does within columns[0, lean_from).  Under the same conditions as a light zone.  A column or piece outside the rule sets status
+ * bit 1 and is left out (a backstop).
+ * eps_scan_lean_blocks_per_cu: workgroups of that body a compute unit holds at its LDS size, as the runtime counts them (4 is what the
+ * geometry is built for), or a negative error code. */
+int eps_scan_lean_blocks_per_cu(void);
 /* light_from (csrc/scan_light.hip; n_columns or more, or negative: no light zone): columns[light_from, n_columns) are LIGHT --
  * exactly one plan record, of the packed kind, at most 64 rows, paths + known edges <= 2048 -- and go one per WAVE through a lean kernel launched by the same call on the same stream, after the piece
  * kernel has run columns[0, light_from): the same sketch-piece semantics, the same list and status word, tickets of eight columns on
