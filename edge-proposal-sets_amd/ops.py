@@ -795,9 +795,16 @@ HUB_MAX = 16384           # hub rows a graph's bitmap table holds (eps_scan_hub_
                           # ppa-like graph with 4096 / 8192 / 16384 / 32768 rows: 11.27 / 10.40 / 10.00 / 9.87 ms (72 KB per row)
 
 
-def scan_row_records(cuts: torch.Tensor, rowptr: torch.Tensor, fx32: torch.Tensor) -> torch.Tensor:
+SCAN_MAX_NNZ = 1 << 30         # eps_scan_screen's limit; the row records keep rowptr's LOW word and their call takes no nnz: checked here
+
+
+def scan_row_records(cuts: torch.Tensor, rowptr: torch.Tensor, fx32: torch.Tensor, nnz: Optional[int] = None) -> torch.Tensor:
     """int32-bits [N, 32]: per node ONE 128-byte line -- its 32 cuts, its first entry, its screening weight (eps_scan_row_records):
-    what eps_scan_screen gathers per walked row, out of one table instead of three.  Per (graph, weight table)."""
+    what eps_scan_screen gathers per walked row, out of one table instead of three.  Per (graph, weight table).  ``nnz``: the
+    graph's stored entries where the caller has them at hand (col.numel(): no device read) -- the records hold the low 32 bits of
+    rowptr and serve a kernel that refuses nnz >= 2^30, so such a graph is refused here, before any launch."""
+    if nnz is not None and int(nnz) >= SCAN_MAX_NNZ:
+        raise _lib.EpsError(f"scan_row_records: the records keep 32-bit entry positions for eps_scan_screen (nnz < 2^30), got {int(nnz)} entries")
     dev = _need_gpu(cuts, rowptr, fx32)
     _chk(_I16, cuts=cuts); _chk(_I64, rowptr=rowptr); _chk(_I32, fx32=fx32)
     n = fx32.numel()
@@ -875,10 +882,20 @@ def scan_screen_weights(fixw: torch.Tensor, shift: int):
     return out, bad
 
 
+RESCORE_MAX_NNZ = 1 << 30      # eps_rescore_runs[_dev] address col[] with 32-bit byte offsets and take no nnz to check: checked here
+
+
+def _chk_rescore_nnz(who: str, col: torch.Tensor) -> None:
+    if col.numel() >= RESCORE_MAX_NNZ:
+        raise _lib.EpsError(f"{who}: col[] is addressed with 32-bit byte offsets (nnz < 2^30), got {col.numel()} entries")
+
+
 def rescore_runs(rowptr, col, fixw: torch.Tensor, n_nodes: int, keys_by_u: torch.Tensor) -> torch.Tensor:
-    """float32 exact scores of the pairs ``keys_by_u`` = (u << 32) | v, sorted ascending (eps_rescore_runs; unit values)."""
+    """float32 exact scores of the pairs ``keys_by_u`` = (u << 32) | v, sorted ascending (eps_rescore_runs; unit values).
+    A graph of 2^30 stored entries or more is refused (the kernel's 32-bit byte offsets into col[])."""
     dev = _need_gpu(rowptr, col, fixw, keys_by_u)
     _csr(rowptr, col); _chk(_I64, fixw=fixw, keys=keys_by_u)
+    _chk_rescore_nnz("rescore_runs", col)
     out = torch.empty(keys_by_u.numel(), dtype=_F32, device=dev)
     _call("eps_rescore_runs", dev, rowptr, col, fixw, n_nodes, keys_by_u, keys_by_u.numel(), out,
           timed=("rescore_runs", keys_by_u.numel()))
@@ -2376,6 +2393,7 @@ def rescore_runs_dev(rowptr, col, fixw: torch.Tensor, n_nodes: int, keys_by_u: t
     """``rescore_runs`` over the first min(*n_dev, len) keys (eps_rescore_runs_dev); the other outputs are undefined."""
     dev = _need_gpu(rowptr, col, fixw, keys_by_u, n_dev)
     _csr(rowptr, col); _chk(_I64, keys_by_u=keys_by_u, fixw=fixw, n_dev=n_dev)
+    _chk_rescore_nnz("rescore_runs_dev", col)
     out = torch.empty(keys_by_u.numel(), dtype=_F32, device=dev)
     if keys_by_u.numel():
         _call("eps_rescore_runs_dev", dev, rowptr, col, fixw, int(n_nodes), keys_by_u, keys_by_u.numel(), n_dev, out,

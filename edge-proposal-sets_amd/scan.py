@@ -412,7 +412,7 @@ def screen_weights(g0: CSRGraph, g: CSRGraph, perm, node_w: torch.Tensor) -> Scr
                                                    f_lo.view(1), f_hi.view(1)]).tolist()
         bad_h, d_h, min_h = bad_h & 0xFFFFFFFF, d_h & 0xFFFFFFFF, min_h & 0xFFFFFFFF
         usable = fits and bad_h == 0
-        rowrec = ops.scan_row_records(screen_tables(g)[1], g.rowptr, fx32) if usable and one_pass else None
+        rowrec = ops.scan_row_records(screen_tables(g)[1], g.rowptr, fx32, nnz=g.col.numel()) if usable and one_pass else None
         if not usable:
             ssum = smax = plan = plan_build = None
         d_used, w_min = 0, 0.0

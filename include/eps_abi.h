@@ -316,7 +316,11 @@ int32_t eps_scan_windows(void);
  * recur); fixw = eps_fixed_weights(node_w); out[i] = float32 of the exact int64 sum of the 2^-40 fixed-point weights over the
  * common neighbours of pair i -- bit-identical to eps_filter_scan's / eps_expand_fill's score.  Unit-valued adjacency.
  * eps_rescore_weighted: the same for an adjacency with stored values: term = (A[u,w] * A[v,w]) * node_w[w] in float32, each
- * converted to 2^-40 fixed point (eps_expand_fill's weighted score); keys in any order. */
+ * converted to 2^-40 fixed point (eps_expand_fill's weighted score); keys in any order.
+ * LIMIT of eps_rescore_runs and eps_rescore_runs_dev (not of eps_rescore_weighted, which indexes with 64 bits): col[] is addressed
+ * with 32-bit byte offsets and 32-bit entry indices, like eps_scan_screen's -- the graph must hold FEWER THAN 2^30 stored
+ * entries (rowptr[n_nodes] < 2^30).  The two calls take no nnz and cannot check it: the caller must (ops.rescore_runs[_dev]
+ * refuse col.numel() >= 2^30; scan.scan_plausible keeps such graphs away from the scan altogether). */
 int eps_rescore_runs(const int64_t *rowptr, const int32_t *col, const int64_t *fixw, int64_t n_nodes, const int64_t *keys,
                      int64_t n, float *out, void *stream);
 int eps_rescore_weighted(const int64_t *rowptr, const int32_t *col, const float *val, const float *node_w, int64_t n_nodes,
@@ -367,7 +371,10 @@ int eps_scan_column_pack(const int64_t *rowptr, const int32_t *col, const int32_
  * it with plain gathers (eps_amd.scan.column_records). */
 /* eps_scan_row_records: rowrec[w * 32 + 0 .. 15] = the 32 cuts of row w, [16] = rowptr[w] (low word), [17] = fx32[w], rest 0 -- ONE
  * 128-byte line per node with everything eps_scan_screen gathers per walked row (r05: three gathers into three tables were 384
- * bytes of fabric traffic per row for 24 bytes wanted).  Per (graph, weight table); 128-byte aligned; optional for eps_scan_screen. */
+ * bytes of fabric traffic per row for 24 bytes wanted).  Per (graph, weight table); 128-byte aligned; optional for eps_scan_screen.
+ * LIMIT: word 16 keeps the LOW 32 bits of rowptr[w], so the records are right only for a graph of fewer than 2^32 entries; the call
+ * takes no nnz and cannot check it.  Their one reader, eps_scan_screen, refuses nnz >= 2^30; ops.scan_row_records refuses a stated
+ * nnz >= 2^30 (eps_amd.scan passes col.numel()), and eps_amd.scan builds them only for a graph that passed scan_plausible. */
 int eps_scan_row_records(const uint16_t *cuts, const int64_t *rowptr, const uint32_t *fx32, int64_t n_nodes, uint32_t *rowrec,
                          void *stream);
 /* ---- skipped heads (r05; csrc/scan_heads.hip): half of all two-hop paths run through a few thousand hub rows whose weights are
@@ -717,7 +724,7 @@ int eps_select_topk_rows(const int64_t *sel_keys, const float *sel_vals, int64_t
  *          proposal tensor itself: out_pairs[i] = u, out_pairs[out_ld + i] = v, out_scores[i] for the first min(k, 2 m) rows of
  *          the declared order; *n_rows_out_or_null (DEVICE) = that number.  workspace: eps_radix_sort_workspace_bytes(records)
  *          bytes (records = n_max resp. 2 m_max), 256-byte aligned.
- *   eps_rescore_runs_dev: eps_rescore_runs over min(*n_dev, n_max) pairs. */
+ *   eps_rescore_runs_dev: eps_rescore_runs over min(*n_dev, n_max) pairs (the same limit: fewer than 2^30 stored entries). */
 int64_t eps_tail_state_bytes(void);
 /* eps_score_bins / eps_score_hist_into / eps_score_deal_plan: the same selection for a SHARDED step.  Every rank adds the histogram
  * of its re-scored scores to an array of its own (eps_score_bins() words, zeroed by the caller, the same *base on every rank) and
